@@ -6,6 +6,12 @@ ViT-L/14 on synthetic 224x224 images + 77-token texts (BASELINE.json configs[1])
 (weak scaling): --pairs query+candidate pairs per rank, global batch = pairs * n_gpus (4096 at 8 GPUs with the
 default 512).  Prints ONE JSON line on rank 0.
 
+A plain run sets up, runs --warmup untimed and --steps timed steps, and reports them (with the GEMM roofline sampled inside those
+steps).  `--full` adds everything else this file measures or checks, after the headline's steps: the step in the reference's shape,
+the retrieval / embedding / BLIP_FF / CLIP_FF blocks, the CPU baselines and, at N > 1, the collective timings and replica
+checksums.  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs) for output-for-output comparisons of builds:
+every input is seeded, so equal arguments give equal inputs.
+
 Launch (the reference: run_inbatch.sh:50-53, `python -m torch.distributed.run --nproc_per_node=$NPROC train.py`):
   * `python bench.py --gpus N` with no RANK in the environment re-executes itself under
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>`;
@@ -617,6 +623,35 @@ def bench_embed_sharded(dist, dev, world, model_name, items=2048, steps=3):
             "mfma_frac_note": "pair mode, executed FLOPs (packed text tower at the captions' live lengths)"}
 
 
+DUMP_SAMPLE = 1 << 21       # parameter positions sampled per dumped array: 8 MB of float32 each
+
+
+def dump_outputs(path, out, model):
+    """--dump-outputs: what the last timed step hands its caller, as float32 .npy files -- the step's outputs dict (loss, accuracy)
+    and, of the parameters it updated and their gradients (428 M fp32 values at ViT-L/14), the same DUMP_SAMPLE positions drawn
+    with a fixed seed over the named_parameters() order"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float() for k, v in out.items() if isinstance(v, torch.Tensor)}
+    if model is not None:
+        params = [p for _, p in model.named_parameters()]
+        sizes = torch.tensor([p.numel() for p in params], dtype=torch.int64)
+        ends = sizes.cumsum(0)
+        idx = torch.randint(int(ends[-1]), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        cut = torch.searchsorted(idx, ends).tolist()
+        w, g = [], []
+        for i, p in enumerate(params):
+            lo = cut[i - 1] if i else 0
+            if lo == cut[i]:
+                continue
+            local = (idx[lo:cut[i]] - (ends[i] - sizes[i])).to(p.device)
+            w.append(p.detach().reshape(-1)[local].float())
+            g.append(p.grad.reshape(-1)[local].float())
+        arrays["params_sample"], arrays["grads_sample"] = torch.cat(w), torch.cat(g)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
+
+
 def _secondary(name, fn, *a, **kw):
     try:
         r = fn(*a, **kw)
@@ -797,6 +832,10 @@ def main():
     ap.add_argument("--shard-queries", default="64,1024,100000", help="N > 1: global query counts of the sharded retrieval block")
     ap.add_argument("--embed-items", type=int, default=2048, help="items per batch (and rank) of the embedding block")
     ap.add_argument("--check-sharded", action="store_true", help="N > 1 (tests): sharded search == single search over the whole pool")
+    ap.add_argument("--full", action="store_true", help="after the headline line's own steps, also the second timing in the reference's "
+                    "shape, the retrieval / embedding / BLIP_FF / CLIP_FF blocks, the CPU baselines and (N > 1) the collective "
+                    "timings and replica checksums; the --no-* options above thin out this run")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -908,6 +947,8 @@ def main():
             print(f"bench: GEMM sampling failed ({e}); roofline.achieved is null", file=sys.stderr)
             timing = (0.0, 0.0, 0, 0, False)
     loss = float(out["loss"].detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model)
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -917,7 +958,7 @@ def main():
     # the same step in the REFERENCE'S shape -- the text tower on all 77 positions of every caption (clip_model.pack_text = False) and
     # every row through every block (pool_last_block = False): exactly the work the SURVEY 8(d) FLOP count prices
     unpacked = None
-    if not args.dry_run and getattr(model.clip_model, "pack_text", False) and not args.no_unpacked:
+    if args.full and not args.dry_run and getattr(model.clip_model, "pack_text", False) and not args.no_unpacked:
         pool_was = model.clip_model.pool_last_block
         model.clip_model.pack_text, model.clip_model.pool_last_block = False, False
         out = None
@@ -946,14 +987,15 @@ def main():
         rccl = {"backend": dist.get_backend(), "ranks_seen": int(seen.item()),
                 "grad_allreduce": {"overlapped_with_backward": True, "collectives_per_step": int(opt.last_collectives),
                                    "bucket_MB": round((opt.reducer.bucket_elems * 4) / 2**20, 1) if opt.reducer else None}}
-        rccl.update(time_collectives(dist, dev, world, args.pairs, E, flat))
-        if not args.dry_run:     # did the replicas stay identical through the timed steps?  (sum, sum of squares) of every rank
-            from uniir_amd import comm
-            cs = torch.tensor(comm.replica_checksum(model.clip_model), device=dev, dtype=torch.float64)
-            allcs = [torch.zeros_like(cs) for _ in range(world)]
-            dist.all_gather(allcs, cs)
-            rccl["replica_checksums"] = [[float(x) for x in c.cpu()] for c in allcs]
-            rccl["replicas_identical"] = all(torch.equal(c, allcs[0]) for c in allcs)
+        if args.full:
+            rccl.update(time_collectives(dist, dev, world, args.pairs, E, flat))
+            if not args.dry_run:     # did the replicas stay identical through the timed steps?  (sum, sum of squares) of every rank
+                from uniir_amd import comm
+                cs = torch.tensor(comm.replica_checksum(model.clip_model), device=dev, dtype=torch.float64)
+                allcs = [torch.zeros_like(cs) for _ in range(world)]
+                dist.all_gather(allcs, cs)
+                rccl["replica_checksums"] = [[float(x) for x in c.cpu()] for c in allcs]
+                rccl["replicas_identical"] = all(torch.equal(c, allcs[0]) for c in allcs)
 
     result = None
     if rank == 0:
@@ -1042,7 +1084,7 @@ def main():
     del trainer, model, batch, out
     if dev.type == "cuda":
         torch.cuda.empty_cache()
-    if world > 1 and not args.dry_run:      # every rank takes part (collectives inside); rank 0 reports
+    if args.full and world > 1 and not args.dry_run:      # every rank takes part (collectives inside); rank 0 reports
         blocks = {}
         if not args.no_retrieval:
             blocks["retrieval"] = _secondary("retrieval", bench_retrieval_sharded, dist, dev, rank, world, args.shard_rows, 768, 10,
@@ -1051,7 +1093,7 @@ def main():
             blocks["embed"] = _secondary("embed", bench_embed_sharded, dist, dev, world, args.model, args.embed_items)
         if rank == 0:
             result.update(blocks)
-    if rank == 0 and world == 1 and not args.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.dry_run:
         if not args.no_retrieval:
             result["retrieval"] = _secondary("retrieval", bench_retrieval, dev)
             if isinstance(result["retrieval"], dict) and "error" not in result["retrieval"]:

@@ -24,7 +24,7 @@ def _run(argv, env_extra=None):
 
 
 def test_gpus_flag_spawns_that_many_ranks_and_reports_them():
-    p, lines = _run(["--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1", "--pairs", "8"])
+    p, lines = _run(["--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1", "--pairs", "8", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1, p.stdout          # exactly one JSON line, from rank 0
     r = json.loads(lines[0])
@@ -46,6 +46,16 @@ def test_single_rank_dry_run_needs_no_launcher():
     assert r["n_gpus"] == 1 and "rccl" not in r and r["config"]["global_batch"] == 4
 
 
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: what the last timed step returned, as float32 .npy files (the dry run's stand-in step returns its loss)"""
+    import numpy as np
+    p, lines = _run(["--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "0", "--pairs", "4", "--dump-outputs", str(tmp_path / "out")])
+    assert p.returncode == 0, p.stderr[-2000:]
+    r = json.loads(lines[0])
+    loss = np.load(tmp_path / "out" / "loss.npy")
+    assert loss.dtype == np.float32 and float(loss) == r["config"]["final_loss"]
+
+
 def test_world_size_mismatch_is_an_error():
     p, _ = _run(["--gpus", "4", "--dry-run"], {"RANK": "0", "WORLD_SIZE": "2", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1",
                                              "MASTER_PORT": "29999"})
@@ -56,11 +66,13 @@ import pytest
 
 
 @pytest.mark.gpu
-def test_bench_line_schema_on_the_device():
+def test_bench_line_schema_on_the_device(tmp_path):
     """the real (non dry-run) bench path at a small configuration: one JSON line with the contract's keys, a live GEMM sample
-    from the library-side timing hook, the measured-traffic record only for the configuration it was measured on"""
+    from the library-side timing hook, the measured-traffic record only for the configuration it was measured on; a plain run
+    holds none of --full's blocks, and --dump-outputs writes the last timed step's outputs and a sample of the updated parameters"""
+    import numpy as np
     p, lines = _run(["--steps", "2", "--warmup", "1", "--pairs", "16", "--model", "ViT-B/32", "--no-cpu-baseline", "--no-secondary",
-                     "--no-retrieval"])
+                     "--no-retrieval", "--dump-outputs", str(tmp_path / "out")])
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1
     r = json.loads(lines[0])
@@ -74,6 +86,13 @@ def test_bench_line_schema_on_the_device():
     assert rf["launches_timed"] > 0 and rf["achieved"] > 0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
     assert rf["traffic"] is None            # profiles/pmc_gemm_traffic.json is the ViT-L/14, 512-pair measurement
     assert abs(r["value"] - 16 * 2 / (r["ms_per_step"] * 2e-3)) < 1e-2 * r["value"]
+    assert r["value_unpacked"] is None and not any(k in r for k in ("retrieval", "embed", "blip_ff_large", "clip_ff", "cpu_baseline"))
+    got = {f.stem: np.load(f) for f in (tmp_path / "out").glob("*.npy")}
+    assert set(got) == {"loss", "accuracy", "params_sample", "grads_sample"}
+    assert all(a.dtype == np.float32 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert abs(float(got["loss"]) - r["config"]["final_loss"]) < 1e-4
+    w, g = got["params_sample"], got["grads_sample"]
+    assert w.shape == g.shape and np.isfinite(w).all() and np.isfinite(g).all() and np.abs(g).max() > 0
 
 
 @pytest.mark.gpu
@@ -81,7 +100,7 @@ def test_bench_two_ranks_sharing_the_gpu():
     """the REAL multi-rank bench path (self-launch, replica sync at the DDP point, overlapped bucketed all-reduce, the rccl block,
     per-rank checksums, and the N > 1 retrieval / embedding blocks) with two ranks on the one GPU a test box has, over gloo (UNIIR_BENCH_SHARED_GPU=1; RCCL cannot put two
     ranks on one device): ranks seeded differently must end the timed steps with identical parameters"""
-    p, lines = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "16", "--model", "ViT-B/32", "--no-cpu-baseline",
+    p, lines = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "16", "--model", "ViT-B/32", "--full", "--no-cpu-baseline",
                      "--shard-rows", "40030", "--shard-queries", "64,300", "--embed-items", "64", "--check-sharded"],
                     {"UNIIR_BENCH_SHARED_GPU": "1"})
     assert p.returncode == 0, p.stderr[-3000:]
@@ -116,7 +135,7 @@ def test_bench_two_ranks_over_rccl_when_two_gpus_are_visible():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two visible GPUs (RCCL puts one rank on each)")
-    p, lines = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "16", "--model", "ViT-B/32", "--no-cpu-baseline",
+    p, lines = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "16", "--model", "ViT-B/32", "--full", "--no-cpu-baseline",
                      "--shard-rows", "40030", "--shard-queries", "64,300", "--embed-items", "64", "--check-sharded"],
                     {"HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert p.returncode == 0, p.stderr[-3000:]

@@ -18,7 +18,7 @@ for S in $STAGES; do
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log ;;
     bench)
       T0=$(date +%s)
-      timeout 1500 python bench.py ${BENCH_ARGS:-} > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$? wall $(( $(date +%s) - T0 )) s"
+      timeout 1500 python bench.py --full ${BENCH_ARGS:-} > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$? wall $(( $(date +%s) - T0 )) s"
       python tools/bench_summary.py $O/bench_line.json ;;
     profile)
       bash tools/profile_bench.sh $TAG > $O/profile_bench.out 2>&1; tail -14 $O/profile_bench.out | cut -c1-200 ;;

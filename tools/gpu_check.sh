@@ -7,5 +7,5 @@ cd $R
 export PYTHONPATH=$R
 SEL=$1; shift
 if [ -n "$SEL" ]; then timeout 1500 python -m pytest $SEL -m gpu -x -q 2>&1 | tail -4; fi
-timeout 600 python bench.py --no-secondary --no-retrieval --no-cpu-baseline --steps 8 --warmup 3 "$@" 2>/dev/null > /tmp/gpu_check_line.json
+timeout 600 python bench.py --full --no-secondary --no-retrieval --no-cpu-baseline --steps 8 --warmup 3 "$@" 2>/dev/null > /tmp/gpu_check_line.json
 python tools/bench_summary.py /tmp/gpu_check_line.json

@@ -18,6 +18,6 @@ mkdir -p $OUT
 tail -3 $OUT/pytest_gpu.log
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc $?"; tail -2 $OUT/smoke.log
 if [ -z "$NO_BENCH" ]; then
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc $?"
+  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc $?"
   python tools/bench_summary.py $OUT/bench_line.json 2>&1 | tail -40
 fi
