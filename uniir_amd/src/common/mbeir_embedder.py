@@ -16,6 +16,7 @@ for _p in (_os.path.dirname(_os.path.dirname(_SRC)), _SRC, _os.path.join(_SRC, "
         _sys.path.insert(0, _p)
 
 import argparse
+import contextlib
 import gc
 import os
 
@@ -39,8 +40,8 @@ def _clip_towers(model):
     return clip if hasattr(clip, "precision") else None
 
 
-@torch.no_grad()
-def generate_embeds_and_ids_for_dataset_with_gather(model, data_loader, device, use_fp16=True):
+@contextlib.contextmanager
+def _tower_precision(model, use_fp16):
     # the reference runs the towers under torch.cuda.amp.autocast(enabled=use_fp16) (:52-56) -- fp16 matmuls: the CLIP towers here take
     # their fp16 forward for the extraction (clip_model.precision = "fp16") and go back to what they were set to afterwards
     clip = _clip_towers(model)
@@ -48,13 +49,44 @@ def generate_embeds_and_ids_for_dataset_with_gather(model, data_loader, device, 
     if clip is not None and use_fp16 and clip.precision == "bf16":
         restore, clip.precision = clip.precision, "fp16"
     try:
-        return _generate(model, data_loader, device)
+        yield
     finally:
         if restore is not None:
             clip.precision = restore
 
 
-def _generate(model, data_loader, device):
+@torch.no_grad()
+def generate_embeds_and_ids_for_dataset_with_gather(model, data_loader, device, use_fp16=True):
+    with _tower_precision(model, use_fp16):
+        return _generate(model, data_loader, device)
+
+
+@torch.no_grad()
+def generate_embeds_and_ids_on_device(model, data_loader, device, use_fp16=True):
+    """the same tower forward as generate_embeds_and_ids_for_dataset_with_gather, but the result stays in HBM and every rank
+    gets it: -> (fp16 [n, d] on `device`, hashed ids in rank order).  The rank shards are all-gathered instead of being
+    gathered to rank 0 (the UniRAG complement queries are searched by every rank, interactive_retriever.py)."""
+    from uniir_amd import comm
+    with _tower_precision(model, use_fp16):
+        chunks, id_list = _embed_local(model, data_loader, device)
+    dim = chunks[0].shape[1] if chunks else 0
+    if comm.world() > 1:                   # ranks without queries learn the width from the others
+        gloo = dist.get_backend() == "gloo"
+        dims = torch.zeros(comm.world(), dtype=torch.int64, device="cpu" if gloo else device)
+        dist.all_gather_into_tensor(dims, torch.tensor([dim], dtype=torch.int64, device=dims.device))
+        dim = int(dims.max())
+    local = torch.cat(chunks, dim=0) if chunks else torch.zeros(0, max(dim, 1), dtype=torch.float16, device=device)
+    emb, _ = comm.all_gather_varlen(local)
+    if comm.world() > 1:
+        ids = [None] * comm.world()
+        dist.all_gather_object(ids, id_list)
+        id_list = [i for sub in ids for i in sub]
+    assert len(id_list) == emb.shape[0]
+    return emb.contiguous(), id_list
+
+
+def _embed_local(model, data_loader, device):
+    """this rank's forward passes: fp16 chunks on the device and the hashed ids, in loader order"""
     chunks, id_list = [], []
     for batch in data_loader:
         for k, v in batch.items():
@@ -68,6 +100,11 @@ def _generate(model, data_loader, device):
         emb, ids = model(batch, encode_mbeir_batch=True)
         chunks.append(emb.half())          # fp16 on disk, like the reference
         id_list.extend(ids)
+    return chunks, id_list
+
+
+def _generate(model, data_loader, device):
+    chunks, id_list = _embed_local(model, data_loader, device)
     dim = chunks[0].shape[1] if chunks else None
     if not dist.is_initialized():
         if not chunks:

@@ -7,8 +7,12 @@ inverse norms, is sharded row-wise over the visible GPUs, each shard returns its
 (score desc, id asc) gives the result -- identical to the unsharded search.  The ".index" file is our own container
 (np.savez: emb fp16, ids int64), only ever read back by search_index, like the reference's FAISS file.
 Not copied: the reference re-reads and re-uploads the index on every search_index call (:197-206); here device shards
-are cached per index file.  The reference's main() passes an unbound query_embedder_config to run_retrieval (:757);
-here it defaults to None.
+are cached per index file.  Under torch.distributed each rank holds the whole pool on its own device, searches a
+contiguous slice of the queries and the slices are all-gathered (every rank holds the same results); rank 0 writes the
+output files while the others wait at a barrier (the reference: every rank writes the same files).  The reference's main()
+passes an unbound query_embedder_config to run_retrieval without --query_embedder_config_path (:757); here it is None.
+UniRAG raw retrieval (:235-309, :451-472): get_raw_retrieved_candidates and the complement retriever of
+interactive_retriever.py; the candidate jsonl is parsed once and shared with it.
 """
 import os as _os
 import sys as _sys
@@ -21,6 +25,7 @@ for _p in (_os.path.dirname(_os.path.dirname(_SRC)), _SRC, _os.path.join(_SRC, "
 import argparse
 import csv
 import gc
+import json
 import os
 from collections import defaultdict
 from datetime import datetime
@@ -28,10 +33,12 @@ from datetime import datetime
 import numpy as np
 import torch
 
+import dist_utils
 from config import OmegaConf
 from data.preprocessing.utils import (count_entries_in_file, get_mbeir_task_name, load_jsonl_as_list,
                                       load_mbeir_format_pool_file_as_dict, print_mbeir_format_dataset_stats,
                                       save_list_as_jsonl, unhash_did, unhash_qid)
+from interactive_retriever import InteractiveRetriever, load_candidates_by_did
 
 _SHARD_CACHE = {}
 
@@ -67,14 +74,16 @@ def compute_recall_at_k(relevant_docs, retrieved_indices, k):
 
 
 def _device_shards(cand_index_path):
-    """row-shard the pool over the visible GPUs (FAISS shard=True semantics); cached per (path, mtime)"""
-    from uniir_amd import retrieval
+    """row-shard the pool over the visible GPUs (FAISS shard=True semantics); cached per (path, mtime).  Under
+    torch.distributed every rank holds the whole pool on its own device (the other devices belong to the other ranks)."""
+    from uniir_amd import comm, retrieval
     key = (cand_index_path, os.path.getmtime(cand_index_path))
     if key not in _SHARD_CACHE:
         _SHARD_CACHE.clear()
         with np.load(cand_index_path) as z:
             emb, ids = z["emb"], z["ids"]
-        ndev = max(1, torch.cuda.device_count())
+        devs = [torch.cuda.current_device()] if comm.world() > 1 else list(range(max(1, torch.cuda.device_count())))
+        ndev = len(devs)
         # UNIIR_RETRIEVER_SHARDS (tests): that many row shards, placed round-robin on the visible devices -- the N > 1 shard loop
         # and the merge on a box with one GPU
         ngpu = int(os.environ.get("UNIIR_RETRIEVER_SHARDS", "0")) or ndev
@@ -84,7 +93,7 @@ def _device_shards(cand_index_path):
             lo, hi = min(g * per, len(ids)), min((g + 1) * per, len(ids))
             if hi <= lo:
                 continue
-            dev = torch.device("cuda", g % ndev)
+            dev = torch.device("cuda", devs[g % ndev])
             with torch.cuda.device(dev):
                 shards.append(retrieval.PoolShard(torch.from_numpy(emb[lo:hi]).to(dev), torch.from_numpy(ids[lo:hi]).to(dev)))
         print(f"Retriever: {len(ids)} documents in {len(shards)} shard(s) over {min(ngpu, ndev)} GPU(s)")
@@ -98,7 +107,7 @@ def search_index_with_batch(query_embeddings_batch, shards, num_cand_to_retrieve
     for sh in shards:                      # launches are asynchronous per device: the shards search concurrently
         dev = sh.emb.device
         with torch.cuda.device(dev):
-            q = torch.from_numpy(query_embeddings_batch).to(dev)
+            q = torch.as_tensor(query_embeddings_batch).to(dev)      # host fp16 rows or a device tensor
             outs.append(retrieval.search_shard(sh, q, num_cand_to_retrieve))
     dev0 = shards[0].emb.device
     with torch.cuda.device(dev0):
@@ -108,16 +117,90 @@ def search_index_with_batch(query_embeddings_batch, shards, num_cand_to_retrieve
         return ms.cpu().numpy(), mi.cpu().numpy()
 
 
+def search_embeddings(queries, cand_index_path, batch_size=10, num_cand_to_retrieve=10):
+    """exact top-k of fp16 query rows (host array or device tensor) over the cached shards of an index file ->
+    (scores f32 [n, k], hashed dids int64 [n, k]) as numpy, on every rank.  Under torch.distributed rank r searches the
+    contiguous slice r of the queries and the slices are all-gathered; a query's result does not depend on its batch."""
+    from uniir_amd import comm
+    shards = _device_shards(cand_index_path)
+    lo, hi = comm.contiguous_shard(len(queries))
+    dists, idxs = [np.zeros((0, num_cand_to_retrieve), np.float32)], [np.zeros((0, num_cand_to_retrieve), np.int64)]
+    for i in range(lo, hi, max(1, batch_size)):
+        d, ix = search_index_with_batch(queries[i:min(i + batch_size, hi)], shards, num_cand_to_retrieve)
+        dists.append(d)
+        idxs.append(ix)
+    dists, idxs = np.vstack(dists), np.vstack(idxs)
+    if comm.world() > 1:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        dists = comm.all_gather_varlen(torch.from_numpy(dists).to(dev))[0].cpu().numpy()
+        idxs = comm.all_gather_varlen(torch.from_numpy(idxs).to(dev))[0].cpu().numpy()
+    return dists, idxs
+
+
 def search_index(query_embed_path, cand_index_path, batch_size=10, num_cand_to_retrieve=10):
     queries = np.load(query_embed_path).astype(np.float16)   # stored fp16; normalised on the device in fp32
     print(f"Retriever: loaded query embeddings from {query_embed_path} with shape: {queries.shape}")
-    shards = _device_shards(cand_index_path)
-    dists, idxs = [], []
-    for i in range(0, len(queries), max(1, batch_size)):
-        d, ix = search_index_with_batch(queries[i:i + batch_size], shards, num_cand_to_retrieve)
-        dists.append(d)
-        idxs.append(ix)
-    return np.vstack(dists), np.vstack(idxs)
+    return search_embeddings(queries, cand_index_path, batch_size, num_cand_to_retrieve)
+
+
+def get_raw_retrieved_candidates(queries_path, candidates_path, retrieved_indices, hashed_query_ids, complement_retriever):
+    """{qid: {"query", "candidates"[, "complement_candidates"]}} in the order of hashed_query_ids (reference :235-309).
+    A complement query -- (modality, txt, img_path, the other modality) -- is made for every hit of modality exactly "text"
+    or "image" ("image,text" hits get none, so complement_candidates is not aligned with candidates); all of them are
+    retrieved in one call with k = 10, and each takes the first of its results in the complement modality that is not
+    the ORIGINAL query's image or text (None when there is none)."""
+    qid_to_queries = {}
+    with open(queries_path, "r") as f:
+        for line in f:
+            q = json.loads(line.strip())
+            assert q["qid"] not in qid_to_queries, "qids must be unique"
+            qid_to_queries[q["qid"]] = q
+    did_to_candidates = load_candidates_by_did(candidates_path)
+    complement_modalities = {"text": "image", "image": "text"}
+    retrieved_dict = {}
+    complement_queries_list = []          # (qid, its complement queries): maps the flat results back to the queries
+    for idx, indices in enumerate(retrieved_indices):
+        qid = unhash_qid(int(hashed_query_ids[idx]))
+        retrieved_cands = [did_to_candidates[unhash_did(int(h))] for h in indices]
+        retrieved_dict[qid] = {"query": qid_to_queries[qid], "candidates": retrieved_cands}
+        if complement_retriever:
+            complement_queries = [(c.get("modality"), c.get("txt"), c.get("img_path"), complement_modalities[c.get("modality")])
+                                  for c in retrieved_cands if c["modality"] in complement_modalities]
+            complement_queries_list.append((qid, complement_queries))
+            complement_retriever.add_queries(complement_queries)
+    if complement_retriever:
+        retrieved_complements = complement_retriever.retrieve(k=10)
+        start = 0
+        for qid, complement_queries in complement_queries_list:
+            retrieved_comp_cands = retrieved_complements[start:start + len(complement_queries)]
+            start += len(complement_queries)
+            query = retrieved_dict[qid]["query"]
+            complement_candidates = []
+            for idx, complement_query in enumerate(complement_queries):
+                complement_cand = None
+                for cand in retrieved_comp_cands[idx]:
+                    if cand["modality"] == complement_modalities[complement_query[0]]:
+                        # not the original query itself: two independent tests, as in the reference
+                        if cand.get("img_path") and cand.get("img_path") != query["query_img_path"]:
+                            complement_cand = cand
+                            break
+                        if cand.get("txt") and cand.get("txt") != query["query_txt"]:
+                            complement_cand = cand
+                            break
+                if not complement_cand:
+                    print(f"retrieved_dict[qid]: {retrieved_dict[qid].__repr__()}")
+                    print(f"retrieved_comp_cands: {retrieved_comp_cands[idx]}")
+                complement_candidates.append(complement_cand)
+            retrieved_dict[qid]["complement_candidates"] = complement_candidates
+    return retrieved_dict
+
+
+def write_retrieved_jsonl(retrieved_dict, path):
+    """one json.dump line per query (default separators), reference :467-471"""
+    with open(path, "w") as f:
+        for v in retrieved_dict.values():
+            json.dump(v, f)
+            f.write("\n")
 
 
 _DATASET_ORDER = ["visualnews_task0", "mscoco_task0", "fashion200k_task0", "webqa_task1", "edis_task2", "webqa_task2",
@@ -137,10 +220,10 @@ def run_retrieval(config, query_embedder_config=None):
     expt = config.experiment.path_suffix
     results_dir = os.path.join(config.uniir_dir, rc.results_dir_name, expt)
     run_dir, tsv_dir = os.path.join(results_dir, "run_files"), os.path.join(results_dir, "final_tsv")
-    for d in (run_dir, os.path.join(results_dir, "retrieved_candidates"), tsv_dir):
+    cands_dir = os.path.join(results_dir, "retrieved_candidates")
+    main = dist_utils.is_main_process()          # rank 0 writes the files, the other ranks wait for it
+    for d in (run_dir, cands_dir, tsv_dir):
         os.makedirs(d, exist_ok=True)
-    if rc.get("raw_retrieval"):
-        raise NotImplementedError("raw_retrieval (UniRAG candidate dump) is outside the MI355X hot path, see DESIGN.md")
     index_dir = os.path.join(config.uniir_dir, rc.index_dir_name, expt, "cand_pool")
     qrel_dir = os.path.join(config.mbeir_data_dir, rc.qrel_dir_name)
     results = []
@@ -160,20 +243,40 @@ def run_retrieval(config, query_embedder_config=None):
             qids = np.load(os.path.join(embed_dir, f"mbeir_{dataset}_{split}_ids.npy"))
             recalls = [m.strip() for m in metric_names.split(",") if "recall" in m.lower()]
             k = max(int(m.split("@")[1]) for m in recalls)
-            dist_mat, idx_mat = search_index(os.path.join(embed_dir, f"mbeir_{dataset}_{split}_embed.npy"),
-                                             os.path.join(index_dir, f"mbeir_{pool}_cand_pool.index"),
+            index_path = os.path.join(index_dir, f"mbeir_{pool}_cand_pool.index")
+            dist_mat, idx_mat = search_index(os.path.join(embed_dir, f"mbeir_{dataset}_{split}_embed.npy"), index_path,
                                              batch_size=qids.shape[0], num_cand_to_retrieve=k)
             run_id = f"mbeir_{dataset}_{'union' if pool == 'union' else 'single'}_pool_{split}_k{k}"
             by_task = defaultdict(lambda: defaultdict(list))
-            with open(os.path.join(run_dir, f"{run_id}_run.txt"), "w") as rf:
-                for qi, (ds, ix) in enumerate(zip(dist_mat, idx_mat)):
-                    qid = unhash_qid(int(qids[qi]))
-                    task = qid_to_task[qid]
-                    docs = [unhash_did(int(h)) for h in ix]
-                    for rank, (doc, score) in enumerate(zip(docs, ds), start=1):
-                        rf.write(run_file_line(qid, doc, rank, score, run_id, task))
-                    for m in recalls:
-                        by_task[task][m].append(compute_recall_at_k(qrel[qid], docs, int(m.split("@")[1])))
+            lines = []
+            for qi, (ds, ix) in enumerate(zip(dist_mat, idx_mat)):
+                qid = unhash_qid(int(qids[qi]))
+                task = qid_to_task[qid]
+                docs = [unhash_did(int(h)) for h in ix]
+                for rank, (doc, score) in enumerate(zip(docs, ds), start=1):
+                    lines.append(run_file_line(qid, doc, rank, score, run_id, task))
+                for m in recalls:
+                    by_task[task][m].append(compute_recall_at_k(qrel[qid], docs, int(m.split("@")[1])))
+            if main:
+                with open(os.path.join(run_dir, f"{run_id}_run.txt"), "w") as rf:
+                    rf.writelines(lines)
+            if rc.get("raw_retrieval"):      # raw candidates for downstream applications like UniRAG (reference :451-472)
+                queries_path = os.path.join(config.mbeir_data_dir, rc.query_dir_name, f"{split}/mbeir_{dataset}_{split}.jsonl")
+                candidates_path = os.path.join(config.mbeir_data_dir, rc.candidate_dir_name,
+                                               f"mbeir_{pool}_{split}_cand_pool.jsonl")
+                # Deliberate reference quirk: the complement retriever is built for "MSCOCO" (it has both image->text and
+                # text->image instructions) by overwriting dataset_name, so this dataset's result row says "MSCOCO".
+                dataset = "MSCOCO"
+                complement_retriever = (InteractiveRetriever(index_path, candidates_path, dataset, query_embedder_config)
+                                        if rc.get("retrieve_image_text_pairs") else None)
+                retrieved_dict = get_raw_retrieved_candidates(queries_path, candidates_path, idx_mat, qids,
+                                                              complement_retriever)
+                if main:
+                    retrieved_path = os.path.join(cands_dir, f"{run_id}_retrieved.jsonl")
+                    write_retrieved_jsonl(retrieved_dict, retrieved_path)
+                    print(f"Retriever: Retrieved file saved to {retrieved_path}")
+            if dist_utils.is_dist_avail_and_initialized():
+                torch.distributed.barrier()
             for task, vals in by_task.items():
                 row = {"TaskID": int(task), "Task": get_mbeir_task_name(int(task)), "Dataset": dataset, "Split": split,
                        "CandPool": pool}
@@ -184,7 +287,7 @@ def run_retrieval(config, query_embedder_config=None):
     order = {n: i + 1 for i, n in enumerate(_DATASET_ORDER)}
     results.sort(key=lambda r: (r["TaskID"], order.get(r["Dataset"].lower(), 99), {"val": 1, "test": 2}.get(r["Split"], 99),
                                 99 if r["CandPool"] == "union" else 0))
-    if rc.get("write_to_tsv"):
+    if rc.get("write_to_tsv") and main:
         grouped = defaultdict(dict)
         for r in results:
             grouped[(r["TaskID"], r["Task"], r["Dataset"], r["Split"])][r["CandPool"]] = {m: r.get(m) for m in _RECALLS}
@@ -201,6 +304,8 @@ def run_retrieval(config, query_embedder_config=None):
                         w.writerow([tid, task, dataset, split, m, pool, vals[m]] +
                                    (["union", union.get(m, "N/A")] if union else ["", ""]))
         print(f"Retriever: Results saved to {path}")
+    if dist_utils.is_dist_avail_and_initialized():
+        torch.distributed.barrier()
     return results
 
 
@@ -272,12 +377,22 @@ def main():
     config = OmegaConf.load(args.config_path)
     config.uniir_dir, config.mbeir_data_dir = args.uniir_dir, args.mbeir_data_dir
     print(OmegaConf.to_yaml(config, sort_keys=False))
+    query_embedder_config = None
+    if args.query_embedder_config_path:         # UniRAG: the complement retriever embeds queries (reference :734-743)
+        query_embedder_config = OmegaConf.load(args.query_embedder_config_path)
+        query_embedder_config.uniir_dir, query_embedder_config.mbeir_data_dir = args.uniir_dir, args.mbeir_data_dir
+        args.dist_url = query_embedder_config.dist_config.dist_url
+        dist_utils.init_distributed_mode(args)
+        query_embedder_config.dist_config.gpu_id = args.gpu
+        query_embedder_config.dist_config.distributed_mode = args.distributed
     if args.enable_hard_negative_mining:
         run_hard_negative_mining(config)
     if args.enable_create_index:
         create_index(config)
     if args.enable_retrieval:
-        run_retrieval(config, None)
+        run_retrieval(config, query_embedder_config)
+    if query_embedder_config is not None and query_embedder_config.dist_config.distributed_mode:
+        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":
