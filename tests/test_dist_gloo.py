@@ -135,7 +135,7 @@ def _reducer_worker(rank, world, port, q):
     comm.allreduce_sum_(flat_ref)                                        # the round-1 path: one all-reduce of everything
     flat = grads.clone()
     red = comm.GradReducer(flat, bucket_bytes=4 * 1500)
-    # "backward": blocks announced last-to-first like _tower_bwd does (adjacent ranges, to be coalesced), a second tower,
+    # "backward": blocks announced last-to-first like a tower backward does (adjacent ranges, to be coalesced), a second tower,
     # one stray range; [0, 1000) and [9000, 10000) are never announced and must be picked up by finish()
     for lo in range(4000, 1000, -500):
         red.ready(lo, lo + 500)
@@ -178,7 +178,7 @@ def _reducer_worker(rank, world, port, q):
 
 
 def test_bucketed_overlapped_gradient_allreduce_equals_flat_allreduce_bit_for_bit():
-    """DDP-style buckets (comm.GradReducer, fed per finished block by clip_model._tower_bwd) == one all-reduce of the
+    """DDP-style buckets (comm.GradReducer, fed per finished block through clip_model.CLIP.block_done) == one all-reduce of the
     flat gradient buffer, bit for bit, including the never-announced remainder and re-use across steps"""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()

@@ -17,13 +17,13 @@ stash.  Differences from the reference, stated once:
     used un-normalised and a host coin flip decides what is enqueued.
 """
 import json
-import math
 
 import torch
 from torch import nn
 
 from . import _lib, comm, ops
-from .clip_model import ALIGN, _Blk, _tower_bwd, _tower_fwd
+from .flat_store import FlatStore
+from .resblocks import tower_bwd, tower_fwd
 
 VIT_CONFIGS = {   # src/models/uniir_blip/backbone/blip.py:229-255 (create_vit)
     "base": dict(patch_size=16, embed_dim=768, depth=12, num_heads=12, drop_path_rate=0.0),
@@ -86,42 +86,6 @@ def _vit_blk_names(prefix, i):
                 wproj=b + "mlp.fc2.weight", bproj=b + "mlp.fc2.bias", ln2w=b + "norm2.weight", ln2b=b + "norm2.bias")
 
 
-# ------------------------------------------------------------------------------------------------------------
-# flat stores
-# ------------------------------------------------------------------------------------------------------------
-class FlatStore:
-    """One flat fp32 buffer (+ optional flat gradient) + bf16 shadow for an ordered list of named tensors; every
-    tensor starts on a 256-B boundary.  Offers the small interface `_Blk` / the tower launch sequences use."""
-
-    def __init__(self, named_shapes, device, with_grad):
-        self.off, self.shapes, cur = {}, {}, 0
-        for n, shp in named_shapes:
-            self.off[n], self.shapes[n] = cur, tuple(shp)
-            cur += (math.prod(shp) + ALIGN - 1) // ALIGN * ALIGN
-        self.total = cur
-        self.p32 = torch.zeros(cur, device=device, dtype=torch.float32)
-        self.g32 = torch.zeros(cur, device=device, dtype=torch.float32) if with_grad else None
-        self.w16_buf = torch.empty(cur, device=device, dtype=torch.bfloat16)
-        self._flat = dict(off=self.off, shapes=self.shapes, p32=self.p32)
-
-    def _view(self, buf, name, shape=None, numel=None):
-        shape = shape or self.shapes[name]
-        o = self.off[name]
-        return buf[o:o + (numel or math.prod(shape))].view(shape)
-
-    def p(self, name, shape=None):
-        return self._view(self.p32, name, shape)
-
-    def w16(self, name, shape=None):
-        return self._view(self.w16_buf, name, shape)
-
-    def grad_view(self, name, shape=None):
-        return self._view(self.g32, name, shape)
-
-    def refresh_shadow(self):
-        ops.call("uniir_cast_f32_to_bf16", self.p32, self.w16_buf, self.total)
-
-
 def _attach(root, dotted, param):
     mod = root
     parts = dotted.split(".")
@@ -151,13 +115,12 @@ def vit_forward(st, conv16, prefix, cfg, img_size, images, save, drop=None):
     x0 = torch.empty(M * T, D, device=dev, dtype=torch.float32)
     ops.call("uniir_vit_assemble", po, st.p(prefix + "cls_token"), st.p(prefix + "pos_embed"), x0, M, T, D)
     del po
-    blk = lambda i: _Blk(st, None, _vit_blk_names(prefix, i))
     rowscale = None
     if drop is not None and cfg.get("drop_path_rate", 0.0) > 0 and depth > 1:
         keep = 1.0 - torch.linspace(0, cfg["drop_path_rate"], depth).view(depth, 1, 1)
         rowscale = (torch.floor(keep + torch.rand(depth, 2, M)) / keep).to(dev)
-    x, saved = _tower_fwd(st, None, depth, x0, M, T, D, heads, False, save, eps=VIT_EPS, act=ops.ACT_GELU_ERF, blk=blk,
-                          rowscale=rowscale)
+    x, saved = tower_fwd(st, lambda i: _vit_blk_names(prefix, i), depth, x0, M, T, D, heads, False, save, eps=VIT_EPS,
+                         act=ops.ACT_GELU_ERF, rowscale=rowscale)
     tok = ops.layernorm_fwd(x, st.p(prefix + "norm.weight"), st.p(prefix + "norm.bias"), VIT_EPS, rows=M * T, width=D)
     stash = dict(patches=patches, x=x, saved=saved, M=M, T=T, rowscale=rowscale) if save else None
     return tok, T, stash
@@ -171,9 +134,8 @@ def vit_backward(st, dconv, prefix, cfg, dtok, stash):
     dxb = torch.empty(R, D, device=dev, dtype=torch.bfloat16)
     dx = ops.layernorm_bwd(stash["x"], st.p(prefix + "norm.weight"), dtok, st.grad_view(prefix + "norm.weight"),
                            st.grad_view(prefix + "norm.bias"), VIT_EPS, dx_bf16=dxb, rows=R, width=D)
-    blk = lambda i: _Blk(st, None, _vit_blk_names(prefix, i))
-    dx = _tower_bwd(st, None, depth, dx, dxb, stash["saved"], M, T, D, heads, False, eps=VIT_EPS, act=ops.ACT_GELU_ERF,
-                    blk=blk, rowscale=stash["rowscale"])
+    dx = tower_bwd(st, lambda i: _vit_blk_names(prefix, i), depth, dx, dxb, stash["saved"], M, T, D, heads, False, eps=VIT_EPS,
+                   act=ops.ACT_GELU_ERF, rowscale=stash["rowscale"])
     G = T - 1
     dpo = torch.empty(M * G, D, device=dev, dtype=torch.bfloat16)
     ops.call("uniir_vit_assemble_bwd", dx, dpo, st.grad_view(prefix + "cls_token"), st.grad_view(prefix + "pos_embed"),
@@ -654,35 +616,25 @@ class BLIPFeatureFusion(nn.Module):
 
     @torch.no_grad()
     def copy_params(self):
-        for n, _ in self._shapes:
-            enc, rest = n.split(".", 1)
-            self.get_parameter(f"{enc}_m.{rest}").data.copy_(self.get_parameter(n).data)
+        for n, pm in self._momentum_params():
+            pm.data.copy_(self.get_parameter(n).data)
 
     # ---- flat storage --------------------------------------------------------------------------------------
     def _online_params(self):
         return [(n, self.get_parameter(n)) for n, _ in self._shapes] + [("temp", self.temp)]
 
+    def _momentum_params(self):
+        """the momentum encoders' parameters under the ONLINE names: both stores have one layout and one launch sequence"""
+        return [(n, self.get_parameter("{}_m.{}".format(*n.split(".", 1)))) for n, _ in self._shapes]
+
     def _ensure_flat(self):
         dev = self.temp.device
         if dev.type != "cuda":
             raise RuntimeError("uniir_amd BLIPFeatureFusion runs on an MI355X only (no CPU path); move the model to cuda")
-        st = self._online
-        if st is not None and st.p32.device == dev and all(
-                p.data_ptr() == st.p32.data_ptr() + 4 * st.off[n] for n, p in self._online_params()):
-            return self._flat_dict()
-        online = FlatStore(self._shapes + [("temp", ())], dev, True)
-        mom = FlatStore(self._shapes, dev, False)
-        for n, p in self._online_params():
-            online.p(n).copy_(p.data.float())
-            p.data = online.p(n)
-            if n not in self._frozen:
-                p.grad = online.grad_view(n)
-        for n, _ in self._shapes:
-            enc, rest = n.split(".", 1)
-            pm = self.get_parameter(f"{enc}_m.{rest}")
-            mom.p(n).copy_(pm.data.float())
-            pm.data = mom.p(n)
-        self._online, self._mom = online, mom
+        if self._online is not None and self._online.holds(self._online_params()):
+            return self._online
+        self._online = FlatStore.adopt(self._online_params(), dev, frozen=self._frozen)
+        self._mom = FlatStore.adopt(self._momentum_params(), dev, with_grad=False)
         D, P = self.vit_cfg["embed_dim"], self.vit_cfg["patch_size"]
         kpad = (3 * P * P + 63) // 64 * 64
         self._conv16 = torch.zeros(D, kpad, device=dev, dtype=torch.bfloat16)
@@ -690,21 +642,17 @@ class BLIPFeatureFusion(nn.Module):
         self._dconv = torch.zeros(D, kpad, device=dev, dtype=torch.float32)
         self._version = -1
         self.refresh_shadow()
-        return self._flat_dict()
-
-    def _flat_dict(self):
-        """what NativeAdamW reads: one weight-decay group over everything trainable (uniir_blip/train.py:193-197); frozen
-        tensors (BLIP_SF's cross-attention) sit between the trainable range and temp and are skipped"""
-        st = self._online
-        d = dict(p32=st.p32, g32=st.g32, w16=st.w16_buf, total=st.total, split=0)
-        if self._frozen:
-            first = min(st.off[n] for n in self._frozen)
-            d["ranges"] = [(0, first, 1), (st.off["temp"], st.total, 1)]
-        return d
+        return self._online
 
     def optimizer_groups(self):
-        """(no-decay params, decay params) for NativeAdamW: the reference applies weight decay to every parameter"""
+        """(no-decay params, decay params) for NativeAdamW: the reference applies weight decay to every parameter
+        (uniir_blip/train.py:193-197)"""
         return [], [p for n, p in self._online_params() if n not in self._frozen]
+
+    def adamw_group(self, name):
+        """NativeAdamW's param group of tensor `name`: the weight-decay group; frozen tensors (BLIP_SF's cross-attention, between
+        the trainable tensors and temp) are not stepped"""
+        return None if name in self._frozen else 1
 
     def _refresh_conv(self, momentum_too=True):
         D, P = self.vit_cfg["embed_dim"], self.vit_cfg["patch_size"]
@@ -730,10 +678,7 @@ class BLIPFeatureFusion(nn.Module):
 
     def zero_grad(self, set_to_none=False):
         if self._online is not None:
-            self._online.g32.zero_()
-            for n, p in self._online_params():
-                if n not in self._frozen and (p.grad is None or p.grad.data_ptr() != self._online.grad_view(n).data_ptr()):
-                    p.grad = self._online.grad_view(n)
+            self._online.zero_grad(self._online_params(), self._frozen)
         else:
             super().zero_grad(set_to_none=set_to_none)
 

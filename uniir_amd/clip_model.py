@@ -5,8 +5,8 @@ checkpoints: SURVEY.md section 3.2; reference call sites src/models/uniir_clip/c
 
 The arithmetic is entirely in libuniir_hip.so (include/uniir_hip.h): bf16 MFMA GEMMs with fused epilogues,
 fp32 LayerNorm, fused attention, fp32 residual stream.  This file is host plumbing only: parameter bookkeeping
-(one flat fp32 master buffer + flat grad buffer + bf16 shadow), the per-layer launch sequence of forward and
-backward, and the activation stash.  There is no torch fallback.
+(flat_store.FlatStore: one flat fp32 master buffer + flat grad buffer + bf16 shadow), the calls of the C towers
+(csrc/tower.hip), the fp32 forward's launch sequence and the activation stash.  There is no torch fallback.
 """
 import contextlib
 import ctypes as C
@@ -17,13 +17,9 @@ import torch
 from torch import nn
 
 from . import _lib, ops
+from .flat_store import FlatStore
 
-# True (tests): run the CLIP towers as the per-op launch sequence below (what CLIP_FF and BLIP use for their variants) instead of
-# the single-call C towers of csrc/tower.hip -- same kernels, same order
-_PY_TOWERS = False
 _SIDE_STREAMS = {}          # device index -> the torch stream that carries the text leg of two-stream towers (CLIP.side_leg)
-
-ALIGN = 64  # elements; every parameter starts on a 256-B boundary of the flat buffers
 
 def _tensor_version(t):
     try:
@@ -143,8 +139,7 @@ class CLIP(nn.Module):
         self.ln_final = _P(weight=torch.ones(tw), bias=torch.zeros(tw))
         self.text_projection = nn.Parameter(torch.randn(tw, E, generator=g) * tw ** -0.5)
         self.logit_scale = nn.Parameter(torch.ones([]) * math.log(1 / 0.07))
-        # flat storage (built lazily on the device)
-        self._flat = None
+        self._flat = None          # the FlatStore of the parameters (built lazily on the device, _ensure_flat)
         self.kpad = (3 * P * P + 63) // 64 * 64
         # "bf16": MFMA towers, forward + backward (training / fast extraction).  "fp16": the same MFMA towers with fp16 operands and
         # activations, FORWARD ONLY -- the reference embedder's precision (mbeir_embedder.py:52-56: autocast(fp16) then .half()),
@@ -193,61 +188,46 @@ class CLIP(nn.Module):
         self._leg_main = None           # inside side_leg(): the stream the leg forked from
 
     # ---- flat parameter / gradient / bf16-shadow storage -----------------------------------------------------
-    def _ensure_flat(self):
+    def _flat_order(self):
+        """(name, parameter) in flat-buffer order: the no-decay tensors, then the decay tensors, each in named_parameters() order --
+        NativeAdamW's two groups are two ranges, and a residual block's four weight matrices are adjacent (layer_grad_range)"""
         params = list(self.named_parameters())
+        return [(n, p) for n, p in params if _is_no_decay(n, p)] + [(n, p) for n, p in params if not _is_no_decay(n, p)]
+
+    def _ensure_flat(self):
         dev = self.logit_scale.device
         if dev.type != "cuda":
             raise RuntimeError("uniir_amd CLIP runs on an MI355X only (no CPU path); move the model to cuda")
-        fl = self._flat
-        if fl is not None and fl["dev"] == dev and all(p.data_ptr() == fl["p32"].data_ptr() + 4 * fl["off"][n]
-                                                        for n, p in params):
-            return fl
-        order = [(n, p) for n, p in params if _is_no_decay(n, p)] + [(n, p) for n, p in params if not _is_no_decay(n, p)]
-        n_nodecay = sum(1 for n, p in params if _is_no_decay(n, p))
-        off, cur, split = {}, 0, 0
-        for i, (n, p) in enumerate(order):
-            if i == n_nodecay:
-                split = cur
-            off[n] = cur
-            cur += (p.numel() + ALIGN - 1) // ALIGN * ALIGN
-        if n_nodecay == len(order):
-            split = cur
-        p32 = torch.zeros(cur, device=dev, dtype=torch.float32)
-        g32 = torch.zeros(cur, device=dev, dtype=torch.float32)
-        for n, p in order:
-            view = p32[off[n]:off[n] + p.numel()].view(p.shape)
-            view.copy_(p.data.float())
-            p.data = view
-            p.grad = g32[off[n]:off[n] + p.numel()].view(p.shape)
-        w16 = torch.empty(cur, device=dev, dtype=torch.bfloat16)
-        self._flat = fl = dict(dev=dev, p32=p32, g32=g32, w16=w16, off=off, total=cur, split=split, version=-1,
-                               shapes={n: p.shape for n, p in order})
+        if self._flat is not None and self._flat.holds(self.named_parameters()):
+            return self._flat
+        self._flat = FlatStore.adopt(self._flat_order(), dev)
+        self._h16 = self._h16_version = None          # the fp16 shadow (precision = "fp16"): built on first use
+        self._descs = {}                               # tower_desc() cache: raw pointers into this store
         self._conv16 = torch.zeros(self.cfg["vision_width"], self.kpad, device=dev, dtype=torch.bfloat16)
         self._dconv = torch.zeros(self.cfg["vision_width"], self.kpad, device=dev, dtype=torch.float32)
         self.refresh_shadow()
-        return fl
+        return self._flat
 
     def refresh_shadow(self):
         """bf16 copies of the master weights (called after every optimizer step; the fused AdamW does it itself)."""
-        fl = self._flat
-        ops.call("uniir_cast_f32_to_bf16", fl["p32"], fl["w16"], fl["total"])
+        self._flat.refresh_shadow()
         self._refresh_conv()
-        fl["version"] = self._param_version()
-        fl["h16_version"] = None            # the fp16 shadow (precision = "fp16") is rebuilt on demand
+        self._shadow_version = self._param_version()
+        self._h16_version = None            # the fp16 shadow (precision = "fp16") is rebuilt on demand
 
     def _sync_half_shadow(self):
         """fp16 copies of the master weights for the fp16 forward: built on first use, rebuilt when the parameters moved"""
-        fl = self._sync_shadow()
+        st = self._sync_shadow()
         ver = self._param_version()
-        if fl.get("h16") is None:
-            fl["h16"] = torch.empty(fl["total"], device=fl["dev"], dtype=torch.float16)
-            self._conv16h = torch.zeros(self.cfg["vision_width"], self.kpad, device=fl["dev"], dtype=torch.float16)
-        if fl.get("h16_version") != ver:
-            ops.call("uniir_cast_f32_to_f16", fl["p32"], fl["h16"], fl["total"])
+        if self._h16 is None:
+            self._h16 = torch.empty(st.total, device=st.dev, dtype=torch.float16)
+            self._conv16h = torch.zeros(self.cfg["vision_width"], self.kpad, device=st.dev, dtype=torch.float16)
+        if self._h16_version != ver:
+            ops.call("uniir_cast_f32_to_f16", st.p32, self._h16, st.total)
             vw, P = self.cfg["vision_width"], self.cfg["vision_patch_size"]
             ops.call("uniir_cast_pad_rows_f16", self.visual.conv1.weight.data, self._conv16h, vw, 3 * P * P, self.kpad)
-            fl["h16_version"] = ver
-        return fl
+            self._h16_version = ver
+        return st
 
     def _refresh_conv(self):
         vw, P = self.cfg["vision_width"], self.cfg["vision_patch_size"]
@@ -257,42 +237,42 @@ class CLIP(nn.Module):
         return sum(p._version for _, p in self.named_parameters())
 
     def _sync_shadow(self):
-        fl = self._ensure_flat()
-        if fl["version"] != self._param_version():
+        st = self._ensure_flat()
+        if self._shadow_version != self._param_version():
             self.refresh_shadow()
-        return fl
+        return st
+
+    def optimizer_groups(self):
+        """(no-decay params, decay params): NativeAdamW's param groups 0 and 1 (clip_scorefusion/train.py:195-199)"""
+        named = list(self.named_parameters())
+        return [p for n, p in named if _is_no_decay(n, p)], [p for n, p in named if not _is_no_decay(n, p)]
+
+    def adamw_group(self, name):
+        """NativeAdamW's param group of tensor `name`"""
+        return 0 if _is_no_decay(name, self.get_parameter(name)) else 1
 
     def w16(self, name):
-        fl = self._flat
-        o = fl["off"][name]
-        return fl["w16"][o:o + math.prod(fl["shapes"][name])].view(fl["shapes"][name])
-
-    def grad_view(self, name):
-        fl = self._flat
-        o = fl["off"][name]
-        return fl["g32"][o:o + math.prod(fl["shapes"][name])].view(fl["shapes"][name])
+        return self._flat.w16(name)
 
     def tower_desc(self, which, half=False):
         """the POD description uniir_clip_tower_{fwd,bwd} take (include/uniir_hip.h [TOWER]): raw device pointers into the flat
         fp32 / bf16-shadow / gradient buffers; cached until the flat storage is rebuilt.  half: the fp16 forward's description
         (dtype16 = 1, 16-bit weights from the fp16 shadow)"""
-        import ctypes as C
         from ._lib import ClipBlock, ClipTower
-        fl = self._flat
-        key = (which, fl["p32"].data_ptr(), bool(half))
-        cache = fl.setdefault("tower_desc", {})
-        if key in cache:
-            return cache[key][0]
-        cfg = self.cfg
+        key = (which, bool(half))
+        if key in self._descs:
+            return self._descs[key][0]
+        cfg, st = self.cfg, self._flat
+        w16 = self._h16 if half else st.w16_buf
 
         def p(name):
-            return fl["p32"].data_ptr() + 4 * fl["off"][name]
+            return st.ptr(st.p32, name)
 
         def h(name):
-            return (fl["h16"] if half else fl["w16"]).data_ptr() + 2 * fl["off"][name]
+            return st.ptr(w16, name)
 
         def g(name):
-            return fl["g32"].data_ptr() + 4 * fl["off"][name]
+            return st.ptr(st.g32, name)
 
         image = which == "image"
         prefix = "visual.transformer" if image else "transformer"
@@ -316,7 +296,7 @@ class CLIP(nn.Module):
         t.is_text, t.layers, t.width, t.embed_dim = int(not image), L, W, cfg["embed_dim"]
         t.blocks = C.cast(blocks, C.POINTER(ClipBlock))
         # split-K slabs: one scratch buffer PER TOWER (the two towers may run on two streams at the same time)
-        skw = ops._splitk_workspace(fl["dev"], 128 << 20, tag=which)
+        skw = ops._splitk_workspace(st.dev, 128 << 20, tag=which)
         t.splitk_ws, t.splitk_ws_bytes = skw.data_ptr(), skw.numel()
         if image:
             P = cfg["vision_patch_size"]
@@ -335,28 +315,26 @@ class CLIP(nn.Module):
             t.ln_post_w, t.ln_post_b, t.proj16 = p("ln_final.weight"), p("ln_final.bias"), h("text_projection")
             t.g_pos, t.g_token = g("positional_embedding"), g("token_embedding.weight")
             t.g_ln_post_w, t.g_ln_post_b, t.g_proj = g("ln_final.weight"), g("ln_final.bias"), g("text_projection")
-        cache[key] = (t, blocks, skw)          # keep the host array and the scratch alive with the description
+        self._descs[key] = (t, blocks, skw)          # keep the host array and the scratch alive with the description
         return t
 
     def layer_grad_range(self, prefix, i):
         """[lo, hi) of the flat buffers that holds the four weight matrices of residual block i (adjacent: the weight-decay
         section keeps named_parameters() order and the block's gains / biases live in the other section)"""
-        fl = self._flat
-        names = [f"{prefix}.resblocks.{i}.{n}" for n in ("attn.in_proj_weight", "attn.out_proj.weight", "mlp.c_fc.weight",
-                                                         "mlp.c_proj.weight")]
-        lo = min(fl["off"][n] for n in names)
-        hi = max(fl["off"][n] + (math.prod(fl["shapes"][n]) + ALIGN - 1) // ALIGN * ALIGN for n in names)
-        if hi - lo != sum((math.prod(fl["shapes"][n]) + ALIGN - 1) // ALIGN * ALIGN for n in names):
-            raise RuntimeError("flat layout: block weights are not adjacent")
-        return lo, hi
+        return self._flat.span([f"{prefix}.resblocks.{i}.{n}" for n in ("attn.in_proj_weight", "attn.out_proj.weight",
+                                                                        "mlp.c_fc.weight", "mlp.c_proj.weight")])
+
+    def block_done(self, prefix):
+        """DDP overlap: with a gradient reducer armed (trainer.NativeAdamW.arm_overlap), the callable a backward of the tower `prefix`
+        calls once residual block i is finished -- it hands the block's weight gradients to the collective stream while the
+        remaining blocks still run; None when no reducer is armed"""
+        reducer = getattr(self, "_grad_reducer", None)
+        return None if reducer is None else (lambda i: reducer.ready(*self.layer_grad_range(prefix, i)))
 
     def zero_grad(self, set_to_none=False):
         """Gradients live in one flat buffer; zeroing it is one memset (they are never set to None)."""
         if self._flat is not None:
-            self._flat["g32"].zero_()
-            for n, p in self.named_parameters():
-                if p.grad is None or p.grad.data_ptr() != self.grad_view(n).data_ptr():
-                    p.grad = self.grad_view(n)
+            self._flat.zero_grad(self.named_parameters())
         else:
             super().zero_grad(set_to_none=set_to_none)
 
@@ -396,7 +374,7 @@ class CLIP(nn.Module):
 
     def _measured_headroom(self):
         """(bytes of the device the finished step left unused at its peak, torch's peak, bytes held outside torch's allocator)"""
-        dev = self._flat["dev"]
+        dev = self._flat.dev
         free, total = torch.cuda.mem_get_info(dev)
         outside = total - free - torch.cuda.memory_reserved(dev)          # other processes / RCCL / HIP runtime on this device
         peak = torch.cuda.max_memory_allocated(dev)
@@ -414,10 +392,10 @@ class CLIP(nn.Module):
     def side_leg(self, dev):
         """with model.side_leg(dev) as leg: everything enqueued inside (one tower call and the torch ops around it) goes to this
         model's second stream of `dev`, ordered after all work enqueued so far on the current stream; leg is None when the overlap is
-        off (CPU tensors, overlap_towers False, the Python tower sequences) and the body then runs on the current stream as before.
+        off (CPU tensors, overlap_towers False) and the body then runs on the current stream as before.
         The caller hands the tensors the leg produced to join_leg() before the current stream reads them."""
         dev = torch.device(dev)
-        if not self.overlap_on() or dev.type != "cuda" or _PY_TOWERS or self.precision == "fp32" or self._leg_main is not None:
+        if not self.overlap_on() or dev.type != "cuda" or self.precision == "fp32" or self._leg_main is not None:
             yield None
             return
         # every lazily built shared buffer (flat storage, 16-bit shadows of the weights) is brought up to date on the forking stream,
@@ -469,128 +447,6 @@ class CLIP(nn.Module):
         # a leaf that requires grad, so autograd calls the tower backward (parameter grads are written straight
         # into the flat gradient buffer, they do not travel through autograd)
         return torch.zeros(1, device=dev, requires_grad=torch.is_grad_enabled())
-
-
-# ------------------------------------------------------------------------------------------------------------
-# layer launch sequences
-# ------------------------------------------------------------------------------------------------------------
-class _Blk:
-    """names of one residual block's tensors inside the flat buffers"""
-
-    def __init__(self, model, prefix, names=None):
-        p = prefix
-        self.names = names or dict(wqkv=f"{p}.attn.in_proj_weight", bqkv=f"{p}.attn.in_proj_bias", wo=f"{p}.attn.out_proj.weight",
-                          bo=f"{p}.attn.out_proj.bias", ln1w=f"{p}.ln_1.weight", ln1b=f"{p}.ln_1.bias",
-                          wfc=f"{p}.mlp.c_fc.weight", bfc=f"{p}.mlp.c_fc.bias", wproj=f"{p}.mlp.c_proj.weight",
-                          bproj=f"{p}.mlp.c_proj.bias", ln2w=f"{p}.ln_2.weight", ln2b=f"{p}.ln_2.bias")
-        self.m = model
-
-    def w16(self, k):
-        return self.m.w16(self.names[k])
-
-    def p32(self, k):
-        fl = self.m._flat
-        n = self.names[k]
-        o = fl["off"][n]
-        return fl["p32"][o:o + math.prod(fl["shapes"][n])].view(fl["shapes"][n])
-
-    def g(self, k):
-        return self.m.grad_view(self.names[k])
-
-
-def _tower_fwd(model, prefix, layers, x, M, T, W, heads, causal, save, eps=1e-5, act=ops.ACT_QUICKGELU, blk=None,
-               rowscale=None):
-    """pre-LN residual blocks (CLIP resblocks; with eps / act / blk(i) overridden also the BLIP ViT blocks).
-    rowscale fp32 [layers, 2, M]: DropPath factors (0 or 1/keep per item) of the two residual branches of each block
-    (BLIP ViT-large in train mode, backbone/vit.py:79-80); None = no DropPath (the residual add stays in the GEMM)"""
-    blk = blk or (lambda i: _Blk(model, f"{prefix}.resblocks.{i}"))
-    R = M * T
-    dev = x.device
-    h = torch.empty(R, W, device=dev, dtype=torch.bfloat16)
-    g = torch.empty(R, 4 * W, device=dev, dtype=torch.bfloat16)
-    saved = []
-    # DropPath factors per ROW (item factor repeated over its T tokens): applied inside the residual GEMM's epilogue
-    rs_rows = None if rowscale is None else rowscale.repeat_interleave(T, dim=2).contiguous()
-    for i in range(layers):
-        b = blk(i)
-        # with save, the two LayerNorm outputs are kept for the weight gradients (26 GB at ViT-L/14 x 1024 items:
-        # cheaper than re-reading the fp32 stream to recompute them in backward)
-        h1 = torch.empty(R, W, device=dev, dtype=torch.bfloat16) if save else h
-        ops.layernorm_fwd(x, b.p32("ln1w"), b.p32("ln1b"), eps, out_bf16=h1, rows=R, width=W)
-        qkv = ops.linear_fwd(h1, b.w16("wqkv"), b.p32("bqkv"))
-        ao, lse = ops.attention_fwd(qkv, M, T, heads, causal)
-        if rowscale is None:
-            x2 = ops.linear_fwd(ao, b.w16("wo"), b.p32("bo"), epilogue=ops.EPI_RESID_F32, resid=x)
-        else:
-            x2 = ops.linear_fwd(ao, b.w16("wo"), b.p32("bo"), epilogue=ops.EPI_RESID_F32, resid=x, row_scale=rs_rows[i, 0])
-        h2 = torch.empty(R, W, device=dev, dtype=torch.bfloat16) if save else h
-        ops.layernorm_fwd(x2, b.p32("ln2w"), b.p32("ln2b"), eps, out_bf16=h2, rows=R, width=W)
-        if save:
-            f = torch.empty(R, 4 * W, device=dev, dtype=torch.bfloat16)
-            ops.linear_fwd(h2, b.w16("wfc"), b.p32("bfc"), out=f, epilogue=ops.EPI_BIAS_ACT, C2=g, act=act)
-        else:       # forward only: the pre-activation is not needed, only act(f) is written
-            f = None
-            ops.linear_fwd(h2, b.w16("wfc"), b.p32("bfc"), out=g, epilogue=ops.EPI_ACT_ONLY, act=act)
-        if rowscale is None:
-            xn = ops.linear_fwd(g, b.w16("wproj"), b.p32("bproj"), epilogue=ops.EPI_RESID_F32, resid=x2)
-        else:
-            xn = ops.linear_fwd(g, b.w16("wproj"), b.p32("bproj"), epilogue=ops.EPI_RESID_F32, resid=x2, row_scale=rs_rows[i, 1])
-        if save:
-            saved.append((x, qkv, ao, lse, x2, f, h1, h2))
-        x = xn
-    return x, saved
-
-
-def _tower_bwd(model, prefix, layers, dx, dxb, saved, M, T, W, heads, causal, eps=1e-5, act=ops.ACT_QUICKGELU,
-               blk=None, rowscale=None):
-    """dx fp32 [R,W] and its bf16 copy dxb: gradient w.r.t. the tower output.  Returns d(tower input) (fp32).
-    With DropPath factors (rowscale, see _tower_fwd) the gradient entering a branch is rowscale * dx: the LayerNorm backward
-    that produces dx writes its bf16 copy and the branch's bias gradient already scaled (uniir_layernorm_bwd_ex); only the
-    tower's incoming gradient is scaled by a separate pass."""
-    # DDP overlap: with a reducer armed (trainer.NativeAdamW.arm_overlap) a finished block's weight gradients go to the
-    # collective stream while the remaining blocks still run (only the stock CLIP block naming has a range lookup)
-    reducer = getattr(model, "_grad_reducer", None) if blk is None else None
-    blk = blk or (lambda i: _Blk(model, f"{prefix}.resblocks.{i}"))
-    R = M * T
-    dev = dx.device
-    g = torch.empty(R, 4 * W, device=dev, dtype=torch.bfloat16)
-    df = torch.empty(R, 4 * W, device=dev, dtype=torch.bfloat16)
-    dh = torch.empty(R, W, device=dev, dtype=torch.bfloat16)
-    # bias gradient of the last block's c_proj: column sums of the incoming gradient (the other blocks get theirs from
-    # the LayerNorm backward that produces their incoming gradient)
-    rs_rows = None if rowscale is None else rowscale.repeat_interleave(T, dim=2).contiguous()     # factor per row
-    if rowscale is not None:
-        ops.dropout_bf16_(dxb, 0.0, 0, rowscale=rowscale[layers - 1, 1], rows_per_scale=T)
-    ops.call("uniir_colsum_bf16", dxb, W, blk(layers - 1).g("bproj"), R, W)
-    for i in reversed(range(layers)):
-        b = blk(i)
-        x, qkv, ao, lse, x2, f, h1, h2 = saved[i]
-        saved[i] = None
-        # d(mlp): df = (dx @ Wproj) * act'(f); the same epilogue re-materialises g = act(f) for dWproj and sums
-        # df's columns into the c_fc bias gradient
-        ops.linear_dgrad(dxb, b.w16("wproj"), out=df, aux=f, act_out=g, colsum=b.g("bfc"), act=act)
-        ops.linear_wgrad(dxb, g, b.g("wproj"))
-        ops.linear_wgrad(df, h2, b.g("wfc"))
-        ops.linear_dgrad(df, b.w16("wfc"), out=dh)                               # dh := d ln_2 out
-        dx2 = torch.empty(R, W, device=dev, dtype=torch.float32)
-        ops.layernorm_bwd(x2, b.p32("ln2w"), dh, b.g("ln2w"), b.g("ln2b"), eps, dres=dx, dx=dx2, dx_bf16=dxb,
-                          rows=R, width=W, dx_colsum=b.g("bo"),             # d x2 also is d(out_proj out): its bias grad
-                          branch_scale=None if rs_rows is None else rs_rows[i, 0])
-        del x2, f, h2
-        ops.linear_wgrad(dxb, ao, b.g("wo"))
-        ops.linear_dgrad(dxb, b.w16("wo"), out=dh)                               # dh := d attn out
-        dqkv = ops.attention_bwd(qkv, ao, dh, lse, M, T, heads, causal)
-        del qkv, ao, lse
-        ops.linear_wgrad(dqkv, h1, b.g("wqkv"), dbias=b.g("bqkv"))             # + the in_proj bias gradient, same pass over dqkv
-        ops.linear_dgrad(dqkv, b.w16("wqkv"), out=dh)                            # dh := d ln_1 out
-        del dqkv, h1
-        ops.layernorm_bwd(x, b.p32("ln1w"), dh, b.g("ln1w"), b.g("ln1b"), eps, dres=dx2, dx=dx, dx_bf16=dxb,
-                          rows=R, width=W, dx_colsum=(blk(i - 1).g("bproj") if i > 0 else None),
-                          branch_scale=None if (rs_rows is None or i == 0) else rs_rows[i - 1, 1])
-        del x, dx2
-        if reducer is not None:
-            reducer.ready(*model.layer_grad_range(prefix, i))
-    return dx
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -687,17 +543,11 @@ class _TowerFn(torch.autograd.Function):
         ctx.model, ctx.which, ctx.M = model, which, M
         if M == 0:
             return torch.zeros(0, E, device=dev)
-        fl = model._flat
-
-        def p32(name):
-            o = fl["off"][name]
-            return fl["p32"][o:o + math.prod(fl["shapes"][name])].view(fl["shapes"][name])
-
         if model.precision == "fp32":
             if need_grad:
                 raise RuntimeError("precision='fp32' is a forward-only path (embedding extraction / parity); run it under "
                                    "torch.no_grad() or switch back to precision='bf16' for training")
-            return _encode_fp32(model, which, inp, p32)
+            return _encode_fp32(model, which, inp, model._flat.p)
         half = model.precision == "fp16"
         if half:
             if need_grad:
@@ -706,119 +556,77 @@ class _TowerFn(torch.autograd.Function):
             model._sync_half_shadow()
         elif model.precision != "bf16":
             raise RuntimeError(f"unknown precision {model.precision!r}")
-        if not _PY_TOWERS or half:
-            # the whole tower in one C call (csrc/tower.hip); the workspace is the activation stash of the backward
-            lib = _lib.load()
-            desc = model.tower_desc(which, half=half)
-            desc.pool_last_block = int(bool(model.pool_last_block))
-            emb = torch.empty(M, E, device=dev, dtype=torch.float32)
+        # the whole tower in one C call (csrc/tower.hip); the workspace is the activation stash of the backward
+        lib = _lib.load()
+        desc = model.tower_desc(which, half=half)
+        desc.pool_last_block = int(bool(model.pool_last_block))
+        emb = torch.empty(M, E, device=dev, dtype=torch.float32)
 
-            def ws_bytes(stash):
-                desc.stash_act = int(stash)
-                if which == "text" and model.pack_text:
-                    return lib.uniir_clip_tower_workspace_bytes_packed(C.byref(desc), M, text_row_offsets(inp)[1], int(need_grad))
-                return lib.uniir_clip_tower_workspace_bytes(C.byref(desc), M, int(need_grad))
-
-            stash = False
-            auto = False
-            if need_grad and model.stash_act is not False:
-                stash = True
-                if model.stash_act is None:        # automatic: decided once per (tower, batch), see CLIP.__init__
-                    auto = True
-                    key = which
-                    if key not in model._stash_choice:
-                        free, _ = torch.cuda.mem_get_info(dev)
-                        avail = free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-                        need_stash = ws_bytes(True)
-                        model._stash_choice[key] = need_stash + model.stash_margin_bytes <= avail
-                        model.stash_log.append(f"{which} tower, {M} items: act(f) stash {'ON' if model._stash_choice[key] else 'off'} "
-                                               f"(workspace {need_stash / 2**30:.1f} GiB, {avail / 2**30:.1f} GiB available, margin "
-                                               f"{model.stash_margin_bytes / 2**30:.0f} GiB)")
-                    stash = model._stash_choice[key]
+        def ws_bytes(stash):
             desc.stash_act = int(stash)
-            model.last_stash_act[which] = bool(stash)
-
-            def alloc_ws(nbytes_of):
-                """the tower workspace; when the automatic act(f) stash does not fit after all, re-plan this tower without it"""
-                nonlocal stash
-                try:
-                    n = nbytes_of()
-                    return n, (torch.empty(n, device=dev, dtype=torch.uint8) if n >= 0 else None)
-                except torch.OutOfMemoryError:
-                    if not (auto and stash):
-                        raise
-                    torch.cuda.empty_cache()
-                    stash = False
-                    model._stash_choice[which] = False
-                    model.last_stash_act[which] = False
-                    desc.stash_act = 0
-                    model.stash_log.append(f"{which} tower, {M} items: act(f) stash dropped after an out-of-memory error on its allocation")
-                    n = nbytes_of()
-                    return n, (torch.empty(n, device=dev, dtype=torch.uint8) if n >= 0 else None)
-
             if which == "text" and model.pack_text:
-                # exact packing: only the tokens up to each caption's EOT are rows of the text tower (text_row_offsets)
-                row_off, live = text_row_offsets(inp)
-                need, ws = alloc_ws(lambda: lib.uniir_clip_tower_workspace_bytes_packed(C.byref(desc), M, live, int(need_grad)))
-                if need < 0:
-                    raise RuntimeError("uniir_clip_tower: unsupported tower geometry")
-                _lib.check(lib.uniir_clip_tower_fwd_packed(C.byref(desc), inp.data_ptr(), M, row_off.data_ptr(), live, emb.data_ptr(),
-                                                           ws.data_ptr(), need, int(need_grad), ops._stream()), "clip_tower_fwd_packed")
-                model.last_text_rows = (live, M * cfg["context_length"])
-                if need_grad:
-                    ctx.stash = dict(ws=ws, inp=inp, ctower=True, row_off=row_off, live=live, stash_act=int(stash), join_to=model._leg_main,
-                                     pool_last=int(desc.pool_last_block))
-                return emb
-            need, ws = alloc_ws(lambda: lib.uniir_clip_tower_workspace_bytes(C.byref(desc), M, int(need_grad)))
+                return lib.uniir_clip_tower_workspace_bytes_packed(C.byref(desc), M, text_row_offsets(inp)[1], int(need_grad))
+            return lib.uniir_clip_tower_workspace_bytes(C.byref(desc), M, int(need_grad))
+
+        stash = False
+        auto = False
+        if need_grad and model.stash_act is not False:
+            stash = True
+            if model.stash_act is None:        # automatic: decided once per (tower, batch), see CLIP.__init__
+                auto = True
+                key = which
+                if key not in model._stash_choice:
+                    free, _ = torch.cuda.mem_get_info(dev)
+                    avail = free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+                    need_stash = ws_bytes(True)
+                    model._stash_choice[key] = need_stash + model.stash_margin_bytes <= avail
+                    model.stash_log.append(f"{which} tower, {M} items: act(f) stash {'ON' if model._stash_choice[key] else 'off'} "
+                                           f"(workspace {need_stash / 2**30:.1f} GiB, {avail / 2**30:.1f} GiB available, margin "
+                                           f"{model.stash_margin_bytes / 2**30:.0f} GiB)")
+                stash = model._stash_choice[key]
+        desc.stash_act = int(stash)
+        model.last_stash_act[which] = bool(stash)
+
+        def alloc_ws(nbytes_of):
+            """the tower workspace; when the automatic act(f) stash does not fit after all, re-plan this tower without it"""
+            nonlocal stash
+            try:
+                n = nbytes_of()
+                return n, (torch.empty(n, device=dev, dtype=torch.uint8) if n >= 0 else None)
+            except torch.OutOfMemoryError:
+                if not (auto and stash):
+                    raise
+                torch.cuda.empty_cache()
+                stash = False
+                model._stash_choice[which] = False
+                model.last_stash_act[which] = False
+                desc.stash_act = 0
+                model.stash_log.append(f"{which} tower, {M} items: act(f) stash dropped after an out-of-memory error on its allocation")
+                n = nbytes_of()
+                return n, (torch.empty(n, device=dev, dtype=torch.uint8) if n >= 0 else None)
+
+        if which == "text" and model.pack_text:
+            # exact packing: only the tokens up to each caption's EOT are rows of the text tower (text_row_offsets)
+            row_off, live = text_row_offsets(inp)
+            need, ws = alloc_ws(lambda: lib.uniir_clip_tower_workspace_bytes_packed(C.byref(desc), M, live, int(need_grad)))
             if need < 0:
                 raise RuntimeError("uniir_clip_tower: unsupported tower geometry")
-            inp = inp.float().contiguous() if which == "image" else inp
-            _lib.check(lib.uniir_clip_tower_fwd(C.byref(desc), inp.data_ptr(), M, emb.data_ptr(), ws.data_ptr(), need,
-                                                int(need_grad), ops._stream()), "clip_tower_fwd")
+            _lib.check(lib.uniir_clip_tower_fwd_packed(C.byref(desc), inp.data_ptr(), M, row_off.data_ptr(), live, emb.data_ptr(),
+                                                       ws.data_ptr(), need, int(need_grad), ops._stream()), "clip_tower_fwd_packed")
+            model.last_text_rows = (live, M * cfg["context_length"])
             if need_grad:
-                ctx.stash = dict(ws=ws, inp=inp, ctower=True, stash_act=int(stash), join_to=model._leg_main,
+                ctx.stash = dict(ws=ws, inp=inp, row_off=row_off, live=live, stash_act=int(stash), join_to=model._leg_main,
                                  pool_last=int(desc.pool_last_block))
             return emb
-        if which == "image":
-            W, P, L = cfg["vision_width"], cfg["vision_patch_size"], cfg["vision_layers"]
-            res = cfg["image_resolution"]
-            G = (res // P) ** 2
-            T = G + 1
-            heads = W // 64
-            patches = torch.empty(M * G, model.kpad, device=dev, dtype=torch.bfloat16)
-            ops.call("uniir_patchify", inp.float(), patches, M, res, P, model.kpad)
-            po = ops.linear_fwd(patches, model._conv16)
-            x0 = torch.empty(M * T, W, device=dev, dtype=torch.float32)
-            ops.call("uniir_vit_assemble", po, p32("visual.class_embedding"), p32("visual.positional_embedding"), x0,
-                     M, T, W)
-            del po
-            x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
-            ops.layernorm_fwd(x0, p32("visual.ln_pre.weight"), p32("visual.ln_pre.bias"), out_f32=x, rows=M * T, width=W)
-            x, saved = _tower_fwd(model, "visual.transformer", L, x, M, T, W, heads, False, need_grad)
-            rows = torch.empty(M, W, device=dev, dtype=torch.float32)
-            ops.call("uniir_gather_rows", x, None, rows, M, T, W)
-            pooled = ops.layernorm_fwd(rows, p32("visual.ln_post.weight"), p32("visual.ln_post.bias"), rows=M, width=W)
-            emb = torch.empty(M, E, device=dev, dtype=torch.float32)
-            ops.gemm(pooled, model.w16("visual.proj"), emb, M, E, W, W, E, E, b_tmaj=True, epilogue=ops.EPI_F32)
-            if need_grad:
-                ctx.stash = dict(patches=patches, x0=x0, saved=saved, rows=rows, pooled=pooled, T=T, W=W, L=L,
-                                 heads=heads, idx=None)
-            return emb
-        # text tower
-        W, L, ctxlen = cfg["transformer_width"], cfg["transformer_layers"], cfg["context_length"]
-        heads, T = cfg["transformer_heads"], ctxlen
-        x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
-        eot = torch.empty(M, device=dev, dtype=torch.int32)
-        ops.call("uniir_text_embed", inp, p32("token_embedding.weight"), p32("positional_embedding"), x, eot, M, T, W,
-                 cfg["vocab_size"])
-        x, saved = _tower_fwd(model, "transformer", L, x, M, T, W, heads, True, need_grad)
-        rows = torch.empty(M, W, device=dev, dtype=torch.float32)
-        ops.call("uniir_gather_rows", x, eot, rows, M, T, W)
-        pooled = ops.layernorm_fwd(rows, p32("ln_final.weight"), p32("ln_final.bias"), rows=M, width=W)
-        emb = torch.empty(M, E, device=dev, dtype=torch.float32)
-        ops.gemm(pooled, model.w16("text_projection"), emb, M, E, W, W, E, E, b_tmaj=True, epilogue=ops.EPI_F32)
+        need, ws = alloc_ws(lambda: lib.uniir_clip_tower_workspace_bytes(C.byref(desc), M, int(need_grad)))
+        if need < 0:
+            raise RuntimeError("uniir_clip_tower: unsupported tower geometry")
+        inp = inp.float().contiguous() if which == "image" else inp
+        _lib.check(lib.uniir_clip_tower_fwd(C.byref(desc), inp.data_ptr(), M, emb.data_ptr(), ws.data_ptr(), need,
+                                            int(need_grad), ops._stream()), "clip_tower_fwd")
         if need_grad:
-            ctx.stash = dict(text=inp, saved=saved, rows=rows, pooled=pooled, T=T, W=W, L=L, heads=heads, idx=eot)
+            ctx.stash = dict(ws=ws, inp=inp, stash_act=int(stash), join_to=model._leg_main,
+                             pool_last=int(desc.pool_last_block))
         return emb
 
     @staticmethod
@@ -828,81 +636,36 @@ class _TowerFn(torch.autograd.Function):
             return None, None, None, None
         st = ctx.stash
         ctx.stash = None
-        if st.get("ctower"):
-            lib = _lib.load()
-            desc = model.tower_desc(which)
-            desc.stash_act = st["stash_act"]        # part of the workspace layout: the value the forward ran with
-            desc.pool_last_block = st["pool_last"]
-            ws, inp, stream = st["ws"], st["inp"], ops._stream()
-            demb = demb.contiguous().float()
-            need = ws.numel()
-            reducer = getattr(model, "_grad_reducer", None)
-            L = desc.layers
-            prefix = "visual.transformer" if which == "image" else "transformer"
-            if "row_off" in st:         # the text tower on packed rows
-                ro, live = st["row_off"].data_ptr(), st["live"]
-                _lib.check(lib.uniir_clip_tower_bwd_head_packed(C.byref(desc), demb.data_ptr(), M, ro, live, ws.data_ptr(), need, stream),
-                           "tower_bwd_head_packed")
-                for lo, hi in ([(0, L)] if reducer is None else [(i, i + 1) for i in reversed(range(L))]):
-                    _lib.check(lib.uniir_clip_tower_bwd_blocks_packed(C.byref(desc), M, ro, live, lo, hi, ws.data_ptr(), need, stream),
-                               "tower_bwd_blocks_packed")
-                    if reducer is not None:
-                        reducer.ready(*model.layer_grad_range(prefix, lo))
-                _lib.check(lib.uniir_clip_tower_bwd_stem_packed(C.byref(desc), inp.data_ptr(), M, ro, live, ws.data_ptr(), need, stream),
-                           "tower_bwd_stem_packed")
-                _join_backward(st, demb)
-                return None, None, None, None
-            _lib.check(lib.uniir_clip_tower_bwd_head(C.byref(desc), demb.data_ptr(), M, ws.data_ptr(), need, stream), "tower_bwd_head")
-            if reducer is None:
-                _lib.check(lib.uniir_clip_tower_bwd_blocks(C.byref(desc), M, 0, L, ws.data_ptr(), need, stream), "tower_bwd_blocks")
-            else:       # DDP overlap: hand every finished block's weight gradients to the collective stream
-                for i in reversed(range(L)):
-                    _lib.check(lib.uniir_clip_tower_bwd_blocks(C.byref(desc), M, i, i + 1, ws.data_ptr(), need, stream),
-                               "tower_bwd_blocks")
-                    reducer.ready(*model.layer_grad_range(prefix, i))
-            _lib.check(lib.uniir_clip_tower_bwd_stem(C.byref(desc), inp.data_ptr(), M, ws.data_ptr(), need, stream), "tower_bwd_stem")
+        lib = _lib.load()
+        desc = model.tower_desc(which)
+        desc.stash_act = st["stash_act"]        # part of the workspace layout: the value the forward ran with
+        desc.pool_last_block = st["pool_last"]
+        ws, inp, stream = st["ws"], st["inp"], ops._stream()
+        demb = demb.contiguous().float()
+        need = ws.numel()
+        L = desc.layers
+        block_done = model.block_done("visual.transformer" if which == "image" else "transformer")
+        if "row_off" in st:         # the text tower on packed rows
+            ro, live = st["row_off"].data_ptr(), st["live"]
+            _lib.check(lib.uniir_clip_tower_bwd_head_packed(C.byref(desc), demb.data_ptr(), M, ro, live, ws.data_ptr(), need, stream),
+                       "tower_bwd_head_packed")
+            for lo, hi in ([(0, L)] if block_done is None else [(i, i + 1) for i in reversed(range(L))]):
+                _lib.check(lib.uniir_clip_tower_bwd_blocks_packed(C.byref(desc), M, ro, live, lo, hi, ws.data_ptr(), need, stream),
+                           "tower_bwd_blocks_packed")
+                if block_done is not None:
+                    block_done(lo)
+            _lib.check(lib.uniir_clip_tower_bwd_stem_packed(C.byref(desc), inp.data_ptr(), M, ro, live, ws.data_ptr(), need, stream),
+                       "tower_bwd_stem_packed")
             _join_backward(st, demb)
             return None, None, None, None
-        cfg = model.cfg
-        fl = model._flat
-        dev = demb.device
-        E = cfg["embed_dim"]
-        T, W, L, heads = st["T"], st["W"], st["L"], st["heads"]
-        R = M * T
-
-        def p32(name):
-            o = fl["off"][name]
-            return fl["p32"][o:o + math.prod(fl["shapes"][name])].view(fl["shapes"][name])
-
-        image = which == "image"
-        proj_n = "visual.proj" if image else "text_projection"
-        lnw, lnb = (("visual.ln_post.weight", "visual.ln_post.bias") if image else ("ln_final.weight", "ln_final.bias"))
-        prefix = "visual.transformer" if image else "transformer"
-        demb16 = demb.contiguous().to(torch.bfloat16)
-        # dproj[W,E] += pooled^T @ demb ; dpooled[M,W] = demb @ proj^T
-        ops.gemm(st["pooled"], demb16, model.grad_view(proj_n), W, E, M, W, E, E, a_tmaj=True, b_tmaj=True,
-                 epilogue=ops.EPI_ATOMIC_F32)
-        dpooled = torch.empty(M, W, device=dev, dtype=torch.bfloat16)
-        ops.gemm(demb16, model.w16(proj_n), dpooled, M, W, E, E, E, W)
-        drows = ops.layernorm_bwd(st["rows"], p32(lnw), dpooled, model.grad_view(lnw), model.grad_view(lnb), rows=M,
-                                  width=W)
-        dx = torch.zeros(R, W, device=dev, dtype=torch.float32)
-        ops.call("uniir_scatter_rows", drows, st["idx"], dx, M, T, W)
-        dxb = torch.empty(R, W, device=dev, dtype=torch.bfloat16)
-        ops.call("uniir_cast_f32_to_bf16", dx, dxb, dx.numel())
-        dx = _tower_bwd(model, prefix, L, dx, dxb, st["saved"], M, T, W, heads, not image)
-        if image:
-            P = cfg["vision_patch_size"]
-            G = T - 1
-            dx0 = ops.layernorm_bwd(st["x0"], p32("visual.ln_pre.weight"), dx, model.grad_view("visual.ln_pre.weight"),
-                                    model.grad_view("visual.ln_pre.bias"), rows=R, width=W)
-            dpo = torch.empty(M * G, W, device=dev, dtype=torch.bfloat16)
-            ops.call("uniir_vit_assemble_bwd", dx0, dpo, model.grad_view("visual.class_embedding"),
-                     model.grad_view("visual.positional_embedding"), M, T, W)
-            model._dconv.zero_()
-            ops.linear_wgrad(dpo, st["patches"], model._dconv)
-            ops.call("uniir_unpad_add", model._dconv, model.grad_view("visual.conv1.weight"), W, 3 * P * P, model.kpad)
-        else:
-            ops.call("uniir_text_embed_bwd", st["text"], dx, model.grad_view("token_embedding.weight"),
-                     model.grad_view("positional_embedding"), M, T, W, cfg["vocab_size"])
+        _lib.check(lib.uniir_clip_tower_bwd_head(C.byref(desc), demb.data_ptr(), M, ws.data_ptr(), need, stream), "tower_bwd_head")
+        if block_done is None:
+            _lib.check(lib.uniir_clip_tower_bwd_blocks(C.byref(desc), M, 0, L, ws.data_ptr(), need, stream), "tower_bwd_blocks")
+        else:       # DDP overlap: hand every finished block's weight gradients to the collective stream
+            for i in reversed(range(L)):
+                _lib.check(lib.uniir_clip_tower_bwd_blocks(C.byref(desc), M, i, i + 1, ws.data_ptr(), need, stream),
+                           "tower_bwd_blocks")
+                block_done(i)
+        _lib.check(lib.uniir_clip_tower_bwd_stem(C.byref(desc), inp.data_ptr(), M, ws.data_ptr(), need, stream), "tower_bwd_stem")
+        _join_backward(st, demb)
         return None, None, None, None

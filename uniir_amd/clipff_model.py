@@ -12,8 +12,7 @@ import math
 import torch
 
 from . import ops
-from .blip_model import FlatStore
-from .clip_model import _tower_bwd, _tower_fwd
+from .resblocks import clip_block_names, tower_bwd, tower_fwd
 
 T5_EPS = 1e-6
 T5_DROPOUT = 0.1      # transformers T5Config default dropout_rate (clip_ff.py:82,90 build T5Config() without overriding it)
@@ -182,14 +181,14 @@ def t5_backward(st, prefix, dpooled, stash, heads, layers):
 # ------------------------------------------------------------------------------------------------------------
 def vision_tokens_fwd(model, image, save):
     """clip_ff.py:35-59 -> fp32 [M*T, E] = ln_post(all tokens) @ proj"""
-    cfg, fl = model.cfg, model._flat
+    cfg, st = model.cfg, model._flat
     dev = image.device
     M = image.shape[0]
     W, P, L, res, E = cfg["vision_width"], cfg["vision_patch_size"], cfg["vision_layers"], cfg["image_resolution"], cfg["embed_dim"]
     G_ = (res // P) ** 2
     T = G_ + 1
     heads = W // 64
-    p32 = lambda n: fl["p32"][fl["off"][n]:fl["off"][n] + math.prod(fl["shapes"][n])].view(fl["shapes"][n])
+    p32 = st.p
     patches = torch.empty(M * G_, model.kpad, device=dev, dtype=torch.bfloat16)
     ops.call("uniir_patchify", image.float().contiguous(), patches, M, res, P, model.kpad)
     po = ops.linear_fwd(patches, model._conv16)
@@ -198,53 +197,54 @@ def vision_tokens_fwd(model, image, save):
     del po
     x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
     ops.layernorm_fwd(x0, p32("visual.ln_pre.weight"), p32("visual.ln_pre.bias"), out_f32=x, rows=M * T, width=W)
-    x, saved = _tower_fwd(model, "visual.transformer", L, x, M, T, W, heads, False, save)
+    x, saved = tower_fwd(st, lambda i: clip_block_names("visual.transformer", i), L, x, M, T, W, heads, False, save)
     ln = ops.layernorm_fwd(x, p32("visual.ln_post.weight"), p32("visual.ln_post.bias"), rows=M * T, width=W)
     tok = torch.empty(M * T, E, device=dev, dtype=torch.float32)
-    ops.gemm(ln, model.w16("visual.proj"), tok, M * T, E, W, W, E, E, b_tmaj=True, epilogue=ops.EPI_F32)
+    ops.gemm(ln, st.w16("visual.proj"), tok, M * T, E, W, W, E, E, b_tmaj=True, epilogue=ops.EPI_F32)
     stash = dict(patches=patches, x0=x0, saved=saved, xf=x, ln=ln, M=M, T=T) if save else None
     return tok, T, stash
 
 
 def vision_tokens_bwd(model, dtok, stash):
-    cfg, fl = model.cfg, model._flat
+    cfg, st = model.cfg, model._flat
     M, T = stash["M"], stash["T"]
     W, P, L, E = cfg["vision_width"], cfg["vision_patch_size"], cfg["vision_layers"], cfg["embed_dim"]
     R, dev, heads = M * T, dtok.device, W // 64
-    p32 = lambda n: fl["p32"][fl["off"][n]:fl["off"][n] + math.prod(fl["shapes"][n])].view(fl["shapes"][n])
+    p32, G = st.p, st.grad_view
     d16 = torch.empty(R, E, device=dev, dtype=torch.bfloat16)
     ops.call("uniir_cast_f32_to_bf16", dtok.contiguous(), d16, d16.numel())
     # dproj[W,E] += ln^T @ dtok ; dln[R,W] = dtok @ proj^T
-    ops.gemm(stash["ln"], d16, model.grad_view("visual.proj"), W, E, R, W, E, E, a_tmaj=True, b_tmaj=True,
+    ops.gemm(stash["ln"], d16, G("visual.proj"), W, E, R, W, E, E, a_tmaj=True, b_tmaj=True,
              epilogue=ops.EPI_ATOMIC_F32, k_splits=ops.wgrad_splits(R, ((W + 255) // 256) * ((E + 255) // 256)))
     dln = torch.empty(R, W, device=dev, dtype=torch.bfloat16)
-    ops.gemm(d16, model.w16("visual.proj"), dln, R, W, E, E, E, W)
+    ops.gemm(d16, st.w16("visual.proj"), dln, R, W, E, E, E, W)
     dxb = torch.empty(R, W, device=dev, dtype=torch.bfloat16)
-    dx = ops.layernorm_bwd(stash["xf"], p32("visual.ln_post.weight"), dln, model.grad_view("visual.ln_post.weight"),
-                           model.grad_view("visual.ln_post.bias"), dx_bf16=dxb, rows=R, width=W)
-    dx = _tower_bwd(model, "visual.transformer", L, dx, dxb, stash["saved"], M, T, W, heads, False)
-    dx0 = ops.layernorm_bwd(stash["x0"], p32("visual.ln_pre.weight"), dx, model.grad_view("visual.ln_pre.weight"),
-                            model.grad_view("visual.ln_pre.bias"), rows=R, width=W)
+    dx = ops.layernorm_bwd(stash["xf"], p32("visual.ln_post.weight"), dln, G("visual.ln_post.weight"),
+                           G("visual.ln_post.bias"), dx_bf16=dxb, rows=R, width=W)
+    dx = tower_bwd(st, lambda i: clip_block_names("visual.transformer", i), L, dx, dxb, stash["saved"], M, T, W, heads, False,
+                   block_done=model.block_done("visual.transformer"))
+    dx0 = ops.layernorm_bwd(stash["x0"], p32("visual.ln_pre.weight"), dx, G("visual.ln_pre.weight"),
+                            G("visual.ln_pre.bias"), rows=R, width=W)
     dpo = torch.empty(M * (T - 1), W, device=dev, dtype=torch.bfloat16)
-    ops.call("uniir_vit_assemble_bwd", dx0, dpo, model.grad_view("visual.class_embedding"),
-             model.grad_view("visual.positional_embedding"), M, T, W)
+    ops.call("uniir_vit_assemble_bwd", dx0, dpo, G("visual.class_embedding"),
+             G("visual.positional_embedding"), M, T, W)
     model._dconv.zero_()
     ops.linear_wgrad(dpo, stash["patches"], model._dconv)
-    ops.call("uniir_unpad_add", model._dconv, model.grad_view("visual.conv1.weight"), W, 3 * P * P, model.kpad)
+    ops.call("uniir_unpad_add", model._dconv, G("visual.conv1.weight"), W, 3 * P * P, model.kpad)
 
 
 def text_tokens_fwd(model, text, save):
     """clip_ff.py:148-156 -> fp32 [M*77, W] = ln_final(all tokens)"""
-    cfg, fl = model.cfg, model._flat
+    cfg, st = model.cfg, model._flat
     dev = text.device
     M = text.shape[0]
     W, L, T, heads = cfg["transformer_width"], cfg["transformer_layers"], cfg["context_length"], cfg["transformer_heads"]
-    p32 = lambda n: fl["p32"][fl["off"][n]:fl["off"][n] + math.prod(fl["shapes"][n])].view(fl["shapes"][n])
+    p32 = st.p
     x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
     eot = torch.empty(M, device=dev, dtype=torch.int32)
     ops.call("uniir_text_embed", text, p32("token_embedding.weight"), p32("positional_embedding"), x, eot, M, T, W,
              cfg["vocab_size"])
-    x, saved = _tower_fwd(model, "transformer", L, x, M, T, W, heads, True, save)
+    x, saved = tower_fwd(st, lambda i: clip_block_names("transformer", i), L, x, M, T, W, heads, True, save)
     tok = torch.empty(M * T, W, device=dev, dtype=torch.float32)
     ops.layernorm_fwd(x, p32("ln_final.weight"), p32("ln_final.bias"), out_f32=tok, rows=M * T, width=W)
     stash = dict(text=text, saved=saved, xf=x, M=M, T=T) if save else None
@@ -252,17 +252,18 @@ def text_tokens_fwd(model, text, save):
 
 
 def text_tokens_bwd(model, dtok, stash):
-    cfg, fl = model.cfg, model._flat
+    cfg, st = model.cfg, model._flat
     M, T = stash["M"], stash["T"]
     W, L, heads = cfg["transformer_width"], cfg["transformer_layers"], cfg["transformer_heads"]
     R, dev = M * T, dtok.device
-    p32 = lambda n: fl["p32"][fl["off"][n]:fl["off"][n] + math.prod(fl["shapes"][n])].view(fl["shapes"][n])
+    p32, G = st.p, st.grad_view
     dxb = torch.empty(R, W, device=dev, dtype=torch.bfloat16)
-    dx = ops.layernorm_bwd(stash["xf"], p32("ln_final.weight"), dtok.contiguous(), model.grad_view("ln_final.weight"),
-                           model.grad_view("ln_final.bias"), dx_bf16=dxb, rows=R, width=W)
-    dx = _tower_bwd(model, "transformer", L, dx, dxb, stash["saved"], M, T, W, heads, True)
-    ops.call("uniir_text_embed_bwd", stash["text"], dx, model.grad_view("token_embedding.weight"),
-             model.grad_view("positional_embedding"), M, T, W, cfg["vocab_size"])
+    dx = ops.layernorm_bwd(stash["xf"], p32("ln_final.weight"), dtok.contiguous(), G("ln_final.weight"),
+                           G("ln_final.bias"), dx_bf16=dxb, rows=R, width=W)
+    dx = tower_bwd(st, lambda i: clip_block_names("transformer", i), L, dx, dxb, stash["saved"], M, T, W, heads, True,
+                   block_done=model.block_done("transformer"))
+    ops.call("uniir_text_embed_bwd", stash["text"], dx, G("token_embedding.weight"),
+             G("positional_embedding"), M, T, W, cfg["vocab_size"])
 
 
 class FusionFn(torch.autograd.Function):
@@ -299,20 +300,3 @@ class FusionFn(torch.autograd.Function):
         text_tokens_bwd(owner.clip_model, dt, tst)
         vision_tokens_bwd(owner.clip_model, di, ist)
         return None, None, None, None
-
-
-def init_t5_store(owner, d_model, heads, device, seed=0, d_ff=2048, layers=2):
-    """random init like transformers' T5 _init_weights scales (only used when no checkpoint is loaded)"""
-    shapes = t5_param_shapes(d_model, heads, 64, d_ff, layers)
-    st = FlatStore(shapes, device, True)
-    g = torch.Generator().manual_seed(seed)
-    for n, shp in shapes:
-        if n.endswith("layer_norm.weight"):
-            v = torch.ones(shp)
-        elif "relative_attention_bias" in n:
-            v = torch.randn(shp, generator=g) * d_model ** -0.5
-        else:
-            v = torch.randn(shp, generator=g) * shp[-1] ** -0.5
-        st.p(n).copy_(v)
-    st.refresh_shadow()
-    return st, shapes

@@ -13,6 +13,7 @@ from torch import nn
 from uniir_amd import clip_front
 from uniir_amd.blip_model import _attach
 from uniir_amd.clipff_model import FusionFn, t5_param_shapes
+from uniir_amd.flat_store import FlatStore
 from uniir_amd.losses import HardNegNCEFn, InBatchNCEFn
 
 _T5_DMODEL = {"ViT-B/32": 512, "ViT-L/14": 768}
@@ -64,25 +65,18 @@ class CLIPFeatureFusion(nn.Module):
         return [(n, self.t5_layers.get_parameter(n)) for n, _ in self._t5_shapes]
 
     def _ensure_t5(self):
-        from uniir_amd.blip_model import FlatStore
         dev = self.clip_model.logit_scale.device
         if dev.type != "cuda":
             raise RuntimeError("uniir_amd CLIPFeatureFusion runs on an MI355X only (no CPU path); move the model to cuda")
-        st = self._t5
         named = self._t5_named()
-        if st is None or st.p32.device != dev or any(p.data_ptr() != st.p32.data_ptr() + 4 * st.off[n] for n, p in named):
-            st = FlatStore(self._t5_shapes, dev, True)
-            for n, p in named:
-                st.p(n).copy_(p.data.float())
-                p.data = st.p(n)
-                p.grad = st.grad_view(n)
-            self._t5 = st
+        if self._t5 is None or not self._t5.holds(named):
+            self._t5 = FlatStore.adopt(named, dev)
             self._t5_version = -1
         ver = sum(p._version for _, p in named)
         if ver != self._t5_version:
-            st.refresh_shadow()
+            self._t5.refresh_shadow()
             self._t5_version = ver
-        return st
+        return self._t5
 
     def t5_optimizer_group(self, lr, weight_decay=0.2):
         return _T5Group(self, lr, weight_decay)
@@ -90,9 +84,7 @@ class CLIPFeatureFusion(nn.Module):
     def zero_grad(self, set_to_none=False):
         self.clip_model.zero_grad()
         if self._t5 is not None:
-            self._t5.g32.zero_()
-            for n, p in self._t5_named():
-                p.grad = self._t5.grad_view(n)
+            self._t5.zero_grad(self._t5_named())
 
     # ---- reference surface -----------------------------------------------------------------------------------
     def get_img_preprocess_fn(self):

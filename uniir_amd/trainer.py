@@ -18,48 +18,54 @@ from . import comm, ops
 
 
 class NativeAdamW(torch.optim.Optimizer):
-    """torch.optim.AdamW semantics over the CLIP module's flat parameter buffer (two groups: [0, split) without weight
-    decay, [split, total) with).  It is a real torch Optimizer (param_groups / lr schedulers / state_dict work)."""
+    """torch.optim.AdamW semantics over flat parameter stores (flat_store.FlatStore): the model's own store -- param group 0
+    without weight decay, group 1 with -- and one param group per extra store.  Each store gets one fused AdamW launch per run of
+    consecutive tensors of one group (FlatStore.ranges) and one pair of moment buffers.  It is a real torch Optimizer
+    (param_groups / lr schedulers / state_dict work)."""
 
     def __init__(self, clip_model, lr=1e-5, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2, allreduce=True, extra=None,
                  overlap=True, bucket_bytes=64 << 20):
-        """extra: further flat parameter stores, each one param group of its own -- objects with .params (list of
-        nn.Parameter), .store() (-> FlatStore with p32 / g32 / w16_buf / total), .weight_decay and .lr (CLIP_FF's T5
-        stack: clip_featurefusion/train.py:52-61 gives it weight decay 0.2 on everything and its own learning rate)"""
+        """clip_model: the model that owns the main store (CLIP, BLIPFeatureFusion): _ensure_flat() -> its FlatStore,
+        optimizer_groups() -> (no-decay params, decay params), adamw_group(name) -> 0 / 1, or None for a tensor that is not
+        stepped (BLIP_SF's frozen cross-attention).
+        extra: further flat parameter stores, each one param group of its own -- objects with .params (list of nn.Parameter),
+        .store() (-> FlatStore), .weight_decay and .lr (CLIP_FF's T5 stack: clip_featurefusion/train.py:52-61 gives it weight
+        decay 0.2 on everything and its own learning rate)"""
         self.clip = clip_model
         self.extra = list(extra or [])
-        self.extra_mv = [None] * len(self.extra)
-        if hasattr(clip_model, "optimizer_groups"):      # e.g. BLIPFeatureFusion: one group, uniform weight decay
-            nd, d = clip_model.optimizer_groups()
-        else:
-            from .clip_model import _is_no_decay
-            named = list(clip_model.named_parameters())
-            nd = [p for n, p in named if _is_no_decay(n, p)]
-            d = [p for n, p in named if not _is_no_decay(n, p)]
+        nd, d = clip_model.optimizer_groups()
         groups = [{"params": nd, "weight_decay": 0.0}, {"params": d, "weight_decay": weight_decay}]
         groups += [{"params": e.params, "weight_decay": e.weight_decay, "lr": e.lr} for e in self.extra]
         super().__init__(groups, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        # (store getter, tensor name -> param group index) of every store, the model's own first
+        self.sources = [(clip_model._ensure_flat, clip_model.adamw_group)]
+        self.sources += [(e.store, lambda name, gi=2 + i: gi) for i, e in enumerate(self.extra)]
+        self.mv = [None] * len(self.sources)            # (exp_avg, exp_avg_sq) of every store
+        self._ranges = [(None, None)] * len(self.sources)      # (store, its AdamW ranges)
         self.allreduce = allreduce
         self.overlap, self.bucket_bytes = overlap, bucket_bytes
         self.reducer = None
         self.last_collectives = 0
-        self.m = self.v = None
         self.opt_step = 0
 
+    def _moments(self, i, st):
+        mv = self.mv[i]
+        if mv is None or mv[0].numel() != st.total:
+            mv = (torch.zeros_like(st.p32), torch.zeros_like(st.p32))
+        elif mv[0].device != st.dev:          # resumed from a checkpoint mapped to the CPU
+            mv = tuple(t.to(st.dev) for t in mv)
+        self.mv[i] = mv
+        return mv
+
     def _buffers(self):
-        fl = self.clip._ensure_flat()
-        if self.m is None or self.m.numel() != fl["total"] or self.m.device != fl["p32"].device:
-            m, v = torch.zeros_like(fl["p32"]), torch.zeros_like(fl["p32"])
-            if self.m is not None and self.m.numel() == fl["total"]:
-                m.copy_(self.m)
-                v.copy_(self.v)
-            self.m, self.v = m, v
+        st = self.clip._ensure_flat()
+        self._moments(0, st)
         if self.allreduce and self.overlap and comm.world() > 1:
-            if self.reducer is None or self.reducer.flat.data_ptr() != fl["g32"].data_ptr():
-                self.reducer = comm.GradReducer(fl["g32"], self.bucket_bytes)
+            if self.reducer is None or self.reducer.flat.data_ptr() != st.g32.data_ptr():
+                self.reducer = comm.GradReducer(st.g32, self.bucket_bytes)
         else:
             self.reducer = None
-        return fl
+        return st
 
     def arm_overlap(self, last_micro_batch=True):
         """call before backward(): on the LAST micro-batch of an accumulation window the tower backward hands every finished
@@ -71,41 +77,31 @@ class NativeAdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        fl = self._buffers()
+        main = self._buffers()
         world = comm.world() if self.allreduce else 1
-        extra_reduced = set()
+        reduced = set()                    # gradient buffers already all-reduced in this step
         if world > 1:
+            self.last_collectives = 0
             if self.reducer is not None:           # blocks already reduced during backward; now the remainder + wait
-                self.last_collectives, extra_reduced = self.reducer.finish()
-            else:
-                comm.allreduce_sum_(fl["g32"])     # one RCCL all-reduce; the mean is folded into grad_scale
-                self.last_collectives = 1
+                self.last_collectives, reduced = self.reducer.finish()
+                reduced.add(main.g32.data_ptr())
         self.clip._grad_reducer = None
         self.opt_step += 1
-        split, total = fl["split"], fl["total"]
-        # (lo, hi, param-group index); default: [0, split) without weight decay, [split, total) with
-        ranges = fl.get("ranges") or [(0, split, 0), (split, total, 1)]
-        for lo, hi, gi in ranges:
-            group = self.param_groups[gi]
-            if hi > lo:
-                b1, b2 = group["betas"]
-                ops.call("uniir_adamw_step", fl["p32"][lo:hi], fl["g32"][lo:hi], self.m[lo:hi], self.v[lo:hi],
-                         fl["w16"][lo:hi], hi - lo, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                         self.opt_step, 1.0 / world)
-        self.clip._refresh_conv()
-        for i, (e, group) in enumerate(zip(self.extra, self.param_groups[2:])):
-            st = e.store()
-            if self.extra_mv[i] is None or self.extra_mv[i][0].numel() != st.total:
-                self.extra_mv[i] = (torch.zeros_like(st.p32), torch.zeros_like(st.p32))
-            elif self.extra_mv[i][0].device != st.p32.device:     # resumed from a checkpoint mapped to the CPU
-                self.extra_mv[i] = tuple(t.to(st.p32.device) for t in self.extra_mv[i])
-            if world > 1 and st.g32.data_ptr() not in extra_reduced:     # not handed to the reducer during backward
+        for i, (store, group_of) in enumerate(self.sources):
+            st = main if i == 0 else store()
+            m, v = self._moments(i, st)
+            if world > 1 and st.g32.data_ptr() not in reduced:     # one all-reduce of the whole buffer
                 comm.allreduce_sum_(st.g32)
                 self.last_collectives += 1
-            b1, b2 = group["betas"]
-            m, v = self.extra_mv[i]
-            ops.call("uniir_adamw_step", st.p32, st.g32, m, v, st.w16_buf, st.total, float(group["lr"]), b1, b2,
-                     group["eps"], group["weight_decay"], self.opt_step, 1.0 / world)
+            if self._ranges[i][0] is not st:
+                self._ranges[i] = (st, st.ranges(group_of))
+            for lo, hi, gi in self._ranges[i][1]:
+                group = self.param_groups[gi]
+                b1, b2 = group["betas"]
+                ops.call("uniir_adamw_step", st.p32[lo:hi], st.g32[lo:hi], m[lo:hi], v[lo:hi], st.w16_buf[lo:hi], hi - lo,
+                         float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], self.opt_step, 1.0 / world)
+            if i == 0:
+                self.clip._refresh_conv()      # the padded bf16 patch-embedding weights are not part of the shadow
 
     def zero_grad(self, set_to_none=False):
         self.clip._ensure_flat()
@@ -114,13 +110,14 @@ class NativeAdamW(torch.optim.Optimizer):
             e.store().g32.zero_()
 
     def state_dict(self):
-        return {"opt_step": self.opt_step, "exp_avg": self.m, "exp_avg_sq": self.v, "extra": self.extra_mv,
+        exp_avg, exp_avg_sq = self.mv[0] or (None, None)
+        return {"opt_step": self.opt_step, "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq, "extra": self.mv[1:],
                 "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
 
     def load_state_dict(self, sd):
         self.opt_step = sd["opt_step"]
-        self.m, self.v = sd["exp_avg"], sd["exp_avg_sq"]
-        self.extra_mv = list(sd.get("extra", self.extra_mv))
+        main = None if sd["exp_avg"] is None else (sd["exp_avg"], sd["exp_avg_sq"])
+        self.mv = [main] + list(sd.get("extra", self.mv[1:]))
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update(s)
 
