@@ -51,6 +51,7 @@ int uniir_reduce_scratch(void* buf, int64_t bytes, void* stream);
  *   C[M,N] = alpha * op(A)[M,K] . op(B)[K,N]  (+ epilogue)
  * a_tmaj = 0: A stored [M][lda] (K contiguous);  1: A stored [K][lda] (M contiguous)
  * b_tmaj = 0: B stored [N][ldb] (K contiguous; torch Linear weight layout);  1: B stored [K][ldb]
+ * v = alpha * (op(A) . op(B))[m][n] in fp32; every epilogue below starts from it.
  * Requirements: K-contiguous operands need K % 8 == 0, M/N-contiguous ones need that extent % 8 == 0,
  * N % 8 == 0, all base pointers and leading dimensions multiples of 8 elements (16 B).
  * ---------------------------------------------------------------------------------------------- */
@@ -58,9 +59,10 @@ enum {
     UNIIR_EPI_BF16 = 0,          /* C(bf16) = v + bias?                                          */
     UNIIR_EPI_BIAS_ACT = 1,      /* f = bf16(v + bias) -> C ; act(f) -> C2 (both bf16)           */
     UNIIR_EPI_RESID_F32 = 2,     /* C(f32) = v + bias? + resid(f32, ldc) ; C2(bf16 copy) optional */
-    UNIIR_EPI_DACT = 3,          /* C(bf16) = v * act'(aux[m][n]) (aux bf16, ldaux); C2(bf16, ldaux) = act(aux) opt. */
-    UNIIR_EPI_F32 = 4,           /* C(f32) = v  (beta = 0)                                        */
-    UNIIR_EPI_ATOMIC_F32 = 5,    /* C(f32) += v via atomics; enables split-K (wgrad accumulate)  */
+    UNIIR_EPI_DACT = 3,          /* C(bf16) = (v + bias?) * act'(aux[m][n]) (aux bf16, ldaux); C2(bf16, ldaux) = act(aux) opt. */
+    UNIIR_EPI_F32 = 4,           /* C(f32) = v + bias?  (beta = 0)                                */
+    UNIIR_EPI_ATOMIC_F32 = 5,    /* C(f32) += v via atomics; enables split-K (wgrad accumulate); bias must be NULL
+                                    (UNIIR_EUNSUPPORTED otherwise)                                  */
     UNIIR_EPI_ACT_ONLY = 6       /* C(bf16) = act(bf16(v + bias)): BIAS_ACT without the pre-activation output (forward-only
                                     passes: embedding extraction); same rounding as BIAS_ACT's second output */
 };
@@ -84,12 +86,13 @@ typedef struct {
     void* splitk_ws;          /* optional scratch for split-K: when it holds k_splits*M*N floats the splits write */
     int64_t splitk_ws_bytes;  /* plain fp32 slabs that one reduce kernel adds into C (no atomics)               */
     float* colsum;            /* optional [N] fp32: += column sums of the result before rounding (bias gradient);
-                                 honoured by the 256x256 kernel with EPI_RESID_F32 / EPI_DACT / EPI_F32 only     */
+                                 EPI_RESID_F32 / EPI_DACT / EPI_F32 on the 256x256 kernel; EPI_DACT on the general
+                                 kernel sums the rounded bf16 result in a separate pass (needs ldc % 8 == 0)     */
     const float* row_scale;   /* optional [M] fp32, EPI_RESID_F32 only: C = (v + bias) * row_scale[m] + resid -- DropPath /
                                  stochastic depth of a residual branch (BLIP ViT, backbone/vit.py:79-80) without a separate pass */
     float* a_rowsum;          /* optional [M] fp32, a_tmaj only: += sum over K of op(A)'s rows -- the bias gradient of a
                                  weight-gradient GEMM dW = dy^T x, taken from the dy fragments inside the 256x256 transposed
-                                 kernel (bf16, b_tmaj) and by a separate pass over A otherwise                              */
+                                 kernel (bf16, b_tmaj) and by a separate pass over A otherwise; not scaled by alpha       */
 } uniir_gemm_desc;
 
 int uniir_gemm(const uniir_gemm_desc* d, void* stream);

@@ -189,3 +189,67 @@ def test_tower_workspace_query_sees_the_pooled_last_block_flag():
             assert base > 0 and pooled - base == sum(al(x) for x in fwd + (bwd if save else [])), (image, save, pooled - base)
         t.stash_act, t.pool_last_block = 1, 1            # the two layout flags are independent
         assert lib.uniir_clip_tower_workspace_bytes(ctypes.byref(t), M, 1) > pooled
+
+
+# uniir_gemm's descriptor validation (csrc/gemm.hip gemm_impl) runs before the library touches the HIP runtime: every malformed
+# descriptor below is rejected here, on a machine without a GPU, with its own code.  The addresses are never dereferenced.
+_OK_GEMM = dict(A=0x10000, B=0x20000, C=0x30000, M=256, N=128, K=128, lda=128, ldb=128, ldc=128, epilogue=0, k_splits=1, alpha=1.0)
+_GEMM_REJECTS = [
+    # (what, changes, expected code name)
+    ("null A", dict(A=None), "EINVAL"),
+    ("null B", dict(B=None), "EINVAL"),
+    ("null C", dict(C=None), "EINVAL"),
+    ("M = 0", dict(M=0), "EINVAL"),
+    ("N < 0", dict(N=-8), "EINVAL"),
+    ("K = 0", dict(K=0), "EINVAL"),
+    ("k_splits = 0", dict(k_splits=0), "EINVAL"),
+    ("bad epilogue", dict(epilogue=7), "EINVAL"),
+    ("split-K without ATOMIC_F32", dict(k_splits=2, epilogue=4), "EINVAL"),
+    ("ACT_ONLY with C2", dict(epilogue=6, C2=0x40000), "EINVAL"),
+    ("row_scale with F32", dict(epilogue=4, row_scale=0x50000), "EINVAL"),
+    ("row_scale with BF16", dict(row_scale=0x50000), "EINVAL"),
+    ("BIAS_ACT without C2", dict(epilogue=1), "EINVAL"),
+    ("DACT without aux", dict(epilogue=3, ldaux=128), "EINVAL"),
+    ("colsum with BF16", dict(colsum=0x60000), "EUNSUPPORTED"),
+    ("colsum with BIAS_ACT", dict(epilogue=1, C2=0x40000, colsum=0x60000), "EUNSUPPORTED"),
+    ("colsum with ATOMIC_F32", dict(epilogue=5, colsum=0x60000), "EUNSUPPORTED"),
+    ("colsum with ACT_ONLY", dict(epilogue=6, colsum=0x60000), "EUNSUPPORTED"),
+    ("fp16 DACT", dict(dtype=1, epilogue=3, aux=0x70000, ldaux=128), "EUNSUPPORTED"),
+    ("fp16 RESID_F32 with C2", dict(dtype=1, epilogue=2, C2=0x40000), "EUNSUPPORTED"),
+    ("N % 8", dict(N=132, ldc=132), "ESHAPE"),
+    ("K % 8, K-major A", dict(K=100, b_tmaj=1, ldb=128), "ESHAPE"),
+    ("K % 8, K-major B", dict(K=100, a_tmaj=1, lda=256), "ESHAPE"),
+    ("M % 8, T-major A", dict(M=252, a_tmaj=1, b_tmaj=1, lda=256, K=100), "ESHAPE"),
+    ("lda % 8", dict(lda=132), "EALIGN"),
+    ("ldb % 8", dict(ldb=132), "EALIGN"),
+    ("ldc % 4", dict(ldc=130), "EALIGN"),
+    ("A not 16-B aligned", dict(A=0x10008), "EALIGN"),
+    ("B not 16-B aligned", dict(B=0x20008), "EALIGN"),
+    ("C not 16-B aligned", dict(C=0x30004), "EALIGN"),
+    ("aux not 8-B aligned", dict(epilogue=3, aux=0x70004, ldaux=128), "EALIGN"),
+    ("ldaux % 4", dict(epilogue=3, aux=0x70000, ldaux=130), "EALIGN"),
+    ("bias not 16-B aligned", dict(bias=0x80008), "EALIGN"),
+    ("a_rowsum without a_tmaj", dict(epilogue=5, a_rowsum=0x90000), "EUNSUPPORTED"),
+    ("a_rowsum with fp16", dict(epilogue=5, a_tmaj=1, b_tmaj=1, lda=256, ldb=128, dtype=1, a_rowsum=0x90000), "EUNSUPPORTED"),
+    ("bad dtype", dict(dtype=2), "EINVAL"),
+    # bias with ATOMIC_F32: one meaning on every path or none -- rejected, whatever path the shape would take
+    ("bias with ATOMIC_F32, 128-tile shape", dict(epilogue=5, bias=0x80000, K=72), "EUNSUPPORTED"),
+    ("bias with ATOMIC_F32, 256-tile shape", dict(epilogue=5, bias=0x80000, K=192), "EUNSUPPORTED"),
+    ("bias with ATOMIC_F32, split-K", dict(epilogue=5, bias=0x80000, K=1024, k_splits=4), "EUNSUPPORTED"),
+    ("bias with ATOMIC_F32, head + tail", dict(epilogue=5, bias=0x80000, a_tmaj=1, b_tmaj=1, lda=256, K=1100), "EUNSUPPORTED"),
+]
+
+
+def test_gemm_rejects_malformed_descriptors_before_touching_the_device():
+    from uniir_amd import _lib
+    lib = _lib.load()
+    codes = {"EINVAL": -1, "ESHAPE": -2, "EALIGN": -3, "EUNSUPPORTED": -5}
+    assert lib.uniir_gemm(None, None) == codes["EINVAL"]
+    got = []
+    for what, changes, want in _GEMM_REJECTS:
+        d = _lib.GemmDesc()
+        for k, v in {**_OK_GEMM, **changes}.items():
+            setattr(d, k, v)
+        got.append((what, lib.uniir_gemm(ctypes.byref(d), None), codes[want]))
+    wrong = [g for g in got if g[1] != g[2]]
+    assert not wrong, wrong

@@ -423,6 +423,15 @@ def test_pooled_last_block_equals_the_full_last_block(pack_text):
     rows do: below 256 rows uniir_gemm sums a bias gradient from the ROUNDED bf16 result in a separate pass instead of from the fp32
     accumulators in the epilogue -- a 3e-3 difference between kernel classes that has nothing to do with the pooling (the bench's
     1024 items are far above it)."""
+    g_p, g_f = _pooled_and_full(pack_text, 256)
+    for n in g_f:
+        den = g_f[n].norm().clamp_min(1e-20)
+        assert float((g_p[n] - g_f[n]).norm() / den) < 1e-5, (n, float((g_p[n] - g_f[n]).norm() / den))
+
+
+def _pooled_and_full(pack_text, items):
+    """runs the pooled and the full last block on one batch of `items` items, asserts that embeddings and loss are bitwise equal
+    and returns both runs' parameter gradients"""
     from oracle import clip_oracle as O
     cfg = O.tiny_config(vision_width=128, vision_layers=3, transformer_width=128, transformer_heads=2, transformer_layers=3)
     res = {}
@@ -430,11 +439,17 @@ def test_pooled_last_block_equals_the_full_last_block(pack_text):
         model, _, O = _build(cfg, seed=5)
         clip = model.clip_model
         clip.pack_text, clip.pool_last_block = pack_text, pooled
-        batch = O.synthetic_batch(cfg, 128, seed=33)
+        batch = O.synthetic_batch(cfg, (items + 1) // 2, seed=33)
+        if items % 2:          # an odd item count: drop the last item, pair queries with any remaining item
+            for k in ("txt_batched", "image_batched", "txt_mask_batched", "image_mask_batched"):
+                batch[k] = batch[k][:items].contiguous()
+            q = list(range(0, items, 2))
+            batch["index_mapping"] = {"query": [[i] for i in q], "pos_cand": [[(i + 1) % items] for i in q]}
         txt = batch["txt_batched"]
         ctx = txt.shape[1]
-        txt[3] = torch.randint(1, cfg["vocab_size"] - 2, (ctx,), dtype=torch.int32, generator=torch.Generator().manual_seed(7))
-        txt[3, 0], txt[3, ctx - 1] = cfg["vocab_size"] - 2, cfg["vocab_size"] - 1          # a caption that fills the context
+        full = min(3, items - 1)
+        txt[full] = torch.randint(1, cfg["vocab_size"] - 2, (ctx,), dtype=torch.int32, generator=torch.Generator().manual_seed(7))
+        txt[full, 0], txt[full, ctx - 1] = cfg["vocab_size"] - 2, cfg["vocab_size"] - 1          # a caption that fills the context
         dbatch = {k: (v.cuda() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
         model.train()
         clip._ensure_flat()
@@ -451,11 +466,25 @@ def test_pooled_last_block_equals_the_full_last_block(pack_text):
         res[pooled] = (temb.detach().clone(), iemb.detach().clone(), temb_ng, iemb_ng, temb_h, iemb_h, float(out["loss"].detach()), grads)
     p, f = res[True], res[False]
     for k, name in enumerate(("text", "image", "text no-grad", "image no-grad", "text fp16", "image fp16")):
-        assert torch.equal(p[k], f[k]), (name, float((p[k] - f[k]).abs().max()))
+        assert torch.equal(p[k], f[k]), (items, name, float((p[k] - f[k]).abs().max()))
     assert torch.equal(p[0], p[2]) and torch.equal(p[1], p[3])
-    assert p[6] == f[6]
+    assert p[6] == f[6], (items, p[6], f[6])
     g_p, g_f = p[7], f[7]
     assert set(g_p) == set(g_f)
+    return g_p, g_f
+
+
+@pytest.mark.parametrize("items", [1, 3, 130])
+@pytest.mark.parametrize("pack_text", [True, False])
+def test_pooled_last_block_at_small_batches(pack_text, items):
+    """the comparison above with fewer than 256 pooled rows: the pooled weight gradients run with K = items (1 and 3: the general
+    128-tile kernel; 130: a reduction that is not a multiple of 64).  Embeddings and loss bitwise equal; weight gradients to the
+    same 1e-5.  Linear-layer bias gradients: below 256 rows a layer's bias gradient is summed from its ROUNDED bf16 result by a
+    separate pass in one form and from the fp32 accumulators in the other, and every term of a bf16 sum carries a relative
+    rounding error of at most 2^-8 -- held to 2^-7 of the norm (LayerNorm parameters are summed in fp32 by both: 1e-5)."""
+    g_p, g_f = _pooled_and_full(pack_text, items)
     for n in g_f:
         den = g_f[n].norm().clamp_min(1e-20)
-        assert float((g_p[n] - g_f[n]).norm() / den) < 1e-5, (n, float((g_p[n] - g_f[n]).norm() / den))
+        err = float((g_p[n] - g_f[n]).norm() / den)
+        linear_bias = n.endswith("bias") and "ln_" not in n
+        assert err < (2.0 ** -7 if linear_bias else 1e-5), (items, n, err)

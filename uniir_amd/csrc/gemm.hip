@@ -1079,6 +1079,8 @@ static int gemm_impl(const uniir_gemm_desc* d, void* stream) {
     if (((uintptr_t)d->A & 15) || ((uintptr_t)d->B & 15) || ((uintptr_t)d->C & 15)) return UNIIR_EALIGN;
     if (d->aux && ((d->ldaux % 4) || ((uintptr_t)d->aux & 7))) return UNIIR_EALIGN;
     if (d->bias && ((uintptr_t)d->bias & 15)) return UNIIR_EALIGN;
+    // a bias has no single meaning for an accumulating product that may run as several splits, slabs or a head and a tail
+    if (d->bias && d->epilogue == UNIIR_EPI_ATOMIC_F32) return UNIIR_EUNSUPPORTED;
     // A weight gradient (C += A^T B, both operands K-major) whose reduction length is not a multiple of the 64-row K step -- the
     // packed text tower: K = the live rows of the batch -- would fall to the general 128-tile kernel for the WHOLE product (measured,
     // round 4: 188 us instead of ~45 us per text-tower weight gradient, 9 ms per train step).  The last K % 64 rows are a second,
@@ -1144,12 +1146,7 @@ static int gemm_impl(const uniir_gemm_desc* d, void* stream) {
     if (d->a_rowsum) {
         if (!d->a_tmaj || d->dtype != UNIIR_DT_BF16) return UNIIR_EUNSUPPORTED;     // (the separate pass reads bf16 too)
         rowsum_fused = d->dtype == UNIIR_DT_BF16 && d->b_tmaj && pp_eligible(a, d->a_tmaj, d->b_tmaj);
-        if (rowsum_fused) {
-            a.a_rowsum = d->a_rowsum;
-            // one partial per (split, column panel) block, reduced in block order below (atomics in arrival order without a scratch)
-            // (the 256 x 256 kernel's own panel counts: launch_glds_rowsum)
-            a.rowsum_part = reduce_scratch(st, (int64_t)a.k_splits * ((d->N + 255) / 256) * d->M * 4);
-        }
+        if (rowsum_fused) a.a_rowsum = d->a_rowsum;
     }
     int rc;
     // colsum and the DACT epilogue's second output act(aux) exist in the LDS-staged epilogue of the 256-tile kernel only; when the
@@ -1160,6 +1157,7 @@ static int gemm_impl(const uniir_gemm_desc* d, void* stream) {
     if (!staged) {
         if (d->colsum) {
             if (d->epilogue != UNIIR_EPI_DACT) return UNIIR_EUNSUPPORTED;      // fp32 outputs: no separate column-sum pass exists
+            if (d->ldc % 8) return UNIIR_EUNSUPPORTED;         // the pass reads 16-B row pieces: rejected before anything runs
             a.colsum = nullptr;
             colsum_after = true;
         }
@@ -1170,8 +1168,19 @@ static int gemm_impl(const uniir_gemm_desc* d, void* stream) {
             a.C2 = nullptr;
         }
     }
-    if (staged && a.colsum && (d->N % 4 == 0))       // the 256-row panels' column partials, reduced in panel order below
-        a.colsum_part = reduce_scratch(st, (int64_t)((d->M + 255) / 256) * d->N * 4);
+    // deterministic partials out of ONE request of the stream's scratch: the 256-row panels' column partials at its start, one row
+    // partial per (split, column panel) block of the fused row sums (the 256 x 256 kernel's own panel counts: launch_glds_rowsum) at
+    // the next 256-B boundary; both reduced in order below.  When the two together do not fit, both keep their atomics.
+    {
+        const int64_t cbytes = (staged && a.colsum && (d->N % 4 == 0)) ? (int64_t)((d->M + 255) / 256) * d->N * 4 : 0;
+        const int64_t rbytes = rowsum_fused ? (int64_t)a.k_splits * ((d->N + 255) / 256) * d->M * 4 : 0;
+        const int64_t roff = (cbytes + 255) / 256 * 256;
+        if (cbytes || rbytes) {
+            float* part = reduce_scratch(st, roff + rbytes);
+            if (part && cbytes) a.colsum_part = part;
+            if (part && rbytes) a.rowsum_part = (float*)((char*)part + roff);
+        }
+    }
     if (d->dtype == UNIIR_DT_BF16) rc = launch_gemm<ElemBF16>(a, d->a_tmaj, d->b_tmaj, st);
 #ifndef UNIIR_EXP_BUILD
     else if (d->dtype == UNIIR_DT_F16) rc = launch_gemm<ElemF16>(a, d->a_tmaj, d->b_tmaj, st);
