@@ -17,6 +17,7 @@ stash.  Differences from the reference, stated once:
     used un-normalised and a host coin flip decides what is enqueued.
 """
 import json
+import logging
 
 import torch
 from torch import nn
@@ -99,10 +100,23 @@ def _attach(root, dotted, param):
 # ------------------------------------------------------------------------------------------------------------
 # launch sequences
 # ------------------------------------------------------------------------------------------------------------
-def vit_forward(st, conv16, prefix, cfg, img_size, images, save, drop=None):
+def vit_recompute_from(depth, vit_grad_ckpt, vit_ckpt_layer):
+    """the first ViT block whose intermediates are recomputed in the backward, from the reference's two configuration keys: it
+    checkpoints the blocks i >= depth - ckpt_layer when use_grad_checkpointing is set (backbone/vit.py:230), so vit_ckpt_layer: 0
+    with the flag on recomputes nothing, like there.  Returns depth (nothing recomputed) without the flag.
+    The reference checkpoints a block's attention and MLP branches separately (two checkpoints per block, each keeping its input);
+    here the unit is the whole block, which keeps less: the fp32 block input alone (resblocks.tower_fwd's recompute_from)."""
+    if not vit_grad_ckpt:
+        return depth
+    return depth - min(max(int(vit_ckpt_layer), 0), depth)
+
+
+def vit_forward(st, conv16, prefix, cfg, img_size, images, save, drop=None, recompute_from=None):
     """src/models/uniir_blip/backbone/vit.py:196-221 -> bf16 tokens [M*T, D] (after the final norm) + stash.
     drop (ops.DropSeeds, train mode): DropPath with rates linspace(0, drop_path_rate, depth) (vit.py:167), one Bernoulli
-    draw per item and residual branch from torch's CPU generator"""
+    draw per item and residual branch from torch's CPU generator.
+    recompute_from: blocks from this one on keep only their input and are rebuilt in vit_backward (vit_recompute_from); the
+    stash carries what each block kept, so vit_backward needs no argument for it"""
     D, P, depth = cfg["embed_dim"], cfg["patch_size"], cfg["depth"]
     M, dev = images.shape[0], images.device
     G = (img_size // P) ** 2
@@ -120,9 +134,9 @@ def vit_forward(st, conv16, prefix, cfg, img_size, images, save, drop=None):
         keep = 1.0 - torch.linspace(0, cfg["drop_path_rate"], depth).view(depth, 1, 1)
         rowscale = (torch.floor(keep + torch.rand(depth, 2, M)) / keep).to(dev)
     x, saved = tower_fwd(st, lambda i: _vit_blk_names(prefix, i), depth, x0, M, T, D, heads, False, save, eps=VIT_EPS,
-                         act=ops.ACT_GELU_ERF, rowscale=rowscale)
+                         act=ops.ACT_GELU_ERF, rowscale=rowscale, recompute_from=recompute_from)
     tok = ops.layernorm_fwd(x, st.p(prefix + "norm.weight"), st.p(prefix + "norm.bias"), VIT_EPS, rows=M * T, width=D)
-    stash = dict(patches=patches, x=x, saved=saved, M=M, T=T, rowscale=rowscale) if save else None
+    stash = dict(patches=patches, x=x, saved=saved, M=M, T=T, rowscale=rowscale, recompute_from=recompute_from) if save else None
     return tok, T, stash
 
 
@@ -423,7 +437,7 @@ class _EncodeFn(torch.autograd.Function):
         st = model._online
         drop = model._drop_seeds()
         tok, Ti, vst = vit_forward(st, model._conv16, "visual_encoder.", model.vit_cfg, model.image_size, images, save,
-                                   drop=drop)
+                                   drop=drop, recompute_from=model._vit_boundary(save))
         pooled, bst = bert_forward(st, "text_encoder.", model.med_cfg, ids, key_len, tok, Ti, save, drop=drop, pack=pack)
         ctx.model, ctx.vst, ctx.bst = model, vst, bst
         return pooled
@@ -598,6 +612,23 @@ class BLIPFeatureFusion(nn.Module):
         # the bench's caption lengths.  False = the padded rows of the reference, all L positions (A/B, tests)
         self.pack_text = True
         self.last_text_rows = None        # (rows BERT ran on, M * L) of the last encode call (bench: executed FLOPs)
+        # vit_grad_ckpt / vit_ckpt_layer (the reference's keys, large YAMLs: True / 12): the online ViT's blocks from this index on
+        # keep only their fp32 input in a training forward and are rebuilt in the backward (vit_recompute_from); depth = every block
+        # stored.  Bitwise the stored step's results, for one more pass over those blocks' sublayers.  A plain attribute: may be
+        # changed between steps (A/B runs); must be the same on every rank.
+        self.vit_recompute_from = vit_recompute_from(self.vit_cfg["depth"], vit_grad_ckpt, vit_ckpt_layer)
+        self._vit_recompute_logged = False
+
+    def _vit_boundary(self, save):
+        """recompute_from of a ViT forward of the online encoder; the first training forward that recomputes says so once"""
+        depth, k = self.vit_cfg["depth"], self.vit_recompute_from
+        if save and k < depth and not self._vit_recompute_logged:
+            self._vit_recompute_logged = True
+            logging.getLogger(__name__).info(
+                "BLIP ViT: blocks %d..%d of %d are recomputed in the backward (vit_grad_ckpt / vit_ckpt_layer): only their inputs "
+                "are kept; results are bitwise those of the stored step. vit_grad_ckpt: False keeps the whole stash.",
+                max(k, 0), depth - 1, depth)
+        return k
 
     # ---- reference surface ---------------------------------------------------------------------------------
     def get_img_preprocess_fn(self):
@@ -862,7 +893,8 @@ class BLIPScoreFusion(BLIPFeatureFusion):
         M = ids.shape[0]
         E = self.embed_dim
         drop = self._drop_seeds()
-        tok, T, vst = vit_forward(st, conv16, "visual_encoder.", self.vit_cfg, self.image_size, images, save, drop=drop)
+        tok, T, vst = vit_forward(st, conv16, "visual_encoder.", self.vit_cfg, self.image_size, images, save, drop=drop,
+                                  recompute_from=self._vit_boundary(save))
         ifeat16 = tok.view(M, T, -1)[:, 0].contiguous()                     # class-token rows (a copy)
         tfeat, bst = bert_forward(st, "text_encoder.", self.med_cfg, ids, key_len, None, 0, save, cross=False, pool=False,
                                   drop=drop, pack=pack)

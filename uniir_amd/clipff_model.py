@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import ops
-from .resblocks import clip_block_names, tower_bwd, tower_fwd
+from .resblocks import block_set_bytes, clip_block_names, tower_bwd, tower_fwd
 
 T5_EPS = 1e-6
 T5_DROPOUT = 0.1      # transformers T5Config default dropout_rate (clip_ff.py:82,90 build T5Config() without overriding it)
@@ -179,6 +179,20 @@ def t5_backward(st, prefix, dpooled, stash, heads, layers):
 # ------------------------------------------------------------------------------------------------------------
 # towers without pooling
 # ------------------------------------------------------------------------------------------------------------
+def _recompute_from(model, which, save, M, R, W, heads, L):
+    """recompute_from of a tower without pooling: CLIP.recompute_blocks recomputes every block, the meaning the switch has for the C
+    towers (the act(f) stash decisions of those do not exist here).  Logged once per tower in CLIP.stash_log."""
+    if not (save and model.recompute_blocks):
+        return None
+    if which not in model._recompute_logged:
+        model._recompute_logged.add(which)
+        n = block_set_bytes(R, W, heads)
+        model.stash_log.append(f"{which} tower without pooling, {M} items: block recomputation ON (recompute_blocks): block inputs only "
+                               f"({L} x {4 * R * W} bytes) and one shared set of {n} bytes ({n / 2**30:.1f} GiB) that every block is "
+                               f"rebuilt into; act(f) stash not applicable")
+    return 0
+
+
 def vision_tokens_fwd(model, image, save):
     """clip_ff.py:35-59 -> fp32 [M*T, E] = ln_post(all tokens) @ proj"""
     cfg, st = model.cfg, model._flat
@@ -197,7 +211,8 @@ def vision_tokens_fwd(model, image, save):
     del po
     x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
     ops.layernorm_fwd(x0, p32("visual.ln_pre.weight"), p32("visual.ln_pre.bias"), out_f32=x, rows=M * T, width=W)
-    x, saved = tower_fwd(st, lambda i: clip_block_names("visual.transformer", i), L, x, M, T, W, heads, False, save)
+    x, saved = tower_fwd(st, lambda i: clip_block_names("visual.transformer", i), L, x, M, T, W, heads, False, save,
+                         recompute_from=_recompute_from(model, "image", save, M, M * T, W, heads, L))
     ln = ops.layernorm_fwd(x, p32("visual.ln_post.weight"), p32("visual.ln_post.bias"), rows=M * T, width=W)
     tok = torch.empty(M * T, E, device=dev, dtype=torch.float32)
     ops.gemm(ln, st.w16("visual.proj"), tok, M * T, E, W, W, E, E, b_tmaj=True, epilogue=ops.EPI_F32)
@@ -244,7 +259,8 @@ def text_tokens_fwd(model, text, save):
     eot = torch.empty(M, device=dev, dtype=torch.int32)
     ops.call("uniir_text_embed", text, p32("token_embedding.weight"), p32("positional_embedding"), x, eot, M, T, W,
              cfg["vocab_size"])
-    x, saved = tower_fwd(st, lambda i: clip_block_names("transformer", i), L, x, M, T, W, heads, True, save)
+    x, saved = tower_fwd(st, lambda i: clip_block_names("transformer", i), L, x, M, T, W, heads, True, save,
+                         recompute_from=_recompute_from(model, "text", save, M, M * T, W, heads, L))
     tok = torch.empty(M * T, W, device=dev, dtype=torch.float32)
     ops.layernorm_fwd(x, p32("ln_final.weight"), p32("ln_final.bias"), out_f32=tok, rows=M * T, width=W)
     stash = dict(text=text, saved=saved, xf=x, M=M, T=T) if save else None
