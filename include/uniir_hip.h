@@ -137,7 +137,12 @@ int uniir_layernorm_bwd_ex(const float* x, int64_t x_stride, const float* gamma,
                            int32_t rows, int32_t width, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * [ENC] building block 3: fused multi-head attention, head_dim 64, seq <= 512.
+ * [ENC] building block 3: fused multi-head attention, head_dim 64.
+ * Sequence limits per entry point (anything beyond is UNIIR_ESHAPE):
+ *   uniir_attention_fwd / _bwd with causal = 0 : seq <= 1024 (513 .. 1024: K / V or Q / dO streamed through LDS; the backward stays
+ *                                                bitwise reproducible); the uniir_clip_tower vision towers use this form
+ *   uniir_attention_fwd / _bwd with causal = 1 : seq <= 512
+ *   _packed, _ex, _rows, _rel_fwd / _rel_bwd   : seq, tq, tk <= 512 (mask, key_len, dropout, packed rows, relative bias)
  * qkv bf16 [batch*seq][3*heads*64] as produced by nn.MultiheadAttention.in_proj ([q | k | v] per row);
  * out bf16 [batch*seq][heads*64]; lse f32 [batch][heads][seq] (natural log-sum-exp of scaled scores).
  * causal = 1 applies CLIP's build_attention_mask (key <= query).

@@ -1,0 +1,54 @@
+"""Time of one CLIP_SF training step with ViT-L/14@336px (577 image tokens; dev tool, random weights, synthetic batch).
+PAIRS (default 128) query / candidate pairs, STEPS (default 5) timed steps after WARMUP (default 2); RECOMPUTE=1 switches block
+recomputation on.  Prints the median step time, the peak memory and the towers' stash decisions."""
+import os
+import sys
+from types import SimpleNamespace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "uniir_amd", "src"))
+import torch
+from uniir_amd import clip_model
+from uniir_amd.trainer import NativeTrainer
+from models.uniir_clip.clip_scorefusion.clip_sf import CLIPScoreFusion
+
+
+def main():
+    name = os.environ.get("MODEL", "ViT-L/14@336px")
+    pairs, steps, warm = int(os.environ.get("PAIRS", "128")), int(os.environ.get("STEPS", "5")), int(os.environ.get("WARMUP", "2"))
+    cfg = clip_model.CLIP_CONFIGS[name]
+    config = SimpleNamespace(model=SimpleNamespace(gather_embeddings=False), data_config=SimpleNamespace(in_batch_neg_num=0))
+    model = CLIPScoreFusion(name, device="cuda", config=config)
+    model.clip_model.recompute_blocks = os.environ.get("RECOMPUTE", "0") == "1"
+    g = torch.Generator(device="cuda").manual_seed(0)
+    M, res, ctx, vocab = 2 * pairs, cfg["image_resolution"], cfg["context_length"], cfg["vocab_size"]
+    txt = torch.zeros(M, ctx, dtype=torch.int32, device="cuda")
+    for i in range(M):
+        n = 5 + i % 50
+        txt[i, 0] = vocab - 2
+        txt[i, 1:1 + n] = torch.randint(1, vocab - 2, (n,), device="cuda", generator=g, dtype=torch.int32)
+        txt[i, 1 + n] = vocab - 1
+    batch = {"txt_batched": txt, "image_batched": torch.randn(M, 3, res, res, device="cuda", generator=g),
+             "txt_mask_batched": torch.ones(M, device="cuda"), "image_mask_batched": torch.ones(M, device="cuda"),
+             "index_mapping": {"query": [[2 * i] for i in range(pairs)], "pos_cand": [[2 * i + 1] for i in range(pairs)]}}
+    tr = NativeTrainer(model, lr=1e-5, t_total=1000)
+    times = []
+    for it in range(warm + steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = tr.train_step(batch)
+        e1.record()
+        torch.cuda.synchronize()
+        if it >= warm:
+            times.append(e0.elapsed_time(e1))
+    times.sort()
+    print(f"CLIP_SF {name} train step: {pairs} pairs, recompute_blocks={int(model.clip_model.recompute_blocks)}: median {times[len(times) // 2]:.1f} ms "
+          f"(min {times[0]:.1f}, max {times[-1]:.1f}, {steps} steps after {warm}), loss {float(out['loss'].detach()):.4f}, "
+          f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
+    for line in model.clip_model.stash_log:
+        print("  " + line)
+
+
+if __name__ == "__main__":
+    main()

@@ -129,7 +129,8 @@ def load(name="ViT-B/32", device="cuda", jit=False, download_root=None, seed=0):
         raise RuntimeError(f"Model {name} not found; available models = {list(CLIP_CONFIGS)}")
     model = CLIP(CLIP_CONFIGS[name], seed=seed)
     if download_root:
-        path = os.path.join(os.path.expanduser(download_root), name.replace("/", "-") + ".pt")
+        # the published file names: ViT-B-32.pt, ViT-L-14.pt, ViT-L-14-336px.pt
+        path = os.path.join(os.path.expanduser(download_root), name.replace("/", "-").replace("@", "-") + ".pt")
         if os.path.exists(path):
             try:            # the published files are TorchScript archives (upstream clip.load falls back the other way)
                 sd = torch.jit.load(path, map_location="cpu").state_dict()

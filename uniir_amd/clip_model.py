@@ -73,6 +73,10 @@ CLIP_CONFIGS = {
     "ViT-L/14": dict(embed_dim=768, image_resolution=224, vision_layers=24, vision_width=1024, vision_patch_size=14,
                      context_length=77, vocab_size=49408, transformer_width=768, transformer_heads=12,
                      transformer_layers=12),
+    # ViT-L/14 at 336 pixels: 24 x 24 + 1 = 577 tokens (the vision tower's attention streams K / V, csrc/attention_long.hip)
+    "ViT-L/14@336px": dict(embed_dim=768, image_resolution=336, vision_layers=24, vision_width=1024, vision_patch_size=14,
+                           context_length=77, vocab_size=49408, transformer_width=768, transformer_heads=12,
+                           transformer_layers=12),
 }
 
 
@@ -172,6 +176,7 @@ class CLIP(nn.Module):
         # whose stash does not fit.  UNIIR_RECOMPUTE_BLOCKS=1 switches it on at construction; must be the same on every rank.
         self.recompute_blocks = os.environ.get("UNIIR_RECOMPUTE_BLOCKS", "0") not in ("", "0")
         self._recompute_logged = set()    # towers whose "recomputation is on" line is in stash_log already
+        self._full_last_logged = set()    # towers whose "full last block" line is in stash_log already
         self.stash_margin_bytes = 16 << 30
         self.stash_review_headroom_bytes = 6 << 30
         self._stash_choice = {}           # tower -> bool: the automatic decision, made once (at the first training batch)
@@ -570,6 +575,11 @@ class _TowerFn(torch.autograd.Function):
         lib = _lib.load()
         desc = model.tower_desc(which, half=half)
         desc.pool_last_block = int(bool(model.pool_last_block))
+        if desc.pool_last_block and desc.tokens > 512 and which not in model._full_last_logged:
+            # (csrc/tower.hip plan(): the one-query attention of the pooled block holds all keys in LDS, 512 at the most)
+            model._full_last_logged.add(which)
+            model.stash_log.append(f"{which} tower, {desc.tokens} tokens: full last block (pool_last_block needs <= 512 tokens); "
+                                   f"same embeddings, 1/{desc.layers} more block work")
         # recompute_blocks: only the block inputs are kept (uniir_clip_tower.recompute); a forward-only call has no stash to shrink
         recompute = need_grad and bool(model.recompute_blocks)
         desc.recompute = int(recompute)

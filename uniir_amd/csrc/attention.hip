@@ -1,4 +1,5 @@
-// Fused multi-head attention forward / backward for the CLIP towers (head_dim 64; seq 257 / 77 / 50).
+// Fused multi-head attention forward / backward for the CLIP towers (head_dim 64; seq 257 / 77 / 50; up to 512 tokens here,
+// 513 .. 1024 tokens of plain self-attention in attention_long.hip).
 // Replaces nn.MultiheadAttention's softmax(QK^T/sqrt(64) [+ causal mask])V inside openai/CLIP
 // ResidualAttentionBlock.attention (model.py), reached from clip_sf.py:43-47.
 //
@@ -537,6 +538,11 @@ static int launch_attn_bwd_nt(const AttnArgs& a, int batch, int sm, hipStream_t 
     return UNIIR_OK;
 }
 int launch_attn_bwd_pair(const AttnArgs& a, int batch, hipStream_t st);      // attention_pair.hip; 1 = shape not taken
+// attention_long.hip: plain dense self-attention of 513 .. 1024 tokens (one operand streamed through LDS); everything else is UNIIR_ESHAPE
+int launch_attn_long_fwd(const AttnArgs& a, int batch, hipStream_t st, bool f16);
+int launch_attn_long_bwd(const AttnArgs& a, int batch, hipStream_t st);
+#define ATT_SEQ_MAX 512           // a head's K / V (Q / dO) whole in LDS: every kernel of this file and of attention_pair.hip
+#define ATT_LONG_SEQ_MAX 1024     // the streaming kernels
 static int launch_attn_bwd(const AttnArgs& a0, int batch, hipStream_t st) {
     AttnArgs a = a0;
 #ifdef UNIIR_EXP_BUILD
@@ -561,7 +567,7 @@ int attention_fwd_impl(const void* qkv, void* out, float* lse, const int32_t* ro
                        int32_t causal, int f16, void* stream) {
     if (!qkv || !out || !lse || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (seq < 1 || seq > 512) return UNIIR_ESHAPE;
+    if (seq < 1 || seq > ((causal || row_off) ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX)) return UNIIR_ESHAPE;
     if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
     const long W = (long)heads * ATT_D;
     AttnArgs a = {};
@@ -569,6 +575,7 @@ int attention_fwd_impl(const void* qkv, void* out, float* lse, const int32_t* ro
     a.q_ld = a.kv_ld = 3 * W;
     a.out = (unsigned short*)out; a.out_ld = W; a.lse = lse; a.klen = nullptr; a.row_off = row_off;
     a.Tq = a.Tk = seq; a.H = heads; a.causal = causal; a.scale = ATT_SCALE;
+    if (seq > ATT_SEQ_MAX) return launch_attn_long_fwd(a, batch, (hipStream_t)stream, f16 != 0);
     return launch_attn_fwd(a, batch, (hipStream_t)stream, f16 != 0);
 }
 // tower.hip's last block when only one row per item is pooled (the class token / the EOT row): ONE query row per item ([batch][W],
@@ -613,7 +620,7 @@ extern "C" int uniir_attention_fwd(const void* qkv, void* out, float* lse, int32
                                    int32_t heads, int32_t causal, void* stream) {
     if (!qkv || !out || !lse || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (seq < 1 || seq > 512) return UNIIR_ESHAPE;
+    if (seq < 1 || seq > (causal ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX)) return UNIIR_ESHAPE;
     if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
     const long W = (long)heads * ATT_D;
     AttnArgs a = {};
@@ -621,6 +628,7 @@ extern "C" int uniir_attention_fwd(const void* qkv, void* out, float* lse, int32
     a.q_ld = a.kv_ld = 3 * W;
     a.out = (unsigned short*)out; a.out_ld = W; a.lse = lse; a.klen = nullptr;
     a.Tq = a.Tk = seq; a.H = heads; a.causal = causal; a.scale = ATT_SCALE;
+    if (seq > ATT_SEQ_MAX) return launch_attn_long_fwd(a, batch, (hipStream_t)stream, false);
     return launch_attn_fwd(a, batch, (hipStream_t)stream);
 }
 
@@ -629,7 +637,7 @@ extern "C" int uniir_attention_bwd(const void* qkv, const void* out, const void*
                                    void* stream) {
     if (!qkv || !out || !dout || !lse || !dqkv || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (seq < 1 || seq > 512) return UNIIR_ESHAPE;
+    if (seq < 1 || seq > (causal ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX)) return UNIIR_ESHAPE;
     if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)dqkv & 15))
         return UNIIR_EALIGN;
     const long W = (long)heads * ATT_D;
@@ -641,6 +649,7 @@ extern "C" int uniir_attention_bwd(const void* qkv, const void* out, const void*
     a.dout = (const unsigned short*)dout;
     a.dq = (unsigned short*)dqkv; a.dk = a.dq + W; a.dv = a.dq + 2 * W;
     a.dq_ld = a.dkv_ld = 3 * W;
+    if (seq > ATT_SEQ_MAX) return launch_attn_long_bwd(a, batch, (hipStream_t)stream);
     return launch_attn_bwd(a, batch, (hipStream_t)stream);
 }
 

@@ -1,0 +1,441 @@
+// Fused attention for sequences of 513 .. 1024 tokens (head_dim 64): plain self-attention (no causal mask, no bias, no dropout,
+// dense rows), forward in bf16 / fp16 and backward in bf16.  CLIP ViT-L/14@336px: 577 tokens.
+//
+// A head of that length no longer fits LDS whole (attention.hip: 2 * 512 * 128 bytes), so one operand is STREAMED: a workgroup
+// (8 waves) owns 128 rows of one (item, head) -- every wave one 16-row tile for the whole sweep, its accumulators in registers --
+// and the other side passes through LDS in chunks, double-buffered ([row][64] 16-bit, the swizzled image and the fragment
+// helpers of attention.h).  The next chunk is fetched into registers before the current one is computed and written to the
+// other buffer behind it (register staging; one barrier per chunk).
+//   forward : owns 128 queries, streams K / V in 128-key chunks; online softmax with the per-row deferred maximum of attn_fwd_kernel
+//   dK / dV : owns 128 keys, streams Q / dO (and the per-row lse, delta) in query chunks
+//   dQ      : owns 128 queries, streams K / V in key chunks
+// The backward is the two phases of attn_bwd_kernel as two kernels; neither sums across workgroups, nothing is atomic, every sum
+// has a fixed order: the results are bitwise reproducible.  delta = rowsum(dO . O) is recomputed from the O / dO rows (the ABI has no
+// workspace): 8 lanes hold a row's 16-byte pieces, their partial dots meet in a fixed butterfly.
+// A query row's result never depends on the rows that share its tile or its workgroup (the rescale decision is per row).
+#include "attention.h"
+
+#define AL_THREADS 512
+#define AL_WAVES (AL_THREADS / 64)
+#define AL_ROWS (16 * AL_WAVES)      // rows a workgroup owns
+#define AL_KV 128                    // K / V rows per streamed chunk (forward, dQ)
+#define AL_QC 64                     // Q / dO rows per streamed chunk (dK / dV: three operands ride the registers there)
+
+// the 16-byte pieces of rows r0 .. r0 + CH - 1 of a [T][64] head slice: piece c = u * AL_THREADS + tid is row c / 8, columns 8 (c % 8) ..
+// (loads come from clamped, always valid rows; rows >= T are zeroed at the LDS store)
+template <int CH>
+DEVINL void al_load(u32x4_t (&v)[CH * 8 / AL_THREADS], const unsigned short* __restrict__ src, long ld, int r0, int T, int tid) {
+#pragma unroll
+    for (int u = 0; u < CH * 8 / AL_THREADS; ++u) {
+        const int c = u * AL_THREADS + tid;
+        const int row = min(r0 + (c >> 3), T - 1), kc = c & 7;
+        v[u] = ATT_LD(reinterpret_cast<const u32x4_t*>(src + (long)row * ld + kc * 8));
+    }
+}
+template <int CH>
+DEVINL void al_store(char* lds, const u32x4_t (&v)[CH * 8 / AL_THREADS], int r0, int T, int tid) {
+#pragma unroll
+    for (int u = 0; u < CH * 8 / AL_THREADS; ++u) {
+        const int c = u * AL_THREADS + tid;
+        const int row = c >> 3, kc = c & 7;
+        const u32x4_t z = {0u, 0u, 0u, 0u};
+        *reinterpret_cast<u32x4_t*>(lds + row * 128 + ((kc ^ (row & 7)) << 4)) = (r0 + row < T) ? v[u] : z;
+    }
+}
+// delta of the rows whose O / dO pieces the workgroup holds: dl[row] = dO[row] . O[row] (0 for rows >= T).  The 8 lanes of a row are
+// neighbours; the butterfly leaves the same sum in all of them.
+template <int CH>
+DEVINL void al_delta(float* dl, const u32x4_t (&o)[CH * 8 / AL_THREADS], const u32x4_t (&d)[CH * 8 / AL_THREADS], int r0, int T, int tid) {
+#pragma unroll
+    for (int u = 0; u < CH * 8 / AL_THREADS; ++u) {
+        const int c = u * AL_THREADS + tid;
+        const int row = c >> 3, kc = c & 7;
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            s += __uint_as_float(o[u][e] << 16) * __uint_as_float(d[u][e] << 16);
+            s += __uint_as_float(o[u][e] & 0xffff0000u) * __uint_as_float(d[u][e] & 0xffff0000u);
+        }
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        s += __shfl_xor(s, 4);
+        if (kc == 0) dl[row] = (r0 + row < T) ? s : 0.f;
+    }
+}
+
+// ---------------- forward ----------------
+template <bool F16>
+__global__ __launch_bounds__(AL_THREADS) void attn_long_fwd_kernel(AttnArgs a, int nqb) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    constexpr int NL = AL_KV * 8 / AL_THREADS;
+    constexpr int BUF = 2 * AL_KV * 128;      // K chunk, V chunk
+    const int H = a.H, Tq = a.Tq, Tk = a.Tk;
+    const int qb = blockIdx.x % nqb, mh = blockIdx.x / nqb;      // the query blocks of a head are neighbours: K / V stay in L2
+    const int m = mh / H, h = mh % H;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned short* qbase = a.q + (long)m * Tq * a.q_ld + h * ATT_D;
+    const unsigned short* kbase = a.k + (long)m * Tk * a.kv_ld + h * ATT_D;
+    const unsigned short* vbase = a.v + (long)m * Tk * a.kv_ld + h * ATT_D;
+    const int qi = lane & 15, g = lane >> 4;
+    const int q0 = qb * AL_ROWS + w * 16, q = q0 + qi;
+    const bool active = q0 < Tq;          // wave-uniform; an idle wave still stages and meets the barriers
+    const float sl2 = SCALE_LOG2E;
+    bf16x8_t qf[2];
+    qf[0] = frag_rows_global(qbase, a.q_ld, q0, 0, lane, Tq);
+    qf[1] = frag_rows_global(qbase, a.q_ld, q0, 1, lane, Tq);
+    u32x4_t rk[NL], rv[NL];
+    al_load<AL_KV>(rk, kbase, a.kv_ld, 0, Tk, tid);
+    al_load<AL_KV>(rv, vbase, a.kv_ld, 0, Tk, tid);
+    al_store<AL_KV>(lds, rk, 0, Tk, tid);
+    al_store<AL_KV>(lds + AL_KV * 128, rv, 0, Tk, tid);
+    __syncthreads();
+    f32x4_t o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float m_run = -1e30f;
+    f32x4_t l4 = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    const int nch = (Tk + AL_KV - 1) / AL_KV;
+    for (int c = 0; c < nch; ++c) {
+        const char* ldsK = lds + (c & 1) * BUF;
+        const char* ldsV = ldsK + AL_KV * 128;
+        const int k0 = c * AL_KV;
+        if (c + 1 < nch) {
+            al_load<AL_KV>(rk, kbase, a.kv_ld, k0 + AL_KV, Tk, tid);
+            al_load<AL_KV>(rv, vbase, a.kv_ld, k0 + AL_KV, Tk, tid);
+        }
+        if (active) {
+            const int nkb = min(AL_KV / 32, (Tk - k0 + 31) >> 5);      // >= 1
+            // the block structure of attn_fwd_kernel: S^T of a 32-key block one block ahead of its softmax, two logit buffers
+            auto s_block = [&](int kb, f32x4_t (&sx)[2]) {
+#pragma unroll
+                for (int kt = 0; kt < 2; ++kt) {
+                    sx[kt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) sx[kt] = mfma16x<F16>(frag_rows(ldsK, kb * 32 + kt * 16, s, lane), qf[s], sx[kt]);
+                }
+            };
+            auto softmax_pv = [&](int kb, f32x4_t (&st)[2]) {
+                if (k0 + kb * 32 + 32 > Tk) {
+#pragma unroll
+                    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (k0 + kb * 32 + kt * 16 + 4 * g + r >= Tk) st[kt][r] = -1e30f;
+                }
+                // deferred maximum, decided per row (see attn_fwd_kernel): the reference moves when one of the row's own logits
+                // exceeds it by more than ATT_DEFER; alpha is exactly 1 for the rows that keep theirs
+                float mx = -1e30f;
+#pragma unroll
+                for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[kt][r]);
+                const unsigned long long over = __ballot(__builtin_fmaf(mx, sl2, -m_run) > ATT_DEFER);
+                unsigned rows_over = (unsigned)(over | (over >> 32));
+                rows_over = (rows_over | (rows_over >> 16)) & 0xffffu;
+                if (rows_over) {
+                    const float gm = group_max(mx);
+                    const float m_new = ((rows_over >> qi) & 1u) ? fmaxf(m_run, gm * sl2) : m_run;
+                    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+                    l4 = l4 * alpha;
+#pragma unroll
+                    for (int dt = 0; dt < 4; ++dt) o[dt] = o[dt] * alpha;
+                    m_run = m_new;
+                }
+#pragma unroll
+                for (int kt = 0; kt < 2; ++kt) {
+                    const f32x4_t arg = __builtin_elementwise_fma(st[kt], f32x4_t{sl2, sl2, sl2, sl2}, f32x4_t{-m_run, -m_run, -m_run, -m_run});
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) st[kt][r] = __builtin_amdgcn_exp2f(arg[r]);
+                    l4 = l4 + st[kt];
+                }
+                const bf16x8_t pf = pack8x<F16>(st[0], st[1]);
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) o[dt] = mfma16x<F16>(frag_cols_tr(ldsV, kb * 32, dt, lane), pf, o[dt]);
+            };
+            f32x4_t sa[2], sb[2];
+            s_block(0, sa);
+            for (int kb = 0; kb < nkb; kb += 2) {
+                if (kb + 1 < nkb) s_block(kb + 1, sb);
+                softmax_pv(kb, sa);
+                if (kb + 1 >= nkb) break;
+                if (kb + 2 < nkb) s_block(kb + 2, sa);
+                softmax_pv(kb + 1, sb);
+            }
+        }
+        if (c + 1 < nch) {
+            char* nx = lds + ((c + 1) & 1) * BUF;      // last read in iteration c - 1, which every wave has left (barrier below)
+            al_store<AL_KV>(nx, rk, k0 + AL_KV, Tk, tid);
+            al_store<AL_KV>(nx + AL_KV * 128, rv, k0 + AL_KV, Tk, tid);
+        }
+        __syncthreads();
+    }
+    if (active) {
+        const float l_run = group_sum((l4[0] + l4[1]) + (l4[2] + l4[3]));
+        const bool live = q < Tq;
+        att_store_tile<F16>(o, 1.0f / l_run, a.out + ((long)m * Tq + min(q, Tq - 1)) * a.out_ld + h * ATT_D, live, g);
+        if (live && g == 0) a.lse[((long)m * H + h) * Tq + q] = m_run * LN2F + __logf(l_run);
+    }
+}
+
+// the lane parts of the swizzled fragment addresses (attn_bwd_kernel): row fragments of k-step s, transposed fragments of column tile dt
+struct AlOffs {
+    int r[2], t[4];
+};
+DEVINL AlOffs al_offs(int li, int g) {
+    AlOffs x;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) x.r[s] = li * 128 + (((s * 4 + g) ^ (li & 7)) << 4);
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        const int row = 4 * g + (li >> 2), col = 16 * dt + 4 * (li & 3);
+        x.t[dt] = row * 128 + ((((col >> 3) ^ (row & 7)) << 4) | ((col & 7) << 1));
+    }
+    return x;
+}
+DEVINL bf16x8_t al_rows_frag(const char* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(p)); }
+DEVINL bf16x8_t al_cols_frag(const char* p) {      // 32-row block: rows 4g.., 16 + 4g.. of one column tile
+    const u32x2_t l2 = __builtin_bit_cast(u32x2_t, lds_read_tr16(p));
+    const u32x2_t h2 = __builtin_bit_cast(u32x2_t, lds_read_tr16(p + 2048));
+    const u32x4_t r = {l2[0], l2[1], h2[0], h2[1]};
+    return __builtin_bit_cast(bf16x8_t, r);
+}
+
+// ---------------- backward: dK, dV (phase 1 of attn_bwd_kernel, the queries streamed) ----------------
+// buffer: Q chunk, dO chunk, lse * log2 e, delta.  Rows >= Tq of a chunk are zero in all four: p = 1, dP = 0, dS = 0, and the zero dO / Q
+// rows add nothing.  A key's dK / dV column depends on that key alone, so the dead keys of the last tile need no mask: they are not stored.
+__global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dkdv_kernel(AttnArgs a, int nkblk) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    constexpr int NL = AL_QC * 8 / AL_THREADS;
+    constexpr int BUF = 2 * AL_QC * 128 + 2 * AL_QC * 4;
+    const int H = a.H, Tq = a.Tq, Tk = a.Tk;
+    const int kblk = blockIdx.x % nkblk, mh = blockIdx.x / nkblk;
+    const int m = mh / H, h = mh % H;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned short* qbase = a.q + (long)m * Tq * a.q_ld + h * ATT_D;
+    const unsigned short* kbase = a.k + (long)m * Tk * a.kv_ld + h * ATT_D;
+    const unsigned short* vbase = a.v + (long)m * Tk * a.kv_ld + h * ATT_D;
+    const unsigned short* obase = a.out + (long)m * Tq * a.out_ld + h * ATT_D;
+    const unsigned short* dobase = a.dout + (long)m * Tq * a.out_ld + h * ATT_D;
+    const float* lsebase = a.lse + ((long)m * H + h) * Tq;
+    const int li = lane & 15, g = lane >> 4;
+    const int k0 = kblk * AL_ROWS + w * 16, key = k0 + li;
+    const bool active = k0 < Tk;
+    bf16x8_t kf[2], vf[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        kf[s] = frag_rows_global(kbase, a.kv_ld, k0, s, lane, Tk);
+        vf[s] = frag_rows_global(vbase, a.kv_ld, k0, s, lane, Tk);
+    }
+    const f32x4_t zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4_t dv[4], dk[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        dv[dt] = zero4;
+        dk[dt] = zero4;
+    }
+    const AlOffs off = al_offs(li, g);
+    u32x4_t rq[NL], rdo[NL], ro[NL];
+    float rl = 0.f;
+    auto fetch = [&](int r0) {
+        al_load<AL_QC>(rq, qbase, a.q_ld, r0, Tq, tid);
+        al_load<AL_QC>(rdo, dobase, a.out_ld, r0, Tq, tid);
+        al_load<AL_QC>(ro, obase, a.out_ld, r0, Tq, tid);
+        if (tid < AL_QC) rl = lsebase[min(r0 + tid, Tq - 1)];
+    };
+    auto put = [&](char* buf, int r0) {
+        al_store<AL_QC>(buf, rq, r0, Tq, tid);
+        al_store<AL_QC>(buf + AL_QC * 128, rdo, r0, Tq, tid);
+        float* st = reinterpret_cast<float*>(buf + 2 * AL_QC * 128);
+        if (tid < AL_QC) st[tid] = (r0 + tid < Tq) ? rl * LOG2EF : 0.f;
+        al_delta<AL_QC>(st + AL_QC, ro, rdo, r0, Tq, tid);
+    };
+    fetch(0);
+    put(lds, 0);
+    __syncthreads();
+    const int nch = (Tq + AL_QC - 1) / AL_QC;
+    for (int c = 0; c < nch; ++c) {
+        const char* bufA = lds + (c & 1) * BUF;      // Q; dO sits AL_QC * 128 bytes behind it at the same lane offsets
+        constexpr int dAB = AL_QC * 128;
+        const float* lse2 = reinterpret_cast<const float*>(bufA + 2 * AL_QC * 128);
+        const float* Dq = lse2 + AL_QC;
+        const int r0 = c * AL_QC;
+        if (c + 1 < nch) fetch(r0 + AL_QC);
+        if (active) {
+            const int nqblk = min(AL_QC / 32, (Tq - r0 + 31) >> 5);
+            for (int qb = 0; qb < nqblk; ++qb) {
+                const int blk = qb * 4096;
+                f32x4_t pt[2], dst[2];
+#pragma unroll
+                for (int qt = 0; qt < 2; ++qt) {
+                    f32x4_t sa = zero4, dp = zero4;
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        sa = mfma16(al_rows_frag(bufA + off.r[s] + blk + qt * 2048), kf[s], sa);
+                        dp = mfma16(al_rows_frag(bufA + off.r[s] + dAB + blk + qt * 2048), vf[s], dp);
+                    }
+                    // A rows = queries, B cols = keys -> acc[r] = S[q = 4g + r][key = li]
+                    const int qv = qb * 32 + qt * 16 + 4 * g;
+                    const f32x4_t l4 = *reinterpret_cast<const f32x4_t*>(lse2 + qv);
+                    const f32x4_t d4 = *reinterpret_cast<const f32x4_t*>(Dq + qv);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[r], SCALE_LOG2E, -l4[r]));
+                        pt[qt][r] = p;
+                        dst[qt][r] = p * (dp[r] - d4[r]);
+                    }
+                }
+                const bf16x8_t pf = pack8(pt[0], pt[1]), dsf = pack8(dst[0], dst[1]);
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) {
+                    dv[dt] = mfma16(al_cols_frag(bufA + off.t[dt] + dAB + blk), pf, dv[dt]);
+                    dk[dt] = mfma16(al_cols_frag(bufA + off.t[dt] + blk), dsf, dk[dt]);
+                }
+            }
+        }
+        if (c + 1 < nch) put(lds + ((c + 1) & 1) * BUF, r0 + AL_QC);
+        __syncthreads();
+    }
+    if (active) {
+        const bool live = key < Tk;
+        const long krow = ((long)m * Tk + min(key, Tk - 1)) * a.dkv_ld + h * ATT_D;
+        att_store_tile(dk, ATT_SCALE, a.dk + krow, live, g);
+        att_store_tile(dv, 1.0f, a.dv + krow, live, g);
+    }
+}
+
+// ---------------- backward: dQ (phase 2 of attn_bwd_kernel, the keys streamed) ----------------
+__global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dq_kernel(AttnArgs a, int nqb) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    constexpr int NL = AL_KV * 8 / AL_THREADS;
+    constexpr int BUF = 2 * AL_KV * 128;
+    const int H = a.H, Tq = a.Tq, Tk = a.Tk;
+    const int qb = blockIdx.x % nqb, mh = blockIdx.x / nqb;
+    const int m = mh / H, h = mh % H;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned short* qbase = a.q + (long)m * Tq * a.q_ld + h * ATT_D;
+    const unsigned short* kbase = a.k + (long)m * Tk * a.kv_ld + h * ATT_D;
+    const unsigned short* vbase = a.v + (long)m * Tk * a.kv_ld + h * ATT_D;
+    const unsigned short* obase = a.out + (long)m * Tq * a.out_ld + h * ATT_D;
+    const unsigned short* dobase = a.dout + (long)m * Tq * a.out_ld + h * ATT_D;
+    const float* lsebase = a.lse + ((long)m * H + h) * Tq;
+    const int li = lane & 15, g = lane >> 4;
+    const int qw0 = qb * AL_ROWS;                  // the workgroup's first query row (< Tq)
+    const int q0 = qw0 + w * 16, q = q0 + li;
+    const bool active = q0 < Tq;
+    float* lse2 = reinterpret_cast<float*>(lds + 2 * BUF);      // [AL_ROWS] lse * log2 e, then [AL_ROWS] delta
+    float* Dq = lse2 + AL_ROWS;
+    u32x4_t rk[NL], rv[NL];
+    al_load<AL_KV>(rk, kbase, a.kv_ld, 0, Tk, tid);
+    al_load<AL_KV>(rv, vbase, a.kv_ld, 0, Tk, tid);
+    {
+        u32x4_t ro[AL_ROWS * 8 / AL_THREADS], rdo[AL_ROWS * 8 / AL_THREADS];
+        al_load<AL_ROWS>(ro, obase, a.out_ld, qw0, Tq, tid);
+        al_load<AL_ROWS>(rdo, dobase, a.out_ld, qw0, Tq, tid);
+        if (tid < AL_ROWS) lse2[tid] = (qw0 + tid < Tq) ? lsebase[qw0 + tid] * LOG2EF : 0.f;
+        al_delta<AL_ROWS>(Dq, ro, rdo, qw0, Tq, tid);
+    }
+    al_store<AL_KV>(lds, rk, 0, Tk, tid);
+    al_store<AL_KV>(lds + AL_KV * 128, rv, 0, Tk, tid);
+    bf16x8_t qf[2], dof[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        qf[s] = frag_rows_global(qbase, a.q_ld, q0, s, lane, Tq);
+        dof[s] = frag_rows_global(dobase, a.out_ld, q0, s, lane, Tq);
+    }
+    __syncthreads();
+    const float my_lse = lse2[w * 16 + li], my_D = Dq[w * 16 + li];
+    const f32x4_t zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4_t dq[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) dq[dt] = zero4;
+    const AlOffs off = al_offs(li, g);
+    const int nch = (Tk + AL_KV - 1) / AL_KV;
+    for (int c = 0; c < nch; ++c) {
+        const char* bufA = lds + (c & 1) * BUF;      // K; V sits AL_KV * 128 bytes behind it
+        constexpr int dAB = AL_KV * 128;
+        const int k0 = c * AL_KV;
+        if (c + 1 < nch) {
+            al_load<AL_KV>(rk, kbase, a.kv_ld, k0 + AL_KV, Tk, tid);
+            al_load<AL_KV>(rv, vbase, a.kv_ld, k0 + AL_KV, Tk, tid);
+        }
+        if (active) {
+            const int nkb = min(AL_KV / 32, (Tk - k0 + 31) >> 5);
+            for (int kb = 0; kb < nkb; ++kb) {
+                const int blk = kb * 4096;
+                const bool edge = k0 + kb * 32 + 32 > Tk;
+                f32x4_t dst[2];
+#pragma unroll
+                for (int kt = 0; kt < 2; ++kt) {
+                    f32x4_t sa = zero4, dp = zero4;
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        sa = mfma16(al_rows_frag(bufA + off.r[s] + blk + kt * 2048), qf[s], sa);
+                        dp = mfma16(al_rows_frag(bufA + off.r[s] + dAB + blk + kt * 2048), dof[s], dp);
+                    }
+                    // A rows = keys, B cols = queries -> acc[r] = S[key = 4g + r][q = li]
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) dst[kt][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[r], SCALE_LOG2E, -my_lse));
+                    if (edge) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (k0 + kb * 32 + kt * 16 + 4 * g + r >= Tk) dst[kt][r] = 0.f;
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) dst[kt][r] = dst[kt][r] * (dp[r] - my_D);
+                }
+                const bf16x8_t dsf = pack8(dst[0], dst[1]);
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma16(al_cols_frag(bufA + off.t[dt] + blk), dsf, dq[dt]);
+            }
+        }
+        if (c + 1 < nch) {
+            char* nx = lds + ((c + 1) & 1) * BUF;
+            al_store<AL_KV>(nx, rk, k0 + AL_KV, Tk, tid);
+            al_store<AL_KV>(nx + AL_KV * 128, rv, k0 + AL_KV, Tk, tid);
+        }
+        __syncthreads();
+    }
+    if (active)
+        att_store_tile(dq, ATT_SCALE, a.dq + ((long)m * Tq + min(q, Tq - 1)) * a.dq_ld + h * ATT_D, q < Tq, g);
+}
+
+// what the long kernels take: dense rows, no mask, no bias, no dropout, the default scale
+static bool attn_long_plain(const AttnArgs& a) {
+    return !a.causal && !a.klen && !a.row_off && !a.kv_row_off && !a.rel_emb && a.drop_p == 0.f && a.scale == ATT_SCALE;
+}
+static const int AL_FWD_LDS = 2 * 2 * AL_KV * 128;
+static const int AL_DKDV_LDS = 2 * (2 * AL_QC * 128 + 2 * AL_QC * 4);
+static const int AL_DQ_LDS = 2 * 2 * AL_KV * 128 + 2 * AL_ROWS * 4;
+
+int launch_attn_long_fwd(const AttnArgs& a, int batch, hipStream_t st, bool f16) {
+    if (!attn_long_plain(a) || a.Tq < 1 || a.Tk < 1 || a.Tq > 1024 || a.Tk > 1024) return UNIIR_ESHAPE;
+    const int nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
+    const long grid = (long)batch * a.H * nqb;
+    if (grid > 0x7fffffffL) return UNIIR_ESHAPE;
+    static PerDeviceOnce attr;
+    if (attr.first()) {
+        (void)hipFuncSetAttribute((const void*)attn_long_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_FWD_LDS);
+        (void)hipFuncSetAttribute((const void*)attn_long_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_FWD_LDS);
+    }
+    if (f16) hipLaunchKernelGGL(attn_long_fwd_kernel<true>, dim3((unsigned)grid), dim3(AL_THREADS), AL_FWD_LDS, st, a, nqb);
+    else hipLaunchKernelGGL(attn_long_fwd_kernel<false>, dim3((unsigned)grid), dim3(AL_THREADS), AL_FWD_LDS, st, a, nqb);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+int launch_attn_long_bwd(const AttnArgs& a, int batch, hipStream_t st) {
+    if (!attn_long_plain(a) || a.Tq < 1 || a.Tk < 1 || a.Tq > 1024 || a.Tk > 1024) return UNIIR_ESHAPE;
+    const int nkblk = (a.Tk + AL_ROWS - 1) / AL_ROWS, nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
+    const long gk = (long)batch * a.H * nkblk, gq = (long)batch * a.H * nqb;
+    if (gk > 0x7fffffffL || gq > 0x7fffffffL) return UNIIR_ESHAPE;
+    static PerDeviceOnce attr;
+    if (attr.first()) {
+        (void)hipFuncSetAttribute((const void*)attn_long_dkdv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DKDV_LDS);
+        (void)hipFuncSetAttribute((const void*)attn_long_dq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DQ_LDS);
+    }
+    hipLaunchKernelGGL(attn_long_dkdv_kernel, dim3((unsigned)gk), dim3(AL_THREADS), AL_DKDV_LDS, st, a, nkblk);
+    HIP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(attn_long_dq_kernel, dim3((unsigned)gq), dim3(AL_THREADS), AL_DQ_LDS, st, a, nqb);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}

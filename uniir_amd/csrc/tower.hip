@@ -101,7 +101,7 @@ Plan plan(const uniir_clip_tower* t, int batch, bool save, int rows = -1, const 
     p.lay_stride = (save && !p.recompute) ? lc : 0;
     cur += (save && !p.recompute) ? lc * p.L : lc;
     p.x_last = take(R * W * 4);          // with !save the stream ping-pongs between o_x of the single layer set and this
-    p.pool_last = t->pool_last_block != 0;
+    p.pool_last = t->pool_last_block != 0 && t->tokens <= 512;      // the one-query attention holds all keys in LDS: above 512 tokens the full last block runs (same embeddings)
     if (p.pool_last) {
         p.pl_q = take(M * W * 2); p.pl_h1 = take(M * W * 2); p.pl_x = take(M * W * 4); p.pl_ao = take(M * W * 2);
         p.pl_lse = take(M * (int64_t)p.H * 4); p.pl_x2 = take(M * W * 4); p.pl_h2 = take(M * W * 2);
@@ -140,7 +140,8 @@ int check_tower(const uniir_clip_tower* t, int batch) {
     if (!t || !t->blocks || batch < 0) return UNIIR_EINVAL;
     if (t->layers <= 0 || t->width <= 0 || t->heads <= 0 || t->tokens < 2 || t->embed_dim <= 0) return UNIIR_EINVAL;
     if (t->recompute != 0 && t->recompute != 1) return UNIIR_EINVAL;
-    if (t->width != t->heads * 64 || t->width % 64 || t->embed_dim % 8 || t->tokens > 512) return UNIIR_ESHAPE;
+    // (a vision tower's plain attention streams up to 1024 tokens, attention_long.hip; the causal / packed text forms hold a head in LDS)
+    if (t->width != t->heads * 64 || t->width % 64 || t->embed_dim % 8 || t->tokens > (t->is_text ? 512 : 1024)) return UNIIR_ESHAPE;
     if (!t->pos_emb || !t->ln_post_w || !t->ln_post_b || !t->proj16) return UNIIR_EINVAL;
     if (t->is_text) {
         if (!t->token_emb || t->vocab <= 0) return UNIIR_EINVAL;

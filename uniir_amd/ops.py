@@ -222,6 +222,9 @@ def layernorm_bwd(x, gamma, dy, dgamma, dbeta, eps=1e-5, *, dres=None, dx=None, 
 
 
 def attention_fwd(qkv, batch, seq, heads, causal, *, out=None, lse=None):
+    """softmax(q k^T / 8 [+ causal mask]) v on the packed in_proj layout qkv [batch*seq, 3*heads*64] (bf16) -> out [batch*seq, heads*64],
+    lse [batch, heads, seq] (fp32, natural log).  seq <= 512 with or without the causal mask; 513 .. 1024 tokens without it (the
+    streaming kernels of csrc/attention_long.hip); anything longer, or causal above 512, is UNIIR_ESHAPE."""
     if out is None:
         out = torch.empty(batch * seq, heads * 64, device=qkv.device, dtype=torch.bfloat16)
     if lse is None:
@@ -232,6 +235,7 @@ def attention_fwd(qkv, batch, seq, heads, causal, *, out=None, lse=None):
 
 
 def attention_bwd(qkv, out, dout, lse, batch, seq, heads, causal, *, dqkv=None):
+    """d loss / d qkv of attention_fwd (bf16, same layout and the same limits on seq); bitwise reproducible at every length."""
     if dqkv is None:
         dqkv = torch.empty_like(qkv)
     check(_lib.load().uniir_attention_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), batch, seq, heads,
