@@ -158,9 +158,16 @@ int uniir_attention_fwd_packed(const void* qkv, void* out, float* lse, const int
                                int32_t max_seq, int32_t heads, int32_t causal, void* stream);
 int uniir_attention_bwd_packed(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                const int32_t* row_off, int32_t batch, int32_t max_seq, int32_t heads, int32_t causal, void* stream);
+/* Every packed item has at least one row (row_off[m + 1] > row_off[m]) and every key_len[m] below is >= 1: the kernels stage an
+ * item's row T - 1 for the padding behind it, so a length of 0 is not an input. */
+/* The forward on fp16 tensors (qkv / out fp16, lse f32): row_off == NULL is uniir_attention_fwd (causal = 0: seq <= 1024, causal = 1:
+ * seq <= 512), otherwise uniir_attention_fwd_packed (seq = max_seq <= 512).  There is no fp16 backward. */
+int uniir_attention_fwd_f16(const void* qkv, void* out, float* lse, const int32_t* row_off, int32_t batch, int32_t seq,
+                            int32_t heads, int32_t causal, void* stream);
 /* General form: separate Q [batch*tq][q_ld] and K/V [batch*tk][kv_ld] tensors (head h at column h*64) for the BLIP
  * MED cross-attention (uniir_blip/backbone/med.py:160-232 with encoder_hidden_states), and an optional per-item key
- * length (keys >= key_len[m] masked: the BERT padding mask, med.py:687-688 "(1 - mask) * -10000").
+ * length (keys >= key_len[m] masked: the BERT padding mask, med.py:687-688 "(1 - mask) * -10000"; 1 <= key_len[m], values above
+ * tk count as tk: a row with no valid key is not an input).
  * lse is [batch][heads][tq].  bwd writes dq [batch*tq][dq_ld], dk / dv [batch*tk][dkv_ld]. */
 int uniir_attention_fwd_ex(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, void* out,
                            int64_t out_ld, float* lse, const int32_t* key_len, int32_t batch, int32_t tq,

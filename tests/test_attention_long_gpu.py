@@ -2,8 +2,9 @@
 against fp32 torch on the bf16-rounded inputs (the reference of tests/test_kernels_gpu.py::test_attention_fwd_bwd, restated here),
 with that test's gates.
 
-The fp16 forward (attn_long_fwd_kernel<true>) has no handle in uniir_amd.ops: it is reached through the fp16 towers only, so
-tests/test_clip_336_gpu.py::test_fp16_and_fp32_embeddings_against_the_oracle covers it (577 tokens, against the fp32 oracle)."""
+The fp16 forward (attn_long_fwd_kernel<true>) has its own entry point, uniir_attention_fwd_f16: tests/test_attention_paths_gpu.py
+judges it element by element against the fp64 reference at 513 .. 1024 tokens, and the fp16 towers reach it in
+tests/test_clip_336_gpu.py::test_fp16_and_fp32_embeddings_against_the_oracle (577 tokens, against the fp32 oracle)."""
 import os
 import sys
 

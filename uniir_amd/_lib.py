@@ -71,6 +71,7 @@ SIGNATURES = {
     "uniir_attention_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, S]),
     "uniir_attention_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, S]),
     "uniir_attention_fwd_packed": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, S]),
+    "uniir_attention_fwd_f16": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, S]),
     "uniir_attention_bwd_packed": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, S]),
     "uniir_attention_fwd_ex": (c_int, [P, c_i64, P, P, c_i64, P, c_i64, P, P, c_int, c_int, c_int, c_int, c_int, c_float,
                                        C.c_uint32, S]),

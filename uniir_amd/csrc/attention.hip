@@ -632,6 +632,13 @@ extern "C" int uniir_attention_fwd(const void* qkv, void* out, float* lse, int32
     return launch_attn_fwd(a, batch, (hipStream_t)stream);
 }
 
+// the fp16 forward of the embedding towers on its own (fp16 qkv / out): dense rows (row_off == nullptr; plain up to 1024 tokens,
+// causal up to 512) or packed rows (up to 512); the argument checks are attention_fwd_impl's, those of uniir_attention_fwd / _fwd_packed
+extern "C" int uniir_attention_fwd_f16(const void* qkv, void* out, float* lse, const int32_t* row_off, int32_t batch, int32_t seq,
+                                       int32_t heads, int32_t causal, void* stream) {
+    return attention_fwd_impl(qkv, out, lse, row_off, batch, seq, heads, causal, 1, stream);
+}
+
 extern "C" int uniir_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
                                    void* dqkv, int32_t batch, int32_t seq, int32_t heads, int32_t causal,
                                    void* stream) {
