@@ -34,7 +34,7 @@ extern "C" {
 #define UNIIR_EUNSUPPORTED (-5)
 
 const char* uniir_strerror(int code);
-/* ABI version; bumped on any signature or struct-layout change (3: uniir_clip_tower.recompute). */
+/* ABI version; bumped on any signature or struct-layout change (3: uniir_clip_tower.recompute; 4: uniir_reduce_stats). */
 int uniir_abi_version(void);
 /* Reproducible reductions (round 6).  Bias, LayerNorm-weight and token-embedding gradients are sums over every row of a batch taken by
  * many workgroups; added with fp32 atomics they depend on the arrival order, and two runs of one training step differ in their last
@@ -42,9 +42,19 @@ int uniir_abi_version(void);
  * the entry) and every such reduction launched on that stream -- uniir_gemm's colsum / a_rowsum, uniir_layernorm_bwd*, uniir_colsum_bf16,
  * uniir_text_embed_bwd* and the tower entry points that use them -- stores per-workgroup partials there and adds them in a fixed
  * order (one extra small launch each): same inputs, same bits.  Kernels on one stream run one after the other, so one buffer per
- * stream is enough.  A reduction that needs more than the buffer holds keeps its atomics.  Host-side table (16 streams), not
- * thread-safe: one training thread per process, as in the reference (train.py). */
+ * stream is enough.  A reduction that needs more than the buffer holds keeps its atomics, and is counted (uniir_reduce_stats).  Also
+ * covered since ABI 4: the relative-position-bias gradient of uniir_attention_rel_bwd (per-workgroup bucket partials).
+ * Thread safety: the host-side table (64 entries, one per (device, stream); when it is full the entry used longest ago goes) and the
+ * counters are guarded by one mutex, so uniir_reduce_scratch, uniir_reduce_stats and the lookups that launches make may run on any
+ * threads at once.  NOT covered: the buffer itself -- two threads that launch reductions on the SAME stream share its scratch and
+ * must order their launches themselves, and a buffer must stay alive until the entry is replaced or removed and the stream's work
+ * that used it has finished. */
 int uniir_reduce_scratch(void* buf, int64_t bytes, void* stream);
+/* process-wide, since the last reset: fallbacks = reduction launches that took the arrival-order (atomic) form because the stream
+ * had no scratch or too small a one; max_request = the largest scratch size any reduction asked for, in bytes.  Either pointer may be
+ * NULL.  An explicit UNIIR_EPI_ATOMIC_F32 epilogue is the caller's request and is not counted.  A caller that grows a stream's buffer
+ * to max_request whenever fallbacks moved has at most the first step of a new geometry in arrival order. */
+int uniir_reduce_stats(int64_t* fallbacks, int64_t* max_request, int32_t reset);
 
 /* ------------------------------------------------------------------------------------------------
  * [ENC] building block 1: 16-bit MFMA GEMM with fused epilogues.
@@ -210,6 +220,11 @@ int uniir_vit_assemble_bwd(const float* dx, void* dpatch_out, float* dclass, flo
 /* x[n][ctx][w] (f32) = token_emb[text[n][t]] + pos_emb[t]; also eot[n] = argmax_t text[n][t] (first max) */
 int uniir_text_embed(const int32_t* text, const float* token_emb, const float* pos_emb, float* x,
                      int32_t* eot, int32_t n, int32_t ctx, int32_t width, int32_t vocab, void* stream);
+/* dtoken_emb[text[n][t]] += dx[n][t], dpos[t] += sum_n dx[n][t].  With a scratch buffer on the stream (uniir_reduce_scratch) the rows
+ * of a token id are added in ascending row order whatever their number (ids with more than 4096 rows: in row slices whose partials
+ * are added in slice order): reproducible bit for bit.  Without one, or for a shape that form does not take (width % 4, a pointer
+ * that is not 16-byte aligned, vocab > 65536, n * ctx > 65535 * 4096), fp32 atomics in arrival order, counted by
+ * uniir_reduce_stats.  The same holds for the packed form below. */
 int uniir_text_embed_bwd(const int32_t* text, const float* dx, float* dtoken_emb, float* dpos,
                          int32_t n, int32_t ctx, int32_t width, int32_t vocab, void* stream);
 /* the same on packed rows: x row row_off[n] + t for t < row_off[n + 1] - row_off[n]; last_row[n] (optional) = the item's last row */
@@ -248,7 +263,8 @@ int uniir_fuse_embeddings(const float* txt_emb, const float* img_emb, const int6
                           const int64_t* img_mask, float* emb, int32_t n, int32_t dim, void* stream);
 int uniir_select_normalize(const float* emb, const int32_t* idx, float* out, float* inv_norm,
                            int32_t rows, int32_t dim, void* stream);
-/* demb[idx[i]] += (dout[i] - out[i] * <out[i], dout[i]>) * inv_norm[i]  (demb zeroed by the caller) */
+/* demb[idx[i]] += (dout[i] - out[i] * <out[i], dout[i]>) * inv_norm[i]  (demb zeroed by the caller).  idx may repeat: the rows that
+ * share a destination are added in ascending i by a single writer, so the result is reproducible bit for bit. */
 int uniir_select_normalize_bwd(const float* out, const float* inv_norm, const float* dout,
                                const int32_t* idx, float* demb, int32_t rows, int32_t dim, void* stream);
 /* dtxt = demb * txt_mask, dimg = demb * img_mask */
@@ -276,7 +292,8 @@ int uniir_infonce_bwd(const float* q, const float* all_p, const float* scale, co
  * in_batch_neg_num): the reference's expand/mask expression for the "in-batch negatives" yields the query's own
  * positive I times, which is reproduced as is (golden G3).  fwd: logits [b][1+N+I], row_lse, row_loss (= -log_softmax(row)[0]) and
  * row_hit (first arg-max == 0) per query; loss = mean(row_loss), accuracy = mean(row_hit).
- * bwd (dloss: device scalar): dq, dn written; dp and dscale ACCUMULATED (zero them first). */
+ * bwd (dloss: device scalar): dq, dn written; dp and dscale ACCUMULATED (zero them first).  Reproducible bit for bit: every dp element
+ * has one writer, and dscale is one fixed-order sum over the b rows added to dscale by a single thread. */
 int uniir_hardneg_fwd(const float* q, const float* p, const float* n, const float* scale, int32_t b, int32_t N,
                       int32_t I, int32_t dim, float* logits, float* row_lse, float* row_loss, float* row_hit,
                       void* stream);
@@ -495,6 +512,11 @@ int uniir_rmsnorm_bwd(const float* x, int64_t x_stride, const float* gamma, cons
 int uniir_attention_rel_fwd(const void* qkv, void* out, float* lse, const float* rel_emb, const int32_t* rel_bucket,
                             int32_t nbuckets, float scale, int32_t batch, int32_t seq, int32_t heads, float drop_p,
                             uint32_t drop_seed, void* stream);
+/* drel [nbuckets][heads] (fp32) += d loss / d rel_emb (accumulated: the layers of a T5 stack share one table; zero it once per
+ * step).  With a scratch buffer of batch * heads * nbuckets floats on the stream the sum has one fixed order (64-bit fixed-point sums
+ * of 2^-40 units inside a workgroup: |sum| < 2^23 per (item, head, bucket); the items' partials added in item order) and is
+ * reproducible bit for bit; otherwise one float atomic per (item, head, bucket), counted by uniir_reduce_stats.  dqkv never depends
+ * on arrival order. */
 int uniir_attention_rel_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                             const float* rel_emb, const int32_t* rel_bucket, int32_t nbuckets, float scale, float* drel,
                             int32_t batch, int32_t seq, int32_t heads, float drop_p, uint32_t drop_seed, void* stream);

@@ -184,6 +184,7 @@ struct AttnArgs {
     const float* rel_emb;         // optional [buckets][H] fp32
     const int* rel_bucket;        // [Tq + Tk - 1] bucket of every key - query offset
     float* drel;                  // backward, optional: [buckets][H] += d loss / d rel_emb
+    float* drel_part;             // backward, optional: [batch][buckets][H] per-workgroup partials of drel (written; the launcher reduces them)
     int nbuckets;
     // attention-probability dropout (BERT attention_probs_dropout_prob, T5 dropout_rate): P V uses P * mask / keep with
     // mask(seed, ((m H + h) Tq + q) Tk + key) (common.h drop_hash); the softmax statistics stay those of the full P

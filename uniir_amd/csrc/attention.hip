@@ -192,6 +192,11 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(AttnArgs a) {
 // NT threads: 512 (8 waves, 128 registers) or 384 (6 waves, 168 registers: no spills, and 5 key tiles of a 77-token head keep 5 of
 // 6 waves busy instead of 5 of 8) -- the launcher picks 384 up to 128 tokens (measured: 50 tokens 0.335 -> 0.261 ms, 77 causal
 // 0.518 -> 0.386 ms at 1024 items; 197 / 257 tokens lose 15-20 % with fewer waves).
+// Fixed point of the relative-position-bias gradient: 2^-40 per unit, so a (workgroup, bucket) sum holds |x| < 2^23 and resolves
+// 9.1e-13 -- finer than the fp32 rounding of any sum above 1.5e-5, and each term is rounded once (round to nearest) where a float
+// accumulator rounds at every add.  A term beyond the range saturates (__float2ll_rn), a NaN term counts as 0: dqkv carries the NaN.
+#define ATT_DREL_FIX 1099511627776.0f
+DEVINL unsigned long long att_drel_fix(float v) { return (unsigned long long)__float2ll_rn(v * ATT_DREL_FIX); }
 template <bool REL, bool DROP, bool CAUSAL, int NT>
 __global__ __launch_bounds__(NT, NT == 512 ? 4 : 3) void attn_bwd_kernel(AttnArgs a) {
     constexpr int NWAVES = NT / 64;
@@ -216,8 +221,10 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : 3) void attn_bwd_kernel(AttnArg
     char* bufB = lds + Tmax * 128;    // dO, later V
     float* lse2 = reinterpret_cast<float*>(lds + 2 * Tmax * 128);
     float* Dq = lse2 + Tqp;
-    float* dbias = Dq + Tqp;               // [Tq + Tk - 1] bias per diagonal (x log2 e), only with rel_emb
-    float* ddiag = dbias + (Tq + Tk);      // [Tq + Tk - 1] gradient per diagonal
+    // only with rel_emb: the bias gradient per bucket and per diagonal as 64-bit fixed point (ATT_DREL_FIX), the bias per diagonal
+    unsigned long long* bsum = reinterpret_cast<unsigned long long*>(Dq + Tqp);      // [64]
+    unsigned long long* ddiag = bsum + 64;                                           // [Tq + Tk - 1]
+    float* dbias = reinterpret_cast<float*>(ddiag + (Tq + Tk));                      // [Tq + Tk - 1] (x log2 e)
     const float sl2 = REL ? a.scale * LOG2EF : SCALE_LOG2E;
     const float oscale = REL ? a.scale : ATT_SCALE;
     const unsigned dth = DROP ? drop_threshold(a.drop_p) : 0u;
@@ -253,10 +260,11 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : 3) void attn_bwd_kernel(AttnArg
             Dq[r] = d;
             lse2[r] = l;
         }
+        if (REL && tid < 64) bsum[tid] = 0ull;
         if (REL)
             for (int d = tid; d < Tq + Tk - 1; d += NT) {
                 dbias[d] = a.rel_emb[a.rel_bucket[d] * H + h] * LOG2EF;
-                ddiag[d] = 0.f;
+                ddiag[d] = 0ull;
             }
     };
     ATT_STAMP(0);
@@ -354,7 +362,9 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : 3) void attn_bwd_kernel(AttnArg
                     dst[qt][r] = p * ((DROP ? dp[r] * mk : dp[r]) - d4[r]);
                 }
                 if (REL && a.drel) {
-                    // d bias = d logits summed along the diagonals.  An LDS float atomic costs ~155 cycles per 64-lane instruction
+                    // d bias = d logits summed along the diagonals, by all waves at once.  The sums are taken in 64-bit fixed point
+                    // (att_drel_fix): integer addition is associative, so the LDS atomics below give the same bits in whatever
+                    // order the waves arrive (float atomics did not).  An LDS float atomic cost ~155 cycles per 64-lane instruction
                     // (measured: 3.1 of the 4.9 ms of this kernel at 334 tokens were the four per-element atomics), so the 4 x 16
                     // block of this 16-lane row is first summed along its diagonals with DPP row shifts: lane j ends with
                     // diagonal (key_j - (qv + 3)), i.e. d(r = 3, j) + d(2, j - 1) + d(1, j - 2) + d(0, j - 3); the six elements
@@ -371,13 +381,13 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : 3) void attn_bwd_kernel(AttnArg
                     t = v[2] + shr1(t);
                     t = v[3] + shr1(t);
                     const int dgt = key - (qv + 3) + Tq - 1;
-                    if (dgt >= 0 && dgt <= Tq + Tk - 2 && t != 0.f) atomicAdd(&ddiag[dgt], t);
+                    if (dgt >= 0 && dgt <= Tq + Tk - 2 && t != 0.f) atomicAdd(&ddiag[dgt], att_drel_fix(t));
                     const float w1 = li >= 14 ? v[1] : 0.f, w2 = li == 15 ? v[2] : 0.f;
                     float wv = li >= 13 ? v[0] : 0.f;
                     wv += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, w1), 0x101, 0xf, 0xf, true));   // row_shl:1
                     wv += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, w2), 0x102, 0xf, 0xf, true));   // row_shl:2
                     const int dgw = key - qv + Tq - 1;
-                    if (li >= 13 && dgw >= 0 && dgw <= Tq + Tk - 2 && wv != 0.f) atomicAdd(&ddiag[dgw], wv);
+                    if (li >= 13 && dgw >= 0 && dgw <= Tq + Tk - 2 && wv != 0.f) atomicAdd(&ddiag[dgw], att_drel_fix(wv));
                 }
             }
             const bf16x8_t pf = pack8(pt[0], pt[1]), dsf = pack8(dst[0], dst[1]);
@@ -462,15 +472,21 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : 3) void attn_bwd_kernel(AttnArg
         att_store_tile(dq, oscale, dqbase + (long)min(q, Tq - 1) * a.dq_ld, q < Tq && !ATT_EXP(16), g);
     }
     ATT_STAMP(7);
-    if (REL && a.drel) {      // diagonals -> buckets -> global (one atomic per touched bucket and workgroup)
+    if (REL && a.drel) {
+        // diagonals -> buckets, still in fixed point (any order gives the same integer), then ONE conversion to fp32 per bucket.  With
+        // a partial buffer the workgroup stores its nbuckets sums, zeros included, and the launcher adds the items' partials into
+        // drel in item order (reduce_partials); without one they go to drel with float atomics in arrival order (a counted lapse).
         __syncthreads();
-        float* bsum = lse2;     // phase 2 is over: reuse
-        for (int b = tid; b < a.nbuckets; b += NT) bsum[b] = 0.f;
+        for (int d = tid; d < Tq + Tk - 1; d += NT) {
+            const unsigned long long v = ddiag[d];
+            if (v) atomicAdd(&bsum[a.rel_bucket[d]], v);
+        }
         __syncthreads();
-        for (int d = tid; d < Tq + Tk - 1; d += NT) atomicAdd(&bsum[a.rel_bucket[d]], ddiag[d]);
-        __syncthreads();
-        for (int b = tid; b < a.nbuckets; b += NT)
-            if (bsum[b] != 0.f) atomicAdd(a.drel + b * H + h, bsum[b]);
+        for (int b = tid; b < a.nbuckets; b += NT) {
+            const float v = (float)(long long)bsum[b] * (1.0f / ATT_DREL_FIX);
+            if (a.drel_part) a.drel_part[((long)m * a.nbuckets + b) * H + h] = v;
+            else if (v != 0.f) atomicAdd(a.drel + b * H + h, v);
+        }
     }
 }
 
@@ -517,7 +533,7 @@ template <int NT>
 static int launch_attn_bwd_nt(const AttnArgs& a, int batch, int sm, hipStream_t st) {
     static PerDeviceOnce attr;
     if (attr.first()) {
-        const int big = 2 * 512 * 128 + 2 * 512 * 4 + 2 * 1024 * 4;
+        const int big = 2 * 512 * 128 + 2 * 512 * 4 + 64 * 8 + 1024 * 12;      // 147968 of the 163840 bytes of a workgroup
         (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<false, false, false, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
         (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<false, true, false, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
         (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<true, false, false, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
@@ -556,7 +572,7 @@ static int launch_attn_bwd(const AttnArgs& a0, int batch, hipStream_t st) {
     a.legacy_stage = attn_legacy_stage(true, tmax);
     const int Tqp = (a.Tq + 31) & ~31, Tkp = (a.Tk + 31) & ~31;
     const int Tmax = Tqp > Tkp ? Tqp : Tkp;
-    const int sm = 2 * Tmax * 128 + 2 * Tqp * 4 + (a.rel_emb ? 2 * (a.Tq + a.Tk) * 4 : 0);
+    const int sm = 2 * Tmax * 128 + 2 * Tqp * 4 + (a.rel_emb ? 64 * 8 + (a.Tq + a.Tk) * 12 : 0);
     bool six = tmax <= 128;
     if (six && (Tmax * 8 + 383) / 384 > 8) six = false;      // stage_two holds <= 8 loads per thread and slice: 384 threads stop at 384 tokens
     return six ? launch_attn_bwd_nt<384>(a, batch, sm, st) : launch_attn_bwd_nt<512>(a, batch, sm, st);
@@ -792,7 +808,8 @@ extern "C" int uniir_attention_bwd_rows(const void* q, int64_t q_ld, const void*
 
 // T5-style self-attention for the CLIP_FF fusion stack: logits = scale * q.k + rel_emb[rel_bucket[key - query + seq - 1]][head]
 // (transformers T5Attention: scale 1, bucketed relative position bias shared by all layers), packed qkv like
-// uniir_attention_fwd.  bwd adds d loss / d rel_emb into drel (fp32 [buckets][heads], zero it once per step).
+// uniir_attention_fwd.  bwd adds d loss / d rel_emb into drel (fp32 [buckets][heads], zero it once per step), in a fixed order when
+// the stream has a scratch buffer: fixed-point sums inside a workgroup, the workgroups' partials added in item order.
 extern "C" int uniir_attention_rel_fwd(const void* qkv, void* out, float* lse, const float* rel_emb,
                                        const int32_t* rel_bucket, int32_t nbuckets, float scale, int32_t batch,
                                        int32_t seq, int32_t heads, float drop_p, uint32_t drop_seed, void* stream) {
@@ -830,5 +847,10 @@ extern "C" int uniir_attention_rel_bwd(const void* qkv, const void* out, const v
     a.rel_emb = rel_emb; a.rel_bucket = rel_bucket; a.nbuckets = nbuckets; a.drel = drel;
     if (drop_p < 0.f || drop_p >= 1.f) return UNIIR_EINVAL;
     a.drop_p = drop_p; a.drop_seed = drop_seed;
-    return launch_attn_bwd(a, batch, (hipStream_t)stream);
+    // one workgroup per (item, head) stores its bucket sums in the stream's scratch as [item][bucket][head]; they are added into drel
+    // in item order below.  drel is accumulated, not overwritten: the layers of a T5 stack share one bias table.
+    if (drel) a.drel_part = reduce_scratch((hipStream_t)stream, (int64_t)batch * heads * nbuckets * 4);
+    const int rc = launch_attn_bwd(a, batch, (hipStream_t)stream);
+    if (rc || !a.drel_part) return rc;
+    return reduce_partials(a.drel_part, batch, (long)nbuckets * heads, nbuckets * heads, drel, nullptr, nullptr, 0, (hipStream_t)stream);
 }

@@ -4,6 +4,7 @@
 // embeddings, token embedding, EOT pooling) as called from clip_sf.py:43-47.
 #include "common.h"
 #include "../../include/uniir_hip.h"
+#include <mutex>
 
 static inline int grid_for(long work, int per_block, int cap = 8192) {
     long g = (work + per_block - 1) / per_block;
@@ -17,6 +18,10 @@ static inline int grid_for(long work, int per_block, int cap = 8192) {
 #define RED_SLOTS 64
 static struct { hipStream_t st; int dev; float* buf; int64_t bytes; bool used; unsigned long stamp; } g_red_scratch[RED_SLOTS];
 static unsigned long g_red_clock = 0;
+// one lock for the table, its clock and the lapse counters: registration, lookup and the stamp may come from any host thread (ctypes
+// releases the GIL around every call)
+static std::mutex g_red_mutex;
+static int64_t g_red_fallbacks = 0, g_red_max_request = 0;
 static int red_device() {          // the NULL stream is every device's default stream: entries are per (device, stream)
     int d = 0;
     (void)hipGetDevice(&d);
@@ -26,6 +31,7 @@ extern "C" int uniir_reduce_scratch(void* buf, int64_t bytes, void* stream) {
     if ((buf && bytes <= 0) || ((uintptr_t)buf & 255)) return UNIIR_EINVAL;
     int slot = -1, oldest = 0;
     const int dev = red_device();
+    std::lock_guard<std::mutex> lock(g_red_mutex);
     for (int i = 0; i < RED_SLOTS; ++i) {
         if (g_red_scratch[i].used && g_red_scratch[i].st == (hipStream_t)stream && g_red_scratch[i].dev == dev) {
             if (!buf) { g_red_scratch[i].used = false; return UNIIR_OK; }
@@ -42,17 +48,32 @@ extern "C" int uniir_reduce_scratch(void* buf, int64_t bytes, void* stream) {
     g_red_scratch[slot].bytes = bytes; g_red_scratch[slot].used = true; g_red_scratch[slot].stamp = ++g_red_clock;
     return UNIIR_OK;
 }
+// Every caller that gets nullptr here launches its arrival-order (atomic) form, so the lapse is counted here, with the size asked for.
 float* reduce_scratch(hipStream_t st, int64_t bytes) {
     int dev = -1;
+    std::lock_guard<std::mutex> lock(g_red_mutex);
+    if (bytes > g_red_max_request) g_red_max_request = bytes;
     for (int i = 0; i < RED_SLOTS; ++i)
         if (g_red_scratch[i].used && g_red_scratch[i].st == st) {
-            if (dev < 0) dev = red_device();
-            if (g_red_scratch[i].dev == dev) {
-                g_red_scratch[i].stamp = ++g_red_clock;
-                return g_red_scratch[i].bytes >= bytes ? g_red_scratch[i].buf : nullptr;
-            }
+            if (dev < 0) dev = red_device();          // asked only when a stream matches (a process without scratch never pays for it)
+            if (g_red_scratch[i].dev != dev) continue;
+            g_red_scratch[i].stamp = ++g_red_clock;
+            if (g_red_scratch[i].bytes >= bytes) return g_red_scratch[i].buf;
+            break;
         }
+    ++g_red_fallbacks;
     return nullptr;
+}
+void reduce_lapse() {          // an atomic form taken without asking for scratch (a shape the fixed-order form does not cover)
+    std::lock_guard<std::mutex> lock(g_red_mutex);
+    ++g_red_fallbacks;
+}
+extern "C" int uniir_reduce_stats(int64_t* fallbacks, int64_t* max_request, int32_t reset) {
+    std::lock_guard<std::mutex> lock(g_red_mutex);
+    if (fallbacks) *fallbacks = g_red_fallbacks;
+    if (max_request) *max_request = g_red_max_request;
+    if (reset) g_red_fallbacks = g_red_max_request = 0;
+    return UNIIR_OK;
 }
 // block = 8 groups of 4 columns x 32 chunks of the parts; chunk q adds its contiguous range of parts in order (16-byte loads, all
 // independent), the 32 chunk sums are added in order: one fixed summation tree per column, whatever order the producers finished in.
@@ -301,9 +322,14 @@ extern "C" int uniir_text_embed(const int32_t* text, const float* token_emb, con
 // words collide), so the plain kernels below add with fp32 atomics in arrival order.  With a scratch buffer on the stream the rows are
 // bucketed by id instead (counting sort: integer atomics only, whose results do not depend on order), every bucket is put in ascending
 // row order, and one workgroup per id adds its rows in that order: the same bits every run.  A bucket longer than TOKD_SORT rows
-// (only the padding id of an UNPACKED batch -- rows behind the EOT / the valid length, whose gradients are exact zeros -- or the
-// special tokens of a batch of more than 4096 captions) is added in bucket order as filled.
+// (the padding id of an UNPACKED batch, the special tokens of a batch of more than 4096 captions) does not fit the LDS sort and
+// would keep one workgroup busy for milliseconds.  Its rows are cut by ROW RANGE instead: slice s holds the rows s * TOKD_SORT ..
+// (s + 1) * TOKD_SORT - 1, rows are unique, so a slice has at most TOKD_SORT entries of any bucket.  One workgroup per (long id, slice,
+// column slab) picks its slice's entries out of the bucket (in whatever order it was filled), sorts and adds them like a short
+// bucket and stores the partial; the slices' partials are then added into dtok in slice order.  Neither depends on the fill order.
+// The long ids are handled TOKD_KCAP at a time (rounds that find no long id left end at once), which bounds the partial buffer.
 #define TOKD_SORT 4096
+#define TOKD_KCAP 8
 DEVINL bool tokd_row(const int* __restrict__ text, const int* __restrict__ row_off, long row, int ctx, int vocab, int* id, long* dxrow) {
     const int t = (int)(row % ctx), m = (int)(row / ctx);
     if (row_off) {
@@ -327,8 +353,10 @@ __global__ __launch_bounds__(256) void tokd_count_kernel(const int* __restrict__
 // one workgroup: starts = exclusive prefix sums of counts ([vocab + 1]), cursor = a copy the fill pass advances.  A thread owns
 // <= TOKD_PER consecutive ids, read with all loads in flight (vocab <= 1024 * TOKD_PER)
 #define TOKD_PER 64
+// longs (when kmax > 0): [0] = the number of ids with more than TOKD_SORT rows (at most kmax = rows / (TOKD_SORT + 1)), then those ids
+// in ascending order
 __global__ __launch_bounds__(1024) void tokd_scan_kernel(const int* __restrict__ counts, int* __restrict__ starts, int* __restrict__ cursor,
-                                                         int vocab) {
+                                                         int vocab, int* __restrict__ longs, int kmax) {
     __shared__ int part[1024];
     const int tid = threadIdx.x, per = (vocab + 1023) / 1024, lo = tid * per;
     int c[TOKD_PER];
@@ -355,6 +383,27 @@ __global__ __launch_bounds__(1024) void tokd_scan_kernel(const int* __restrict__
         }
     }
     if (tid == 1023) starts[vocab] = part[1023];
+    if (kmax <= 0) return;
+    int nl = 0;
+#pragma unroll
+    for (int i = 0; i < TOKD_PER; ++i) nl += c[i] > TOKD_SORT;
+    __syncthreads();
+    part[tid] = nl;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const int v = tid >= off ? part[tid - off] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int at = part[tid] - nl;
+#pragma unroll
+    for (int i = 0; i < TOKD_PER; ++i)
+        if (c[i] > TOKD_SORT) {
+            if (at < kmax) longs[1 + at] = lo + i;
+            ++at;
+        }
+    if (tid == 1023) longs[0] = min(part[1023], kmax);
 }
 __global__ __launch_bounds__(256) void tokd_fill_kernel(const int* __restrict__ text, const int* __restrict__ row_off, long rows, int ctx,
                                                         int vocab, int* __restrict__ cursor, int* __restrict__ bucket) {
@@ -363,39 +412,31 @@ __global__ __launch_bounds__(256) void tokd_fill_kernel(const int* __restrict__ 
         if (tokd_row(text, row_off, r, ctx, vocab, &id, &dxr)) bucket[atomicAdd(cursor + id, 1)] = (int)dxr;
     }
 }
-// one workgroup per (token id, 256-column slab): the id's bucket in ascending row order (bitonic sort in LDS), then its rows added in
-// that order -- four contiguous quarters of the bucket in parallel (eight 16-byte loads in flight per thread), the four quarter sums
-// added in order: one fixed summation tree per element
-__global__ __launch_bounds__(256) void tokd_accum_kernel(const int* __restrict__ starts, const int* __restrict__ bucket,
-                                                         const float* __restrict__ dx, float* __restrict__ dtok, int w) {
-    __shared__ int srt[TOKD_SORT];
-    __shared__ f32x4_t red[4][64];
-    const int id = blockIdx.x, tid = threadIdx.x;
-    const int b0 = starts[id], cnt = starts[id + 1] - b0;
-    if (cnt == 0) return;
-    const int* rows = bucket + b0;
-    const bool sorted = cnt <= TOKD_SORT;
-    if (sorted && cnt > 1) {
-        int np = 2;
-        while (np < cnt) np <<= 1;
-        for (int i = tid; i < np; i += 256) srt[i] = i < cnt ? rows[i] : 0x7fffffff;
-        __syncthreads();
-        for (int k = 2; k <= np; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < np; i += 256) {
-                    const int l = i ^ j;
-                    if (l > i) {
-                        const int a = srt[i], b = srt[l];
-                        const bool up = (i & k) == 0;
-                        if ((a > b) == up) { srt[i] = b; srt[l] = a; }
-                    }
+// srt[0 .. cnt) -> ascending (bitonic sort in LDS, the tail padded with INT_MAX); all 256 threads
+DEVINL void tokd_sort(int* srt, int cnt, int tid) {
+    if (cnt <= 1) return;
+    int np = 2;
+    while (np < cnt) np <<= 1;
+    for (int i = cnt + tid; i < np; i += 256) srt[i] = 0x7fffffff;
+    __syncthreads();
+    for (int k = 2; k <= np; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < np; i += 256) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const int a = srt[i], b = srt[l];
+                    const bool up = (i & k) == 0;
+                    if ((a > b) == up) { srt[i] = b; srt[l] = a; }
                 }
-                __syncthreads();
             }
-        rows = nullptr;
-    }
-    auto row_at = [&](int i) { return (sorted && cnt > 1) ? srt[i] : bucket[b0 + i]; };
-    const int cg = tid & 63, q = tid >> 6, col = blockIdx.y * 256 + cg * 4;
+            __syncthreads();
+        }
+}
+// the dx rows srt[0 .. cnt) added in that order -- four contiguous quarters in parallel (eight 16-byte loads in flight per thread), the
+// four quarter sums added in order: one fixed summation tree per element.  The sum of columns col .. col + 3 is returned to the
+// threads of quarter 0 (tid < 64); all 256 threads
+DEVINL f32x4_t tokd_sum(const int* srt, int cnt, const float* __restrict__ dx, int w, int col, int tid, f32x4_t (*red)[64]) {
+    const int cg = tid & 63, q = tid >> 6;
     const int per = (cnt + 3) / 4, i0 = q * per, i1 = min(cnt, i0 + per);
     f32x4_t s = {0.f, 0.f, 0.f, 0.f};
     if (col < w) {
@@ -403,34 +444,103 @@ __global__ __launch_bounds__(256) void tokd_accum_kernel(const int* __restrict__
         for (; i + 8 <= i1; i += 8) {
             f32x4_t v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4_t*>(dx + (long)row_at(i + u) * w + col);
+            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4_t*>(dx + (long)srt[i + u] * w + col);
 #pragma unroll
             for (int u = 0; u < 8; ++u) s += v[u];
         }
-        for (; i < i1; ++i) s += *reinterpret_cast<const f32x4_t*>(dx + (long)row_at(i) * w + col);
+        for (; i < i1; ++i) s += *reinterpret_cast<const f32x4_t*>(dx + (long)srt[i] * w + col);
     }
     red[q][cg] = s;
     __syncthreads();
-    if (q == 0 && col < w) {
-        const f32x4_t t = ((red[0][cg] + red[1][cg]) + red[2][cg]) + red[3][cg];
+    return ((red[0][cg] + red[1][cg]) + red[2][cg]) + red[3][cg];
+}
+// one workgroup per (token id, 256-column slab): the id's bucket in ascending row order, then its rows added in that order.  Ids with
+// more than TOKD_SORT rows are tokd_long_kernel's.
+__global__ __launch_bounds__(256) void tokd_accum_kernel(const int* __restrict__ starts, const int* __restrict__ bucket,
+                                                         const float* __restrict__ dx, float* __restrict__ dtok, int w) {
+    __shared__ int srt[TOKD_SORT];
+    __shared__ f32x4_t red[4][64];
+    const int id = blockIdx.x, tid = threadIdx.x;
+    const int b0 = starts[id], cnt = starts[id + 1] - b0;
+    if (cnt == 0 || cnt > TOKD_SORT) return;
+    for (int i = tid; i < cnt; i += 256) srt[i] = bucket[b0 + i];
+    if (cnt == 1) __syncthreads();
+    tokd_sort(srt, cnt, tid);
+    const int col = blockIdx.y * 256 + (tid & 63) * 4;
+    const f32x4_t t = tokd_sum(srt, cnt, dx, w, col, tid, red);
+    if (tid < 64 && col < w) {
         f32x4_t* o = reinterpret_cast<f32x4_t*>(dtok + (long)id * w + col);
         *o = *o + t;
     }
+}
+// grid (TOKD_KCAP, slices, slabs): long id number k0 + blockIdx.x, the rows of slice blockIdx.y -> part[blockIdx.x][slice][w]
+__global__ __launch_bounds__(256) void tokd_long_kernel(const int* __restrict__ starts, const int* __restrict__ bucket,
+                                                        const int* __restrict__ longs, int k0, const float* __restrict__ dx,
+                                                        float* __restrict__ part, int w) {
+    __shared__ int srt[TOKD_SORT];
+    __shared__ f32x4_t red[4][64];
+    __shared__ int nsel;
+    const int k = k0 + blockIdx.x, tid = threadIdx.x;
+    if (k >= longs[0]) return;
+    const int id = longs[1 + k];
+    const int b0 = starts[id], cnt = starts[id + 1] - b0;
+    const int lo = blockIdx.y * TOKD_SORT, hi = lo + TOKD_SORT;
+    if (tid == 0) nsel = 0;
+    __syncthreads();
+    for (int i = tid; i < cnt; i += 256) {
+        const int r = bucket[b0 + i];
+        if (r >= lo && r < hi) {
+            const int at = atomicAdd(&nsel, 1);      // any order: sorted below (rows are unique, so at < TOKD_SORT; checked all the same)
+            if (at < TOKD_SORT) srt[at] = r;
+        }
+    }
+    __syncthreads();
+    const int sel = min(nsel, TOKD_SORT);
+    tokd_sort(srt, sel, tid);
+    const int col = blockIdx.z * 256 + (tid & 63) * 4;
+    const f32x4_t t = tokd_sum(srt, sel, dx, w, col, tid, red);
+    if (tid < 64 && col < w)
+        *reinterpret_cast<f32x4_t*>(part + ((long)blockIdx.x * gridDim.y + blockIdx.y) * w + col) = t;
+}
+// grid (TOKD_KCAP, slabs) x 64 threads: dtok[long id] += its slices' partials in slice order
+__global__ __launch_bounds__(64) void tokd_long_reduce_kernel(const int* __restrict__ longs, int k0, const float* __restrict__ part,
+                                                              int nslices, float* __restrict__ dtok, int w) {
+    const int k = k0 + blockIdx.x, col = blockIdx.y * 256 + threadIdx.x * 4;
+    if (k >= longs[0] || col >= w) return;
+    f32x4_t s = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < nslices; ++j) s += *reinterpret_cast<const f32x4_t*>(part + ((long)blockIdx.x * nslices + j) * w + col);
+    f32x4_t* o = reinterpret_cast<f32x4_t*>(dtok + (long)longs[1 + k] * w + col);
+    *o = *o + s;
 }
 // the bucketed form when the stream has a scratch buffer: 1 = done, 0 = not applicable (the caller runs the atomic kernel), < 0 = a
 // launch failed (nothing may be added a second time)
 static int tokd_run(const int* text, const float* dx, const int* row_off, float* dtok, int n, int ctx, int w, int vocab, hipStream_t st) {
     const long rows = (long)n * ctx;
-    if (rows >= 0x7fffffffL || vocab > 1024 * TOKD_PER || (w & 3) || (((uintptr_t)dx | (uintptr_t)dtok) & 15)) return 0;
-    int* ws = (int*)reduce_scratch(st, (int64_t)(3L * vocab + 4 + rows) * 4);
+    // (a grid dimension holds 65535 slices of TOKD_SORT rows)
+    if (rows > 65535L * TOKD_SORT || vocab > 1024 * TOKD_PER || (w & 3) || (((uintptr_t)dx | (uintptr_t)dtok) & 15)) {
+        reduce_lapse();
+        return 0;
+    }
+    // at most kmax ids can have more than TOKD_SORT rows; their partials follow the integer tables at the next 16-byte boundary
+    const int kmax = (int)(rows / (TOKD_SORT + 1)), nslices = (int)((rows + TOKD_SORT - 1) / TOKD_SORT);
+    const int64_t nint = (3L * vocab + 4 + rows + (kmax ? 1 + kmax : 0) + 3) & ~3L;
+    const int64_t npart = kmax ? (int64_t)TOKD_KCAP * nslices * w : 0;
+    int* ws = (int*)reduce_scratch(st, (nint + npart) * 4);
     if (!ws) return 0;
     int *counts = ws, *starts = ws + vocab + 1, *cursor = starts + vocab + 1, *bucket = cursor + vocab + 1;
+    int* longs = ws + 3L * vocab + 4 + rows;
+    float* part = (float*)(ws + nint);
     if (hipMemsetAsync(counts, 0, (size_t)(vocab + 1) * 4, st) != hipSuccess) return UNIIR_ELAUNCH;
     const int g = grid_for(rows, 256, 4096);
     hipLaunchKernelGGL(tokd_count_kernel, dim3(g), dim3(256), 0, st, text, row_off, rows, ctx, vocab, counts);
-    hipLaunchKernelGGL(tokd_scan_kernel, dim3(1), dim3(1024), 0, st, counts, starts, cursor, vocab);
+    hipLaunchKernelGGL(tokd_scan_kernel, dim3(1), dim3(1024), 0, st, counts, starts, cursor, vocab, longs, kmax);
     hipLaunchKernelGGL(tokd_fill_kernel, dim3(g), dim3(256), 0, st, text, row_off, rows, ctx, vocab, cursor, bucket);
     hipLaunchKernelGGL(tokd_accum_kernel, dim3(vocab, (w + 255) / 256), dim3(256), 0, st, starts, bucket, dx, dtok, w);
+    for (int k0 = 0; k0 < kmax; k0 += TOKD_KCAP) {
+        hipLaunchKernelGGL(tokd_long_kernel, dim3(TOKD_KCAP, nslices, (w + 255) / 256), dim3(256), 0, st, starts, bucket, longs, k0, dx,
+                           part, w);
+        hipLaunchKernelGGL(tokd_long_reduce_kernel, dim3(TOKD_KCAP, (w + 255) / 256), dim3(64), 0, st, longs, k0, part, nslices, dtok, w);
+    }
     return hipGetLastError() == hipSuccess ? 1 : UNIIR_ELAUNCH;
 }
 
@@ -860,8 +970,15 @@ extern "C" int uniir_select_normalize(const float* emb, const int32_t* idx, floa
     HIP_LAUNCH_CHECK();
     return UNIIR_OK;
 }
-// bwd of y = x/||x||: dx = (dy - y <y,dy>) / ||x||; scattered (+=) to demb[idx[i]] with atomics (an item may
-// be selected more than once, e.g. as hard negative of several queries).
+// bwd of y = x/||x||: dx = (dy - y <y,dy>) / ||x||, added (+=) to demb[idx[i]].  An item may be selected more than once (e.g. as hard
+// negative of several queries), so a destination row can have several source rows.  Each destination has ONE writer: the wave of the
+// FIRST source row that selects it adds the contributions of all its source rows in ascending row order in registers and does one
+// plain += (the waves of the later source rows find an earlier one and leave).  The number of destinations is not an argument, so
+// the rows are matched by scanning idx: O(rows^2 / 64) integer compares per wave, nothing at the b * (1 + N) rows of a batch.
+// Without idx every row is its own destination: one pass, no scan.  The form assumes FEW source rows per destination, as in a batch
+// (a candidate that is the negative of two or three queries): the rows of one destination are walked by one wave, one after the
+// other, and their dot products are taken again for every sweep of 1024 columns.
+#define SELN_MAXC 16          // columns per lane held in registers: dim <= 1024 in one sweep, wider rows in sweeps of 1024 columns
 __global__ __launch_bounds__(256) void select_norm_bwd_kernel(const float* __restrict__ y,
                                                               const float* __restrict__ inv,
                                                               const float* __restrict__ dy,
@@ -870,14 +987,50 @@ __global__ __launch_bounds__(256) void select_norm_bwd_kernel(const float* __res
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
-    const float* yr = y + (long)r * dim;
-    const float* dr = dy + (long)r * dim;
-    float s = 0.f;
-    for (int c = lane; c < dim; c += 64) s += yr[c] * dr[c];
-    s = wave_sum(s);
-    const float iv = inv[r];
-    float* dst = demb + (long)(idx ? idx[r] : r) * dim;
-    for (int c = lane; c < dim; c += 64) unsafeAtomicAdd(dst + c, (dr[c] - yr[c] * s) * iv);
+    if (!idx) {
+        const float* yr = y + (long)r * dim;
+        const float* dr = dy + (long)r * dim;
+        float s = 0.f;
+        for (int c = lane; c < dim; c += 64) s += yr[c] * dr[c];
+        s = wave_sum(s);
+        const float iv = inv[r];
+        float* dst = demb + (long)r * dim;
+        for (int c = lane; c < dim; c += 64) dst[c] += (dr[c] - yr[c] * s) * iv;
+        return;
+    }
+    const int d = idx[r];
+    bool earlier = false;
+    for (int j = lane; j < r; j += 64) earlier |= idx[j] == d;
+    if (__any(earlier)) return;
+    float* dst = demb + (long)d * dim;
+    for (int c0 = 0; c0 < dim; c0 += 64 * SELN_MAXC) {
+        float acc[SELN_MAXC];
+#pragma unroll
+        for (int u = 0; u < SELN_MAXC; ++u) acc[u] = 0.f;
+        for (int base = r; base < rows; base += 64) {
+            unsigned long long m = __ballot(base + lane < rows && idx[min(base + lane, rows - 1)] == d);
+            while (m) {          // the source rows of this destination, ascending (wave-uniform loop)
+                const int r2 = base + __builtin_ctzll(m);
+                m &= m - 1;
+                const float* yr = y + (long)r2 * dim;
+                const float* dr = dy + (long)r2 * dim;
+                float s = 0.f;
+                for (int c = lane; c < dim; c += 64) s += yr[c] * dr[c];
+                s = wave_sum(s);
+                const float iv = inv[r2];
+#pragma unroll
+                for (int u = 0; u < SELN_MAXC; ++u) {
+                    const int c = c0 + u * 64 + lane;
+                    if (c < dim) acc[u] += (dr[c] - yr[c] * s) * iv;
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < SELN_MAXC; ++u) {
+            const int c = c0 + u * 64 + lane;
+            if (c < dim) dst[c] += acc[u];
+        }
+    }
 }
 extern "C" int uniir_select_normalize_bwd(const float* out, const float* inv_norm, const float* dout,
                                           const int32_t* idx, float* demb, int32_t rows, int32_t dim,

@@ -479,37 +479,57 @@ __global__ __launch_bounds__(256) void hardneg_fwd_kernel(const float* __restric
     }
 }
 
-// dq [b][dim] (written), dn [b*N][dim] (written), dp [b][dim] and dscale (ACCUMULATED with atomics: zero them first)
+// dq [b][dim] (written), dn [b*N][dim] (written), dp [b][dim] (ACCUMULATED: zero it first).  Nothing here depends on arrival order:
+// dp[i][e] has a single writer -- only thread e % 256 of block i touches it (the in-batch entries of row i are p_i itself, see above),
+// adding its 1 + I terms in ascending c -- so its += is a plain read-modify-write.  dscale is hardneg_dscale_kernel's.
 __global__ __launch_bounds__(256) void hardneg_bwd_kernel(const float* __restrict__ q, const float* __restrict__ p,
                                                           const float* __restrict__ n, const float* __restrict__ scale,
                                                           const float* __restrict__ logits, const float* __restrict__ row_lse,
                                                           const float* __restrict__ dloss, int b, int N, int I, int dim,
                                                           float* __restrict__ dq, float* __restrict__ dp,
-                                                          float* __restrict__ dn, float* __restrict__ dscale) {
-    __shared__ float red[4];
-    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+                                                          float* __restrict__ dn) {
+    const int i = blockIdx.x, tid = threadIdx.x;
     const int C = 1 + N + I;
     const float s = *scale, g = *dloss / (float)b, lse = row_lse[i];
     const float* qi = q + (long)i * dim;
     const float* lrow = logits + (long)i * C;
-    float ds = 0.f;
-    for (int c = tid; c < C; c += 256) ds += (expf(lrow[c] - lse) - (c == 0 ? 1.f : 0.f)) * g * lrow[c];
-    ds = wave_sum(ds);
-    if (lane == 0) red[w] = ds;
-    __syncthreads();
-    if (tid == 0) atomicAdd(dscale, ((red[0] + red[1]) + (red[2] + red[3])) / s);
     for (int e = tid; e < dim; e += 256) {
         const float qe = qi[e];
-        float acc = 0.f;
+        float acc = 0.f, dpe = dp[(long)i * dim + e];
         for (int c = 0; c < C; ++c) {
             const float dl = (expf(lrow[c] - lse) - (c == 0 ? 1.f : 0.f)) * g * s;   // d loss / d <q, v_c>
             const float* v = hn_vec(p, n, i, c, N, dim);
             acc = fmaf(dl, v[e], acc);
             if (c >= 1 && c <= N) dn[((long)i * N + (c - 1)) * dim + e] = dl * qe;
-            else atomicAdd(dp + (v - p) + e, dl * qe);
+            else dpe += __fmul_rn(dl, qe);      // the product rounded on its own, as when it went through an atomic add
         }
         dq[(long)i * dim + e] = acc;
+        dp[(long)i * dim + e] = dpe;
     }
+}
+// dscale += sum_i sum_c d loss / d logit[i][c] * logit[i][c] / scale, in ONE fixed order (one float atomic per query block landed
+// in arrival order before): thread t recomputes the terms of rows t, t + 256, ... from logits / row_lse (C = 1 + N + I is small), adds
+// each row's terms in ascending c and its rows in ascending i; the 256 thread sums go through the tree of nce_dscale_kernel.
+__global__ __launch_bounds__(256) void hardneg_dscale_kernel(const float* __restrict__ scale, const float* __restrict__ logits,
+                                                             const float* __restrict__ row_lse, const float* __restrict__ dloss,
+                                                             int b, int C, float* __restrict__ dscale) {
+    __shared__ float part[256];
+    const float g = *dloss / (float)b;
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < b; i += 256) {
+        const float* lrow = logits + (long)i * C;
+        const float lse = row_lse[i];
+        float ds = 0.f;
+        for (int c = 0; c < C; ++c) ds += (expf(lrow[c] - lse) - (c == 0 ? 1.f : 0.f)) * g * lrow[c];
+        acc += ds;
+    }
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) dscale[0] += part[0] / scale[0];
 }
 
 extern "C" int uniir_hardneg_fwd(const float* q, const float* p, const float* n, const float* scale, int32_t b, int32_t N,
@@ -530,7 +550,9 @@ extern "C" int uniir_hardneg_bwd(const float* q, const float* p, const float* n,
         return UNIIR_EINVAL;
     if (b <= 0 || N < 0 || I < 0 || I > b - 1 || dim <= 0) return UNIIR_EINVAL;
     hipLaunchKernelGGL(hardneg_bwd_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, q, p, n, scale, logits, row_lse, dloss,
-                       b, N, I, dim, dq, dp, dn, dscale);
+                       b, N, I, dim, dq, dp, dn);
+    hipLaunchKernelGGL(hardneg_dscale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scale, logits, row_lse, dloss, b,
+                       1 + N + I, dscale);
     HIP_LAUNCH_CHECK();
     return UNIIR_OK;
 }

@@ -3,6 +3,7 @@ plumbing here: every function passes raw device pointers + the current HIP strea
 There is no torch fallback: a CPU tensor raises."""
 import ctypes as C
 import os
+import warnings
 
 import torch
 
@@ -52,28 +53,77 @@ def gemm_timing_filter(windows, samples, merge_ms=-1.0):
 
 
 # Reproducible reductions (include/uniir_hip.h uniir_reduce_scratch): every stream this module launches on gets a scratch buffer, so
-# that bias / LayerNorm / embedding gradients are added in a fixed order and two runs of one step give the same bits.
-# UNIIR_DETERMINISTIC=0 leaves the kernels on their fp32 atomics (A/B of the extra reduce launches).
+# that bias / LayerNorm / embedding / relative-position-bias gradients are added in a fixed order and two runs of one step give the
+# same bits.  A reduction that asks for more than the buffer holds keeps its atomics for that launch and the library counts it
+# (reduce_stats); the next launch on the stream finds the request in the library's max_request and grows the buffer, so at most the
+# first step of a new geometry is added in arrival order, and the counter says when that was.
+# UNIIR_DETERMINISTIC=0 registers no scratch: the kernels stay on their fp32 atomics (A/B of the extra reduce launches) and the
+# counter simply counts.
 RED_SCRATCH_BYTES = 64 << 20
 _RED_SCRATCH = {}
 _DETERMINISTIC = os.environ.get("UNIIR_DETERMINISTIC", "1") != "0"
+_RED_REFUSED = {}          # (device, stream) -> the smallest size whose allocation failed: not tried again
+# max_request is read before every launch, so the read is kept cheap: one word and one bound function for the module.  Python threads
+# share the word, which is harmless: it holds a process-wide figure that only grows between resets, whoever read it last.
+_RED_MAX = C.c_int64()
+_RED_MAX_REF = C.byref(_RED_MAX)
+_RED_STATS = None
+
+
+def reduce_stats():
+    """-> (fallbacks, max_request) of the process since the last reset: reduction launches that were added in arrival order (fp32
+    atomics) because their stream had no scratch buffer or too small a one, and the largest scratch size any reduction asked for
+    (bytes)"""
+    f, m = C.c_int64(), C.c_int64()
+    check(_lib.load().uniir_reduce_stats(C.byref(f), C.byref(m), 0), "reduce_stats")
+    return f.value, m.value
+
+
+def reset_reduce_stats():
+    check(_lib.load().uniir_reduce_stats(None, None, 1), "reduce_stats")
+
+
+def _register_scratch(s, nbytes):
+    with torch.cuda.device(s.device), torch.cuda.stream(s):      # allocated ON the stream: the caching allocator hands the old
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=s.device)      # buffer's memory to later work of this stream only
+        check(_lib.load().uniir_reduce_scratch(C.c_void_p(buf.data_ptr()), nbytes, C.c_void_p(s.cuda_stream)), "reduce_scratch")
+    return buf
 
 
 def _stream():
     s = torch.cuda.current_stream()
     if _DETERMINISTIC:
         key = (s.device.index, s.cuda_stream)
-        if key not in _RED_SCRATCH:
+        buf = _RED_SCRATCH.get(key)
+        if buf is None:
             if len(_RED_SCRATCH) >= 24:          # streams come and go (tests): forget the oldest entry -- in the library's table
                 old = next(iter(_RED_SCRATCH))   # first, so that it never points at freed memory
                 with torch.cuda.device(old[0]):
                     _lib.load().uniir_reduce_scratch(None, 0, C.c_void_p(old[1]))
                 del _RED_SCRATCH[old]
-            with torch.cuda.device(s.device):
-                buf = torch.empty(RED_SCRATCH_BYTES, dtype=torch.uint8, device=s.device)
-                check(_lib.load().uniir_reduce_scratch(C.c_void_p(buf.data_ptr()), RED_SCRATCH_BYTES, C.c_void_p(s.cuda_stream)),
-                      "reduce_scratch")
-            _RED_SCRATCH[key] = buf
+                _RED_REFUSED.pop(old, None)
+            buf = _RED_SCRATCH[key] = _register_scratch(s, RED_SCRATCH_BYTES)
+        global _RED_STATS
+        if _RED_STATS is None:
+            _RED_STATS = _lib.load().uniir_reduce_stats
+        _RED_STATS(None, _RED_MAX_REF, 0)
+        need = _RED_MAX
+        if need.value > buf.numel():             # some reduction did not fit (and kept its atomics): the next power of two
+            nbytes = 1 << (need.value - 1).bit_length()
+            if nbytes < _RED_REFUSED.get(key, nbytes + 1):
+                try:
+                    new = _register_scratch(s, nbytes)
+                except torch.cuda.OutOfMemoryError:
+                    # the old buffer stays registered; reductions of that size keep their atomics and stay counted
+                    _RED_REFUSED[key] = nbytes
+                    warnings.warn(f"uniir_amd: a reduction asked for {need.value} bytes of scratch, but {nbytes} bytes could not be "
+                                  f"allocated for stream {s.cuda_stream:#x}; it stays in arrival order (ops.reduce_stats())",
+                                  RuntimeWarning, stacklevel=3)
+                else:
+                    warnings.warn(f"uniir_amd: a reduction asked for {need.value} bytes of scratch; the buffer of stream "
+                                  f"{s.cuda_stream:#x} grows from {buf.numel()} to {nbytes} bytes (launches before this one were "
+                                  "added in arrival order, see ops.reduce_stats())", RuntimeWarning, stacklevel=3)
+                    _RED_SCRATCH[key] = new
     return C.c_void_p(s.cuda_stream)
 
 
