@@ -599,6 +599,59 @@ int uniir_image_preprocess(const void* rgb_u8, int32_t h, int32_t w, int32_t oh,
                            int32_t n, const float* mean3, const float* std3, float* out, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* Batched form: one table of per-image geometry, a constant number of launches per batch (three kernels, whatever `count`).
+ * All images sit in ONE packed uint8 buffer; image i is RGB [h][w][3] at byte `offset` (a multiple of 16).  Per image:
+ *   crop the source box (box_left, box_top, box_w, box_h) -> PIL resize of the BOX to (oh, ow) with BICUBIC -> rows
+ *   [top, top+n) x columns [left, left+n) of the resized box -> mirror the n kept columns when flip -> x / 255 ->
+ *   (v - mean[c]) / std[c] -> out[out_index] fp32 [3][n][n].
+ * This is Pillow's image.crop(box).resize((ow, oh), BICUBIC): the resample windows are clamped at the BOX edges, never
+ * reading pixels outside it (Image.resize(box=...) does read them and gives other bytes).  A pass is skipped when its
+ * axis keeps its size (box_w == ow / box_h == oh), as Pillow and uniir_image_preprocess do.  Both older chains are
+ * special cases: CLIP = whole-image box + Resize / CenterCrop geometry, flip 0; BLIP eval = whole-image box, oh = ow = n;
+ * BLIP train = the RandomResizedCrop box, oh = ow = n, the drawn flip.
+ *
+ * uniir_image_batch_plan is HOST-ONLY arithmetic (no HIP call): it validates the host copy of the table, fills one
+ * uniir_image_plan per image and the batch summary.  Errors: null pointers, non-positive sizes, a flip other than 0 / 1, an
+ * offset that is negative or no multiple of 16, out_index outside [0, out_items), two descriptors with one out_index ->
+ * UNIIR_EINVAL; box outside the image, window outside (oh, ow), image bytes outside [0, packed_bytes) -> UNIIR_ESHAPE; a
+ * box whose touched row segment exceeds the staging buffer of the horizontal pass (16384 pixels) -> UNIIR_EUNSUPPORTED.
+ * count == 0 is valid (workspace_bytes 0).
+ *
+ * uniir_image_preprocess_batch takes DEVICE copies of the pixels and of both tables, and the HOST summary `info` of the plan
+ * call that produced the plan table; it trusts them.  It checks only its own arguments: null pointers, workspace smaller
+ * than info->workspace_bytes or not 256-byte aligned -> UNIIR_EINVAL.  It allocates nothing, copies nothing and never
+ * synchronises; slots of `out` that no descriptor names are left untouched; info->count == 0 returns UNIIR_OK without a
+ * launch.  mean3 / std3 are HOST pointers to 3 floats. */
+typedef struct uniir_image_desc {
+    int64_t offset;                             /* byte offset of the image in the packed buffer, multiple of 16 */
+    int32_t h, w;                               /* image size */
+    int32_t box_left, box_top, box_w, box_h;    /* source box inside the image */
+    int32_t oh, ow;                             /* size the box is resized to */
+    int32_t top, left;                          /* n x n window inside (oh, ow) */
+    int32_t flip;                               /* 1: mirror the kept columns */
+    int32_t out_index;                          /* [3][n][n] slot of `out` */
+} uniir_image_desc;
+typedef struct uniir_image_plan {
+    int64_t bx_off, by_off;     /* workspace byte offsets: (first, count) window bounds per kept column / row, int32 [n][2] */
+    int64_t cx_off, cy_off;     /* 22-bit fixed-point weights, int32 [n][kx] / [n][ky] */
+    int64_t tmp_off;            /* horizontal-pass result, uint8 [rows][n][3] */
+    int32_t kx, ky;             /* window capacity per axis (Pillow's ksize); 0 for a skipped pass */
+    int32_t y0, rows;           /* box rows [y0, y0 + rows) that the vertical windows of the kept rows touch */
+    int32_t x0, cols;           /* box columns [x0, x0 + cols) that the horizontal windows of the kept columns touch */
+} uniir_image_plan;
+typedef struct uniir_image_batch_info {
+    int64_t workspace_bytes;    /* what uniir_image_preprocess_batch needs, 256-byte aligned */
+    int32_t count, n, out_items;
+    int32_t max_rows;           /* largest plan.rows: the row extent of the horizontal pass's grid */
+    int32_t launches;           /* kernel launches of the batched call for this batch: the same for every count >= 1 */
+    int32_t reserved;
+} uniir_image_batch_info;
+int uniir_image_batch_plan(const uniir_image_desc* descs, int32_t count, int32_t n, int32_t out_items, int64_t packed_bytes,
+                           uniir_image_plan* plans, uniir_image_batch_info* info);
+int uniir_image_preprocess_batch(const void* packed_u8, const uniir_image_desc* descs, const uniir_image_plan* plans,
+                                 const uniir_image_batch_info* info, const float* mean3, const float* std3, float* out,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

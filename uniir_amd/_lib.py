@@ -51,6 +51,25 @@ class ClipTower(C.Structure):
     ]
 
 
+class ImageDesc(C.Structure):
+    """uniir_image_desc (include/uniir_hip.h [IMAGE]): per-image geometry of the batched device transform"""
+    _fields_ = [("offset", c_i64), ("h", c_int), ("w", c_int),
+                ("box_left", c_int), ("box_top", c_int), ("box_w", c_int), ("box_h", c_int),
+                ("oh", c_int), ("ow", c_int), ("top", c_int), ("left", c_int), ("flip", c_int), ("out_index", c_int)]
+
+
+class ImagePlan(C.Structure):
+    """uniir_image_plan: what uniir_image_batch_plan derives per image (workspace offsets, window capacities, touched source range)"""
+    _fields_ = [("bx_off", c_i64), ("by_off", c_i64), ("cx_off", c_i64), ("cy_off", c_i64), ("tmp_off", c_i64),
+                ("kx", c_int), ("ky", c_int), ("y0", c_int), ("rows", c_int), ("x0", c_int), ("cols", c_int)]
+
+
+class ImageBatchInfo(C.Structure):
+    """uniir_image_batch_info: the plan call's summary of one batch (host side)"""
+    _fields_ = [("workspace_bytes", c_i64), ("count", c_int), ("n", c_int), ("out_items", c_int), ("max_rows", c_int),
+                ("launches", c_int), ("reserved", c_int)]
+
+
 # name -> (restype, argtypes); P = device pointer, S = stream
 P, S = c_void_p, c_void_p
 SIGNATURES = {
@@ -133,6 +152,9 @@ SIGNATURES = {
     "uniir_topk_ncand": (c_int, [c_int, c_int]),
     "uniir_image_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int, c_int]),
     "uniir_image_preprocess": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_i64, S]),
+    "uniir_image_batch_plan": (c_int, [C.POINTER(ImageDesc), c_int, c_int, c_int, c_i64, C.POINTER(ImagePlan),
+                                       C.POINTER(ImageBatchInfo)]),
+    "uniir_image_preprocess_batch": (c_int, [P, P, P, C.POINTER(ImageBatchInfo), P, P, P, P, c_i64, S]),
     "uniir_topk_coarse": (c_int, [P, P, c_i64, c_int, P, c_int, c_int, P, P, P, c_i64, S]),
     "uniir_topk_rescore": (c_int, [P, P, P, c_i64, c_int, P, P, c_int, P, c_int, c_int, P, P, P, S]),
     "uniir_topk_merge": (c_int, [P, P, c_int, c_int, c_int, P, P, S]),

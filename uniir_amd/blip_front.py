@@ -73,6 +73,44 @@ def get_blip_transform(image_size, min_scale=0.5, is_train=True):
     return train_fn if is_train else eval_fn
 
 
+class RawBlipTransform:
+    """Drop-in `img_preprocess_fn` that defers get_blip_transform's work to the GPU (clip_front.RawImageBatch ->
+    uniir_image_preprocess_batch): the worker only decodes to uint8 and, in train mode, draws the RandomResizedCrop box and
+    the flip from `random` with exactly the calls, order and count of train_fn above (the fallback box after ten failed tries
+    included), so the same `random` state going in gives the same tensor, bit for bit, and the same state afterwards.  Eval
+    mode draws nothing and uses the whole image."""
+    center_crop = False          # Resize((n, n)) of the box, no crop window
+    mean, std = _MEAN, _STD
+
+    def __init__(self, image_size, min_scale=0.5, is_train=True):
+        self.n_px = self.image_size = image_size
+        self.min_scale, self.is_train = min_scale, is_train
+
+    def draw(self, w, h):
+        """-> (left, top, box_w, box_h, flip) for a w x h image"""
+        area = w * h
+        box = None
+        for _ in range(10):
+            target = area * random.uniform(self.min_scale, 1.0)
+            ratio = math.exp(random.uniform(math.log(3 / 4), math.log(4 / 3)))
+            cw, ch = int(round(math.sqrt(target * ratio))), int(round(math.sqrt(target / ratio)))
+            if 0 < cw <= w and 0 < ch <= h:
+                top, left = random.randint(0, h - ch), random.randint(0, w - cw)
+                box = (left, top, cw, ch)
+                break
+        if box is None:
+            r = w / h
+            cw, ch = (w, int(round(w / (3 / 4)))) if r < 3 / 4 else ((int(round(h * (4 / 3))), h) if r > 4 / 3 else (w, h))
+            box = ((w - cw) // 2, (h - ch) // 2, cw, ch)
+        return box + (int(random.random() < 0.5),)
+
+    def __call__(self, image):
+        from .clip_front import RawImage
+        data = torch.from_numpy(np.array(image.convert("RGB"), dtype=np.uint8))
+        w, h = image.size
+        return RawImage(data, self.draw(w, h) if self.is_train else None)
+
+
 def interpolate_pos_embed(pos_embed_checkpoint, num_patches, num_extra_tokens=1):
     """[1, 1+g0*g0, D] -> [1, 1+g*g, D]: class token kept, grid resized bicubically (align_corners False)"""
     D = pos_embed_checkpoint.shape[-1]

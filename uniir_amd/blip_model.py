@@ -631,8 +631,12 @@ class BLIPFeatureFusion(nn.Module):
         return k
 
     # ---- reference surface ---------------------------------------------------------------------------------
-    def get_img_preprocess_fn(self):
-        from .blip_front import get_blip_transform
+    def get_img_preprocess_fn(self, raw=False):
+        """raw=True: the deferred form of the same transform (blip_front.RawBlipTransform) -- the workers decode and draw the
+        crop box / flip, the batched device transform does the rest; also set it as the collator's `raw_transform`"""
+        from .blip_front import RawBlipTransform, get_blip_transform
+        if raw:
+            return RawBlipTransform(self.image_size, min_scale=0.5, is_train=self.training)
         return get_blip_transform(self.image_size, min_scale=0.5, is_train=self.training)
 
     def get_tokenizer(self):

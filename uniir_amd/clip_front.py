@@ -79,18 +79,113 @@ def preprocess_on_device(images, n_px, device, mean=_MEAN, std=_STD, center_crop
     return out
 
 
-class RawImage:
-    """a decoded RGB image waiting for the device transform (uint8 [h, w, 3], shareable between loader workers)"""
-    __slots__ = ("data",)
+class PackedImages:
+    """A batch of decoded images ready for ONE host -> device copy and ONE call of uniir_image_preprocess_batch: a single
+    uint8 host buffer holding [descriptor table | plan table | pixels, every image 16-byte aligned] (include/uniir_hip.h
+    [IMAGE]).  `geoms[i]` = (box_left, box_top, box_w, box_h, oh, ow, top, left, flip) of image i, or None for the CLIP
+    chain on the whole image; `out_index[i]` = the output slot it lands in (default i).  The plan call validates the table
+    on the host: a malformed descriptor raises here, before anything reaches the device."""
 
-    def __init__(self, data):
-        self.data = data
+    def __init__(self, images, geoms, n_px, out_index=None, out_items=None, pin=False):
+        import ctypes
+
+        from . import _lib
+        lib = _lib.load()
+        count = len(images)
+        geoms = [None] * count if geoms is None else list(geoms)
+        out_index = list(range(count)) if out_index is None else [int(i) for i in out_index]
+        if len(geoms) != count or len(out_index) != count:
+            raise ValueError("images, geoms and out_index must have one entry per image")
+        self.count, self.n_px = count, int(n_px)
+        self.out_items = int(out_items) if out_items is not None else (max(out_index) + 1 if out_index else 0)
+        arrays, descs, off = [], (_lib.ImageDesc * max(count, 1))(), 0
+        for i, img in enumerate(images):
+            if isinstance(img, torch.Tensor):
+                if img.is_cuda:
+                    raise ValueError("PackedImages packs host images")
+                a = img.contiguous().numpy()
+            elif isinstance(img, np.ndarray):
+                a = np.ascontiguousarray(img)
+            else:
+                a = np.asarray(img.convert("RGB"), dtype=np.uint8)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("images must be RGB uint8 [h, w, 3]")
+            h, w = int(a.shape[0]), int(a.shape[1])
+            g = geoms[i]
+            if g is None:
+                oh, ow, top, left = resize_geometry(h, w, n_px)
+                g = (0, 0, w, h, oh, ow, top, left, 0)
+            d = descs[i]
+            d.offset, d.h, d.w = off, h, w
+            d.box_left, d.box_top, d.box_w, d.box_h, d.oh, d.ow, d.top, d.left, d.flip = (int(v) for v in g)
+            d.out_index = out_index[i]
+            arrays.append(a)
+            off += (a.size + 15) & ~15
+        plans, self.info = (_lib.ImagePlan * max(count, 1))(), _lib.ImageBatchInfo()
+        _lib.check(lib.uniir_image_batch_plan(descs, count, self.n_px, max(self.out_items, 1), off, plans,
+                                              ctypes.byref(self.info)), "image_batch_plan")
+        nd, npl = count * ctypes.sizeof(_lib.ImageDesc), count * ctypes.sizeof(_lib.ImagePlan)
+        self.plan0 = (nd + 255) & ~255
+        self.pix0 = self.plan0 + ((npl + 255) & ~255)
+        self.blob = torch.empty(self.pix0 + off, dtype=torch.uint8, pin_memory=bool(pin))
+        self.pinned = bool(pin)
+        view = self.blob.numpy()
+        if count:
+            view[:nd] = np.frombuffer(descs, dtype=np.uint8, count=nd)
+            view[self.plan0:self.plan0 + npl] = np.frombuffer(plans, dtype=np.uint8, count=npl)
+        for i, a in enumerate(arrays):
+            view[self.pix0 + descs[i].offset:self.pix0 + descs[i].offset + a.size] = a.reshape(-1)
+        self.descs, self.plans = descs, plans
+
+    def run(self, device, mean=_MEAN, std=_STD, out=None, blob=None):
+        """one non_blocking copy of the buffer (or `blob`: a device copy made earlier) + one call of the batched entry point
+        on the current stream -> out fp32 [out_items, 3, n, n]; slots that no image names keep what they held"""
+        import ctypes
+
+        from . import _lib
+        lib = _lib.load()
+        n = self.n_px
+        if out is None:
+            out = torch.empty(self.out_items, 3, n, n, device=device, dtype=torch.float32)
+        elif (tuple(out.shape) != (self.out_items, 3, n, n) or out.dtype != torch.float32 or not out.is_contiguous()
+              or not out.is_cuda):
+            raise ValueError(f"out must be a contiguous fp32 [{self.out_items}, 3, {n}, {n}] device tensor")
+        if self.count == 0:
+            return out
+        dev = self.blob.to(device, non_blocking=True) if blob is None else blob
+        ws = torch.empty(max(int(self.info.workspace_bytes), 256), device=device, dtype=torch.uint8)
+        mean_c, std_c = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+        base = dev.data_ptr()
+        _lib.check(lib.uniir_image_preprocess_batch(base + self.pix0, base, base + self.plan0, ctypes.byref(self.info), mean_c,
+                                                    std_c, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                    torch.cuda.current_stream(device).cuda_stream), "image_preprocess_batch")
+        return out
+
+
+def preprocess_batch_on_device(images, geoms, n_px, device, mean=_MEAN, std=_STD, out=None, out_index=None, pin=False):
+    """The batched form of preprocess_on_device with per-image geometry (source box, resized size, window, flip: PackedImages):
+    one packed host buffer, ONE non_blocking copy, ONE call of uniir_image_preprocess_batch (three launches whatever the
+    batch size) -> fp32 [out_items, 3, n_px, n_px].  geoms=None is the CLIP chain on whole images, bit-identical to
+    preprocess_on_device; `out_index` scatters into `out` (other slots untouched).  `images` may be a PackedImages built
+    earlier (a pinned one by RawImageBatch.pin_memory)."""
+    packed = images if isinstance(images, PackedImages) else PackedImages(
+        images, geoms, n_px, out_index=out_index, out_items=None if out is None else int(out.shape[0]), pin=pin)
+    return packed.run(device, mean, std, out=out)
+
+
+class RawImage:
+    """a decoded RGB image waiting for the device transform (uint8 [h, w, 3], shareable between loader workers); `geom` =
+    (box_left, box_top, box_w, box_h, flip) drawn by the worker (blip_front.RawBlipTransform), None = the whole image"""
+    __slots__ = ("data", "geom")
+
+    def __init__(self, data, geom=None):
+        self.data, self.geom = data, geom
 
 
 class RawImageTransform:
     """Drop-in `img_preprocess_fn` that defers resize / crop / normalise to the GPU: the dataset worker only decodes, the
-    collator builds a RawImageBatch, and the batch is transformed by `preprocess_on_device` when it is moved to the device
-    (host_utils.DevicePrefetcher / batch_to_device).  Bit-identical tensors to the CPU transform `_preprocess(n_px)`."""
+    collator builds a RawImageBatch, and the batch is transformed by `preprocess_batch_on_device` when it is moved to the
+    device (host_utils.DevicePrefetcher / batch_to_device).  Bit-identical tensors to the CPU transform `_preprocess(n_px)`."""
 
     def __init__(self, n_px, mean=_MEAN, std=_STD, center_crop=True):
         self.n_px, self.mean, self.std, self.center_crop = n_px, tuple(mean), tuple(std), center_crop
@@ -100,28 +195,38 @@ class RawImageTransform:
 
 
 class RawImageBatch:
-    """what a collator stacks instead of a float tensor when its items are RawImages (None = the black padding image of
-    items without an image, which the reference builds as zeros AFTER normalisation)"""
+    """what a collator stacks instead of a float tensor when its items are RawImages (bare uint8 tensors are whole images;
+    None = the black padding image of items without an image, which the reference builds as zeros AFTER normalisation)"""
 
     def __init__(self, images, transform):
-        self.images, self.transform = list(images), transform
+        self.images, self.transform, self._packed = list(images), transform, None
 
     def size(self, dim=0):
         n = self.transform.n_px
         return (len(self.images), 3, n, n)[dim]
 
+    def _pack(self, pin):
+        t = self.transform
+        have = [i for i, im in enumerate(self.images) if im is not None]
+        datas, geoms = [], []
+        for i in have:
+            im = self.images[i]
+            data, g = (im.data, im.geom) if isinstance(im, RawImage) else (im, None)
+            left, top, bw, bh, flip = g if g is not None else (0, 0, int(data.shape[1]), int(data.shape[0]), 0)
+            datas.append(data)      # the transform's own Resize (+ CenterCrop) applied to the box
+            geoms.append((left, top, bw, bh) + resize_geometry(bh, bw, t.n_px, t.center_crop) + (flip,))
+        return PackedImages(datas, geoms, t.n_px, out_index=have, out_items=len(self.images), pin=pin)
+
     def pin_memory(self):
-        self.images = [im if im is None else im.pin_memory() for im in self.images]
+        if self._packed is None or not self._packed.pinned:
+            self._packed = self._pack(pin=True)         # the single pinned buffer that to_device copies
         return self
 
     def to_device(self, device):
         t = self.transform
         out = torch.zeros(len(self.images), 3, t.n_px, t.n_px, device=device, dtype=torch.float32)
-        have = [i for i, im in enumerate(self.images) if im is not None]
-        if have:
-            got = preprocess_on_device([self.images[i] for i in have], t.n_px, device, t.mean, t.std, t.center_crop)
-            out[torch.tensor(have, device=device)] = got
-        return out
+        packed = self._packed if self._packed is not None else self._pack(pin=False)
+        return packed.run(device, t.mean, t.std, out=out)       # scattered to the positions that have an image
 
 
 def load(name="ViT-B/32", device="cuda", jit=False, download_root=None, seed=0):

@@ -15,4 +15,5 @@ extern "C" const char* uniir_strerror(int code) {
 // 2 (round 6): uniir_clip_tower grew pool_last_block; uniir_gemm_timing_read_ex returns the fallback flag; new entry points
 // uniir_reduce_scratch, uniir_attention_{fwd,bwd}_rows, uniir_dropout_{f32,bf16}_rows, uniir_gemm_timing_filter
 // 4: new entry point uniir_reduce_stats
-extern "C" int uniir_abi_version(void) { return 4; }
+// 5: new entry points uniir_image_batch_plan, uniir_image_preprocess_batch (uniir_image_desc / _plan / _batch_info)
+extern "C" int uniir_abi_version(void) { return 5; }
