@@ -34,7 +34,8 @@ extern "C" {
 #define UNIIR_EUNSUPPORTED (-5)
 
 const char* uniir_strerror(int code);
-/* ABI version; bumped on any signature or struct-layout change (3: uniir_clip_tower.recompute; 4: uniir_reduce_stats). */
+/* ABI version; bumped on any signature or struct-layout change (3: uniir_clip_tower.recompute; 4: uniir_reduce_stats;
+ * 5: uniir_image_*; 6: uniir_attention_fwd_long / _bwd_long). */
 int uniir_abi_version(void);
 /* Reproducible reductions (round 6).  Bias, LayerNorm-weight and token-embedding gradients are sums over every row of a batch taken by
  * many workgroups; added with fp32 atomics they depend on the arrival order, and two runs of one training step differ in their last
@@ -153,6 +154,10 @@ int uniir_layernorm_bwd_ex(const float* x, int64_t x_stride, const float* gamma,
  *                                                bitwise reproducible); the uniir_clip_tower vision towers use this form
  *   uniir_attention_fwd / _bwd with causal = 1 : seq <= 512
  *   _packed, _ex, _rows, _rel_fwd / _rel_bwd   : seq, tq, tk <= 512 (mask, key_len, dropout, packed rows, relative bias)
+ *   uniir_attention_fwd_long / _bwd_long       : tq, tk <= 1024: the general form without the causal mask (Q separate from K | V,
+ *                                                key_len, dropout, packed query rows), K / V or Q / dO streamed through LDS at
+ *                                                every size; bitwise reproducible.  BLIP MED cross-attention over 577 image tokens
+ *   Still 512 at most: the causal mask, fully packed rows (_packed, _rows with kv_packed), the relative bias.
  * qkv bf16 [batch*seq][3*heads*64] as produced by nn.MultiheadAttention.in_proj ([q | k | v] per row);
  * out bf16 [batch*seq][heads*64]; lse f32 [batch][heads][seq] (natural log-sum-exp of scaled scores).
  * causal = 1 applies CLIP's build_attention_mask (key <= query).
@@ -203,6 +208,29 @@ int uniir_attention_bwd_rows(const void* q, int64_t q_ld, const void* k, const v
                              const void* dout, int64_t out_ld, const float* lse, const int32_t* q_row_off, int32_t kv_packed,
                              const int32_t* key_len, void* dq, int64_t dq_ld, void* dk, void* dv, int64_t dkv_ld, int32_t batch,
                              int32_t tq, int32_t tk, int32_t heads, float drop_p, uint32_t drop_seed, void* stream);
+/* The general form for 1 <= tq, tk <= 1024 (bf16, head_dim 64, scale 1/8, no causal mask).  q_row_off == NULL: the call is
+ * uniir_attention_fwd_ex / _bwd_ex with causal = 0 (dense [batch][tq] query rows).  q_row_off != NULL: the call is
+ * uniir_attention_fwd_rows / _bwd_rows with kv_packed = 0: item m's queries are the rows q_row_off[m] .. q_row_off[m + 1] - 1 of q /
+ * out / dout / dq, K / V / dk / dv stay dense [batch][tk].  lse is dense [batch][heads][tq]; entries of rows an item does not have
+ * are not written.  key_len[m] >= 1 (NULL: all tk keys); the dk / dv rows of masked keys are written as exact zeros.  The dropout
+ * factor of an element is drawn at the dense coordinate ((m * heads + h) * tq + query) * tk + key, the softmax statistics come from
+ * the undropped P, so a packed call's live rows are bitwise the dense call's.  Every size runs the streaming kernels (128 query
+ * rows per workgroup, K / V in 128-key chunks; dK / dV: 128 keys per workgroup, Q / dO in 64-query chunks); nothing is atomic.
+ * As for _rows, every item has at least one query row (q_row_off[m + 1] > q_row_off[m]): an item without queries is not an input.
+ * (The kernels would launch no work on its rows and write zeros to its dk / dv rows, but the contract does not promise it and no
+ * test covers it.)  The dropout coordinate is taken modulo 2^32, as in the 512-token kernels: a head's extent tq * tk reaches 2^20
+ * here, so the coordinates of a call wrap -- and items far apart share masks -- once batch * heads * tq * tk exceeds 2^32 (batch *
+ * heads > 4096 at 1024 x 1024, > 12900 at 577 x 577, > 74000 at 100 x 577).
+ * UNIIR_EINVAL: a NULL operand, heads <= 0, batch < 0, drop_p outside [0, 1); UNIIR_ESHAPE: tq or tk outside 1 .. 1024;
+ * UNIIR_EALIGN: a leading dimension that is no multiple of 8 or a pointer that is not 16-byte aligned.  A refused call writes
+ * nothing; batch == 0 is UNIIR_OK. */
+int uniir_attention_fwd_long(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, void* out, int64_t out_ld,
+                             float* lse, const int32_t* q_row_off, const int32_t* key_len, int32_t batch, int32_t tq, int32_t tk,
+                             int32_t heads, float drop_p, uint32_t drop_seed, void* stream);
+int uniir_attention_bwd_long(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, const void* out,
+                             const void* dout, int64_t out_ld, const float* lse, const int32_t* q_row_off, const int32_t* key_len,
+                             void* dq, int64_t dq_ld, void* dk, void* dv, int64_t dkv_ld, int32_t batch, int32_t tq, int32_t tk,
+                             int32_t heads, float drop_p, uint32_t drop_seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * [ENC] small fused pieces of the towers.

@@ -16,4 +16,5 @@ extern "C" const char* uniir_strerror(int code) {
 // uniir_reduce_scratch, uniir_attention_{fwd,bwd}_rows, uniir_dropout_{f32,bf16}_rows, uniir_gemm_timing_filter
 // 4: new entry point uniir_reduce_stats
 // 5: new entry points uniir_image_batch_plan, uniir_image_preprocess_batch (uniir_image_desc / _plan / _batch_info)
-extern "C" int uniir_abi_version(void) { return 5; }
+// 6: new entry points uniir_attention_fwd_long, uniir_attention_bwd_long
+extern "C" int uniir_abi_version(void) { return 6; }

@@ -1,5 +1,9 @@
-// Fused attention for sequences of 513 .. 1024 tokens (head_dim 64): plain self-attention (no causal mask, no bias, no dropout,
-// dense rows), forward in bf16 / fp16 and backward in bf16.  CLIP ViT-L/14@336px: 577 tokens.
+// Fused attention for sequences of 513 .. 1024 tokens (head_dim 64).  Two families of kernels on the same bodies:
+//   attn_long_*  : plain self-attention (no causal mask, no bias, no dropout, dense rows), forward in bf16 / fp16 and backward in
+//                  bf16.  CLIP ViT-L/14@336px: 577 tokens.
+//   attn_xlong_* : the general form (Q separate from K | V, uniir_attention_fwd_long / _bwd_long) in bf16: per-item key counts
+//                  (key_len), packed query rows (q_row_off) and probability dropout (DROP).  BLIP MED cross-attention over the
+//                  577 image tokens of a 384-pixel ViT.  Every size from 1 x 1 to 1024 x 1024 runs here.
 //
 // A head of that length no longer fits LDS whole (attention.hip: 2 * 512 * 128 bytes), so one operand is STREAMED: a workgroup
 // (8 waves) owns 128 rows of one (item, head) -- every wave one 16-row tile for the whole sweep, its accumulators in registers --
@@ -13,6 +17,9 @@
 // has a fixed order: the results are bitwise reproducible.  delta = rowsum(dO . O) is recomputed from the O / dO rows (the ABI has no
 // workspace): 8 lanes hold a row's 16-byte pieces, their partial dots meet in a fixed butterfly.
 // A query row's result never depends on the rows that share its tile or its workgroup (the rescale decision is per row).
+// The bodies are templates: XL = per-item ranges (the queries of item m are rows row_off[m] .. of q / out / dout / dq, its keys stop at
+// kvalid = min(Tk, klen[m]); lse and the dropout coordinates keep the dense [item][head][a.Tq] x a.Tk numbering), DROP = dropout of
+// P.  The attn_long_* kernels are the <XL = false, DROP = false> instantiations.
 #include "attention.h"
 
 #define AL_THREADS 512
@@ -64,18 +71,39 @@ DEVINL void al_delta(float* dl, const u32x4_t (&o)[CH * 8 / AL_THREADS], const u
 }
 
 // ---------------- forward ----------------
-template <bool F16>
-__global__ __launch_bounds__(AL_THREADS) void attn_long_fwd_kernel(AttnArgs a, int nqb) {
+// the rows of item m: first query row and query count (packed with XL and row_off), the keys a sweep visits
+template <bool XL>
+DEVINL void al_item(const AttnArgs& a, int m, long& qr0, int& Tq, int& kvalid) {
+    Tq = a.Tq;
+    qr0 = (long)m * Tq;
+    kvalid = a.Tk;
+    if (XL) {
+        if (a.row_off) {
+            qr0 = a.row_off[m];
+            Tq = a.row_off[m + 1] - a.row_off[m];
+        }
+        if (a.klen) kvalid = min(a.Tk, a.klen[m]);
+    }
+}
+
+template <bool F16, bool XL, bool DROP>
+DEVINL void al_fwd_body(const AttnArgs& a, int nqb) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int NL = AL_KV * 8 / AL_THREADS;
     constexpr int BUF = 2 * AL_KV * 128;      // K chunk, V chunk
-    const int H = a.H, Tq = a.Tq, Tk = a.Tk;
+    const int H = a.H;
     const int qb = blockIdx.x % nqb, mh = blockIdx.x / nqb;      // the query blocks of a head are neighbours: K / V stay in L2
     const int m = mh / H, h = mh % H;
+    long qr0;
+    int Tq, Tk;          // Tk: the keys of the sweep (XL: the item's valid keys; the masked ones are never staged)
+    al_item<XL>(a, m, qr0, Tq, Tk);
+    if (XL && qb * AL_ROWS >= Tq) return;      // a packed item shorter than the call's tq (the whole workgroup leaves)
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned short* qbase = a.q + (long)m * Tq * a.q_ld + h * ATT_D;
-    const unsigned short* kbase = a.k + (long)m * Tk * a.kv_ld + h * ATT_D;
-    const unsigned short* vbase = a.v + (long)m * Tk * a.kv_ld + h * ATT_D;
+    const unsigned short* qbase = a.q + qr0 * a.q_ld + h * ATT_D;
+    const unsigned short* kbase = a.k + (long)m * a.Tk * a.kv_ld + h * ATT_D;
+    const unsigned short* vbase = a.v + (long)m * a.Tk * a.kv_ld + h * ATT_D;
+    const unsigned dth = DROP ? drop_threshold(a.drop_p) : 0u;
+    const float dks = DROP ? 1.0f / (1.0f - a.drop_p) : 1.0f;
     const int qi = lane & 15, g = lane >> 4;
     const int q0 = qb * AL_ROWS + w * 16, q = q0 + qi;
     const bool active = q0 < Tq;          // wave-uniform; an idle wave still stages and meets the barriers
@@ -148,6 +176,14 @@ __global__ __launch_bounds__(AL_THREADS) void attn_long_fwd_kernel(AttnArgs a, i
                     for (int r = 0; r < 4; ++r) st[kt][r] = __builtin_amdgcn_exp2f(arg[r]);
                     l4 = l4 + st[kt];
                 }
+                if (DROP) {      // acc[r] = S[key = 4g + r][q = qi]; dense coordinates: packed rows draw the dense call's mask
+                    const unsigned rowbase = (unsigned)((((long)m * H + h) * a.Tq + q) * a.Tk);
+#pragma unroll
+                    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            st[kt][r] *= drop_scale(rowbase + (unsigned)(k0 + kb * 32 + kt * 16 + 4 * g + r), a.drop_seed, dth, dks);
+                }
                 const bf16x8_t pf = pack8x<F16>(st[0], st[1]);
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) o[dt] = mfma16x<F16>(frag_cols_tr(ldsV, kb * 32, dt, lane), pf, o[dt]);
@@ -172,9 +208,17 @@ __global__ __launch_bounds__(AL_THREADS) void attn_long_fwd_kernel(AttnArgs a, i
     if (active) {
         const float l_run = group_sum((l4[0] + l4[1]) + (l4[2] + l4[3]));
         const bool live = q < Tq;
-        att_store_tile<F16>(o, 1.0f / l_run, a.out + ((long)m * Tq + min(q, Tq - 1)) * a.out_ld + h * ATT_D, live, g);
-        if (live && g == 0) a.lse[((long)m * H + h) * Tq + q] = m_run * LN2F + __logf(l_run);
+        att_store_tile<F16>(o, 1.0f / l_run, a.out + (qr0 + min(q, Tq - 1)) * a.out_ld + h * ATT_D, live, g);
+        if (live && g == 0) a.lse[((long)m * H + h) * a.Tq + q] = m_run * LN2F + __logf(l_run);
     }
+}
+template <bool F16>
+__global__ __launch_bounds__(AL_THREADS) void attn_long_fwd_kernel(AttnArgs a, int nqb) {
+    al_fwd_body<F16, false, false>(a, nqb);
+}
+template <bool DROP>
+__global__ __launch_bounds__(AL_THREADS) void attn_xlong_fwd_kernel(AttnArgs a, int nqb) {
+    al_fwd_body<false, true, DROP>(a, nqb);
 }
 
 // the lane parts of the swizzled fragment addresses (attn_bwd_kernel): row fragments of k-step s, transposed fragments of column tile dt
@@ -203,23 +247,34 @@ DEVINL bf16x8_t al_cols_frag(const char* p) {      // 32-row block: rows 4g.., 1
 // ---------------- backward: dK, dV (phase 1 of attn_bwd_kernel, the queries streamed) ----------------
 // buffer: Q chunk, dO chunk, lse * log2 e, delta.  Rows >= Tq of a chunk are zero in all four: p = 1, dP = 0, dS = 0, and the zero dO / Q
 // rows add nothing.  A key's dK / dV column depends on that key alone, so the dead keys of the last tile need no mask: they are not stored.
-__global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dkdv_kernel(AttnArgs a, int nkblk) {
+// XL: the key rows kvalid .. Tk - 1 of an item are masked: their dK / dV rows are written as exact zeros (a tile behind kvalid skips the
+// sweep; in the tile that holds the edge a lane's accumulators belong to its own key alone and are cleared before the store).
+template <bool XL, bool DROP>
+DEVINL void al_dkdv_body(const AttnArgs& a, int nkblk) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int NL = AL_QC * 8 / AL_THREADS;
     constexpr int BUF = 2 * AL_QC * 128 + 2 * AL_QC * 4;
-    const int H = a.H, Tq = a.Tq, Tk = a.Tk;
+    const int H = a.H, Tk = a.Tk;
     const int kblk = blockIdx.x % nkblk, mh = blockIdx.x / nkblk;
     const int m = mh / H, h = mh % H;
+    long qr0;
+    int Tq, kvalid;
+    al_item<XL>(a, m, qr0, Tq, kvalid);
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned short* qbase = a.q + (long)m * Tq * a.q_ld + h * ATT_D;
+    const unsigned short* qbase = a.q + qr0 * a.q_ld + h * ATT_D;
     const unsigned short* kbase = a.k + (long)m * Tk * a.kv_ld + h * ATT_D;
     const unsigned short* vbase = a.v + (long)m * Tk * a.kv_ld + h * ATT_D;
-    const unsigned short* obase = a.out + (long)m * Tq * a.out_ld + h * ATT_D;
-    const unsigned short* dobase = a.dout + (long)m * Tq * a.out_ld + h * ATT_D;
-    const float* lsebase = a.lse + ((long)m * H + h) * Tq;
+    const unsigned short* obase = a.out + qr0 * a.out_ld + h * ATT_D;
+    const unsigned short* dobase = a.dout + qr0 * a.out_ld + h * ATT_D;
+    const float* lsebase = a.lse + ((long)m * H + h) * a.Tq;
+    const unsigned dth = DROP ? drop_threshold(a.drop_p) : 0u;
+    const float dks = DROP ? 1.0f / (1.0f - a.drop_p) : 1.0f;
+    const unsigned headbase = (unsigned)((((long)m * H + h) * a.Tq) * a.Tk);      // dense coordinates (see the forward)
     const int li = lane & 15, g = lane >> 4;
     const int k0 = kblk * AL_ROWS + w * 16, key = k0 + li;
-    const bool active = k0 < Tk;
+    const bool stores = k0 < Tk;                                  // wave-uniform
+    const bool active = XL ? k0 < kvalid : stores;                // the waves that run the sweep; the others only stage
+    const int nch = (XL && kblk * AL_ROWS >= kvalid) ? 0 : (Tq + AL_QC - 1) / AL_QC;      // a workgroup of masked keys streams nothing
     bf16x8_t kf[2], vf[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -249,10 +304,11 @@ __global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dkdv_kernel(AttnArgs 
         if (tid < AL_QC) st[tid] = (r0 + tid < Tq) ? rl * LOG2EF : 0.f;
         al_delta<AL_QC>(st + AL_QC, ro, rdo, r0, Tq, tid);
     };
-    fetch(0);
-    put(lds, 0);
+    if (!XL || nch > 0) {
+        fetch(0);
+        put(lds, 0);
+    }
     __syncthreads();
-    const int nch = (Tq + AL_QC - 1) / AL_QC;
     for (int c = 0; c < nch; ++c) {
         const char* bufA = lds + (c & 1) * BUF;      // Q; dO sits AL_QC * 128 bytes behind it at the same lane offsets
         constexpr int dAB = AL_QC * 128;
@@ -280,8 +336,14 @@ __global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dkdv_kernel(AttnArgs 
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[r], SCALE_LOG2E, -l4[r]));
-                        pt[qt][r] = p;
-                        dst[qt][r] = p * (dp[r] - d4[r]);
+                        if (DROP) {
+                            const float mk = drop_scale(headbase + (unsigned)(r0 + qv + r) * (unsigned)Tk + (unsigned)key, a.drop_seed, dth, dks);
+                            pt[qt][r] = p * mk;
+                            dst[qt][r] = p * (dp[r] * mk - d4[r]);
+                        } else {
+                            pt[qt][r] = p;
+                            dst[qt][r] = p * (dp[r] - d4[r]);
+                        }
                     }
                 }
                 const bf16x8_t pf = pack8(pt[0], pt[1]), dsf = pack8(dst[0], dst[1]);
@@ -295,29 +357,48 @@ __global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dkdv_kernel(AttnArgs 
         if (c + 1 < nch) put(lds + ((c + 1) & 1) * BUF, r0 + AL_QC);
         __syncthreads();
     }
-    if (active) {
+    if (stores) {
+        if (XL && key >= kvalid) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                dv[dt] = zero4;
+                dk[dt] = zero4;
+            }
+        }
         const bool live = key < Tk;
         const long krow = ((long)m * Tk + min(key, Tk - 1)) * a.dkv_ld + h * ATT_D;
         att_store_tile(dk, ATT_SCALE, a.dk + krow, live, g);
         att_store_tile(dv, 1.0f, a.dv + krow, live, g);
     }
 }
+__global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dkdv_kernel(AttnArgs a, int nkblk) { al_dkdv_body<false, false>(a, nkblk); }
+template <bool DROP>
+__global__ __launch_bounds__(AL_THREADS, 4) void attn_xlong_dkdv_kernel(AttnArgs a, int nkblk) {
+    al_dkdv_body<true, DROP>(a, nkblk);
+}
 
 // ---------------- backward: dQ (phase 2 of attn_bwd_kernel, the keys streamed) ----------------
-__global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dq_kernel(AttnArgs a, int nqb) {
+template <bool XL, bool DROP>
+DEVINL void al_dq_body(const AttnArgs& a, int nqb) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int NL = AL_KV * 8 / AL_THREADS;
     constexpr int BUF = 2 * AL_KV * 128;
-    const int H = a.H, Tq = a.Tq, Tk = a.Tk;
+    const int H = a.H;
     const int qb = blockIdx.x % nqb, mh = blockIdx.x / nqb;
     const int m = mh / H, h = mh % H;
+    long qr0;
+    int Tq, Tk;          // Tk: the keys of the sweep (see al_fwd_body)
+    al_item<XL>(a, m, qr0, Tq, Tk);
+    if (XL && qb * AL_ROWS >= Tq) return;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned short* qbase = a.q + (long)m * Tq * a.q_ld + h * ATT_D;
-    const unsigned short* kbase = a.k + (long)m * Tk * a.kv_ld + h * ATT_D;
-    const unsigned short* vbase = a.v + (long)m * Tk * a.kv_ld + h * ATT_D;
-    const unsigned short* obase = a.out + (long)m * Tq * a.out_ld + h * ATT_D;
-    const unsigned short* dobase = a.dout + (long)m * Tq * a.out_ld + h * ATT_D;
-    const float* lsebase = a.lse + ((long)m * H + h) * Tq;
+    const unsigned short* qbase = a.q + qr0 * a.q_ld + h * ATT_D;
+    const unsigned short* kbase = a.k + (long)m * a.Tk * a.kv_ld + h * ATT_D;
+    const unsigned short* vbase = a.v + (long)m * a.Tk * a.kv_ld + h * ATT_D;
+    const unsigned short* obase = a.out + qr0 * a.out_ld + h * ATT_D;
+    const unsigned short* dobase = a.dout + qr0 * a.out_ld + h * ATT_D;
+    const float* lsebase = a.lse + ((long)m * H + h) * a.Tq;
+    const unsigned dth = DROP ? drop_threshold(a.drop_p) : 0u;
+    const float dks = DROP ? 1.0f / (1.0f - a.drop_p) : 1.0f;
     const int li = lane & 15, g = lane >> 4;
     const int qw0 = qb * AL_ROWS;                  // the workgroup's first query row (< Tq)
     const int q0 = qw0 + w * 16, q = q0 + li;
@@ -380,6 +461,12 @@ __global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dq_kernel(AttnArgs a,
                         for (int r = 0; r < 4; ++r)
                             if (k0 + kb * 32 + kt * 16 + 4 * g + r >= Tk) dst[kt][r] = 0.f;
                     }
+                    if (DROP) {
+                        const unsigned rowbase = (unsigned)((((long)m * H + h) * a.Tq + q) * a.Tk);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            dp[r] *= drop_scale(rowbase + (unsigned)(k0 + kb * 32 + kt * 16 + 4 * g + r), a.drop_seed, dth, dks);
+                    }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) dst[kt][r] = dst[kt][r] * (dp[r] - my_D);
                 }
@@ -396,7 +483,12 @@ __global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dq_kernel(AttnArgs a,
         __syncthreads();
     }
     if (active)
-        att_store_tile(dq, ATT_SCALE, a.dq + ((long)m * Tq + min(q, Tq - 1)) * a.dq_ld + h * ATT_D, q < Tq, g);
+        att_store_tile(dq, ATT_SCALE, a.dq + (qr0 + min(q, Tq - 1)) * a.dq_ld + h * ATT_D, q < Tq, g);
+}
+__global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dq_kernel(AttnArgs a, int nqb) { al_dq_body<false, false>(a, nqb); }
+template <bool DROP>
+__global__ __launch_bounds__(AL_THREADS, 4) void attn_xlong_dq_kernel(AttnArgs a, int nqb) {
+    al_dq_body<true, DROP>(a, nqb);
 }
 
 // what the long kernels take: dense rows, no mask, no bias, no dropout, the default scale
@@ -438,4 +530,87 @@ int launch_attn_long_bwd(const AttnArgs& a, int batch, hipStream_t st) {
     hipLaunchKernelGGL(attn_long_dq_kernel, dim3((unsigned)gq), dim3(AL_THREADS), AL_DQ_LDS, st, a, nqb);
     HIP_LAUNCH_CHECK();
     return UNIIR_OK;
+}
+
+// ---------------- the general form (uniir_attention_fwd_long / _bwd_long) ----------------
+static int launch_attn_xlong_fwd(const AttnArgs& a, int batch, hipStream_t st) {
+    const int nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
+    const long grid = (long)batch * a.H * nqb;
+    if (grid > 0x7fffffffL) return UNIIR_ESHAPE;
+    static PerDeviceOnce attr;
+    if (attr.first()) {
+        (void)hipFuncSetAttribute((const void*)attn_xlong_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_FWD_LDS);
+        (void)hipFuncSetAttribute((const void*)attn_xlong_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_FWD_LDS);
+    }
+    if (a.drop_p > 0.f) hipLaunchKernelGGL(attn_xlong_fwd_kernel<true>, dim3((unsigned)grid), dim3(AL_THREADS), AL_FWD_LDS, st, a, nqb);
+    else hipLaunchKernelGGL(attn_xlong_fwd_kernel<false>, dim3((unsigned)grid), dim3(AL_THREADS), AL_FWD_LDS, st, a, nqb);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+static int launch_attn_xlong_bwd(const AttnArgs& a, int batch, hipStream_t st) {
+    const int nkblk = (a.Tk + AL_ROWS - 1) / AL_ROWS, nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
+    const long gk = (long)batch * a.H * nkblk, gq = (long)batch * a.H * nqb;
+    if (gk > 0x7fffffffL || gq > 0x7fffffffL) return UNIIR_ESHAPE;
+    static PerDeviceOnce attr;
+    if (attr.first()) {
+        (void)hipFuncSetAttribute((const void*)attn_xlong_dkdv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DKDV_LDS);
+        (void)hipFuncSetAttribute((const void*)attn_xlong_dkdv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DKDV_LDS);
+        (void)hipFuncSetAttribute((const void*)attn_xlong_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DQ_LDS);
+        (void)hipFuncSetAttribute((const void*)attn_xlong_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DQ_LDS);
+    }
+    const bool drop = a.drop_p > 0.f;
+    if (drop) hipLaunchKernelGGL(attn_xlong_dkdv_kernel<true>, dim3((unsigned)gk), dim3(AL_THREADS), AL_DKDV_LDS, st, a, nkblk);
+    else hipLaunchKernelGGL(attn_xlong_dkdv_kernel<false>, dim3((unsigned)gk), dim3(AL_THREADS), AL_DKDV_LDS, st, a, nkblk);
+    HIP_LAUNCH_CHECK();
+    if (drop) hipLaunchKernelGGL(attn_xlong_dq_kernel<true>, dim3((unsigned)gq), dim3(AL_THREADS), AL_DQ_LDS, st, a, nqb);
+    else hipLaunchKernelGGL(attn_xlong_dq_kernel<false>, dim3((unsigned)gq), dim3(AL_THREADS), AL_DQ_LDS, st, a, nqb);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+// The general form up to 1024 x 1024: q_row_off == NULL is uniir_attention_fwd_ex / _bwd_ex with causal = 0, otherwise
+// uniir_attention_fwd_rows / _bwd_rows with kv_packed = 0 (packed query rows, K / V dense [batch][tk]).  Every size runs the
+// streaming kernels above; nothing is forwarded to the 512-token kernels.
+extern "C" int uniir_attention_fwd_long(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, void* out,
+                                        int64_t out_ld, float* lse, const int32_t* q_row_off, const int32_t* key_len, int32_t batch,
+                                        int32_t tq, int32_t tk, int32_t heads, float drop_p, uint32_t drop_seed, void* stream) {
+    if (!q || !k || !v || !out || !lse || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (!(drop_p >= 0.f && drop_p < 1.f)) return UNIIR_EINVAL;
+    if (batch == 0) return UNIIR_OK;
+    if (tq < 1 || tk < 1 || tq > 1024 || tk > 1024) return UNIIR_ESHAPE;
+    if ((q_ld % 8) || (kv_ld % 8) || (out_ld % 8)) return UNIIR_EALIGN;
+    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
+    AttnArgs a = {};
+    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
+    a.q_ld = q_ld; a.kv_ld = kv_ld; a.out = (unsigned short*)out; a.out_ld = out_ld; a.lse = lse; a.klen = key_len;
+    a.Tq = tq; a.Tk = tk; a.H = heads; a.causal = 0; a.scale = ATT_SCALE;
+    a.row_off = q_row_off; a.row_off_q_only = 1;
+    a.drop_p = drop_p; a.drop_seed = drop_seed;
+    return launch_attn_xlong_fwd(a, batch, (hipStream_t)stream);
+}
+extern "C" int uniir_attention_bwd_long(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, const void* out,
+                                        const void* dout, int64_t out_ld, const float* lse, const int32_t* q_row_off,
+                                        const int32_t* key_len, void* dq, int64_t dq_ld, void* dk, void* dv, int64_t dkv_ld,
+                                        int32_t batch, int32_t tq, int32_t tk, int32_t heads, float drop_p, uint32_t drop_seed,
+                                        void* stream) {
+    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (!(drop_p >= 0.f && drop_p < 1.f)) return UNIIR_EINVAL;
+    if (batch == 0) return UNIIR_OK;
+    if (tq < 1 || tk < 1 || tq > 1024 || tk > 1024) return UNIIR_ESHAPE;
+    if ((q_ld % 8) || (kv_ld % 8) || (out_ld % 8) || (dq_ld % 8) || (dkv_ld % 8)) return UNIIR_EALIGN;      // 16-byte pieces
+    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dout & 15) ||
+        ((uintptr_t)dq & 15) || ((uintptr_t)dk & 15) || ((uintptr_t)dv & 15))
+        return UNIIR_EALIGN;
+    AttnArgs a = {};
+    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
+    a.q_ld = q_ld; a.kv_ld = kv_ld; a.out = (unsigned short*)const_cast<void*>(out); a.out_ld = out_ld;
+    a.lse = const_cast<float*>(lse); a.klen = key_len;
+    a.Tq = tq; a.Tk = tk; a.H = heads; a.causal = 0; a.scale = ATT_SCALE;
+    a.row_off = q_row_off; a.row_off_q_only = 1;
+    a.dout = (const unsigned short*)dout;
+    a.dq = (unsigned short*)dq; a.dk = (unsigned short*)dk; a.dv = (unsigned short*)dv;
+    a.dq_ld = dq_ld; a.dkv_ld = dkv_ld;
+    a.drop_p = drop_p; a.drop_seed = drop_seed;
+    return launch_attn_xlong_bwd(a, batch, (hipStream_t)stream);
 }

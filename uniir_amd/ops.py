@@ -293,15 +293,27 @@ def attention_bwd(qkv, out, dout, lse, batch, seq, heads, causal, *, dqkv=None):
     return dqkv
 
 
+def _attention_long(tq, tk, causal, kv_packed):
+    """the general form goes to uniir_attention_fwd_long / _bwd_long: more than 512 queries or keys, no causal mask, dense K / V"""
+    return max(tq, tk) > 512 and not causal and not kv_packed
+
+
 def attention_fwd_ex(q, q_ld, k, v, kv_ld, batch, tq, tk, heads, *, key_len=None, causal=False, drop_p=0.0, drop_seed=0,
                      row_off=None, kv_packed=False, rows=None):
     """separate Q / K / V views (head h at column h*64 of rows with the given leading dimension); out [batch*tq, heads*64].
     row_off (int32 [batch + 1], with rows = its total): the query rows are PACKED (item m = rows row_off[m] .. row_off[m + 1] - 1,
-    uniir_attention_fwd_rows); kv_packed: K / V are rows of the same numbering (self-attention), else dense [batch][tk]"""
+    uniir_attention_fwd_rows); kv_packed: K / V are rows of the same numbering (self-attention), else dense [batch][tk].
+    tq, tk <= 512; without the causal mask and with dense K / V (kv_packed false) up to 1024 each: max(tq, tk) > 512 runs
+    uniir_attention_fwd_long (the streaming kernels of csrc/attention_long.hip), everything at 512 and below the calls it always
+    ran.  Causal or kv_packed above 512 is UNIIR_ESHAPE."""
     nrow = batch * tq if row_off is None else int(rows)
     out = torch.empty(nrow, heads * 64, device=q.device, dtype=torch.bfloat16)
     lse = torch.empty(batch, heads, tq, device=q.device, dtype=torch.float32)
-    if row_off is None:
+    if _attention_long(tq, tk, causal, kv_packed):
+        check(_lib.load().uniir_attention_fwd_long(_p(q), q_ld, _p(k), _p(v), kv_ld, _p(out), heads * 64, _p(lse), _p(row_off),
+                                                   _p(key_len), batch, tq, tk, heads, float(drop_p), int(drop_seed), _stream()),
+              "attention_fwd_long")
+    elif row_off is None:
         check(_lib.load().uniir_attention_fwd_ex(_p(q), q_ld, _p(k), _p(v), kv_ld, _p(out), heads * 64, _p(lse), _p(key_len),
                                                  batch, tq, tk, heads, int(causal), float(drop_p), int(drop_seed), _stream()),
               "attention_fwd_ex")
@@ -316,7 +328,12 @@ def attention_fwd_ex(q, q_ld, k, v, kv_ld, batch, tq, tk, heads, *, key_len=None
 
 def attention_bwd_ex(q, q_ld, k, v, kv_ld, out, dout, lse, dq, dq_ld, dk, dv, dkv_ld, batch, tq, tk, heads, *,
                      key_len=None, causal=False, drop_p=0.0, drop_seed=0, row_off=None, kv_packed=False):
-    if row_off is None:
+    """d loss / d q, k, v of attention_fwd_ex into dq / dk / dv (same arguments, same limits, the same choice of entry point)"""
+    if _attention_long(tq, tk, causal, kv_packed):
+        check(_lib.load().uniir_attention_bwd_long(_p(q), q_ld, _p(k), _p(v), kv_ld, _p(out), _p(dout), heads * 64, _p(lse),
+                                                   _p(row_off), _p(key_len), _p(dq), dq_ld, _p(dk), _p(dv), dkv_ld, batch, tq, tk,
+                                                   heads, float(drop_p), int(drop_seed), _stream()), "attention_bwd_long")
+    elif row_off is None:
         check(_lib.load().uniir_attention_bwd_ex(_p(q), q_ld, _p(k), _p(v), kv_ld, _p(out), _p(dout), heads * 64, _p(lse),
                                                  _p(key_len), _p(dq), dq_ld, _p(dk), _p(dv), dkv_ld, batch, tq, tk, heads,
                                                  int(causal), float(drop_p), int(drop_seed), _stream()), "attention_bwd_ex")
