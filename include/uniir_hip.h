@@ -133,6 +133,9 @@ int uniir_gemm_timing_filter(const float* windows, int32_t nwin, const float* sa
  * dgamma/dbeta are ACCUMULATED (+=) in fp32 (zero them once per optimizer step); dx_colsum (optional, [width]) +=
  * the column sums of dx_f32 as written (the bias gradient of the linear layer that produced x).
  * dy may be bf16 (dy_is_f32 = 0) or fp32.
+ * Strides: x rows are x_stride floats apart; dx_f32 AND dres rows are dx_stride floats apart (dres is read at dres + row * dx_stride:
+ * it is the gradient of the same residual stream dx_f32 belongs to; a dense dres needs dx_stride == width); y, dy and dx_bf16 are
+ * dense [rows][width].  width % 4 == 0, width <= 2048, x_stride % 4 == 0, dx_stride % 4 == 0 (UNIIR_ESHAPE otherwise).
  * ---------------------------------------------------------------------------------------------- */
 int uniir_layernorm_fwd(const float* x, int64_t x_stride, const float* gamma, const float* beta,
                         void* y_bf16, float* y_f32, int32_t rows, int32_t width, float eps, void* stream);
