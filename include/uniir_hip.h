@@ -35,7 +35,8 @@ extern "C" {
 
 const char* uniir_strerror(int code);
 /* ABI version; bumped on any signature or struct-layout change (3: uniir_clip_tower.recompute; 4: uniir_reduce_stats;
- * 5: uniir_image_*; 6: uniir_attention_fwd_long / _bwd_long). */
+ * 5: uniir_image_*; 6: uniir_attention_fwd_long / _bwd_long; still 6, new entry points only: uniir_attention_rel_fwd_long /
+ * _rel_bwd_long). */
 int uniir_abi_version(void);
 /* Reproducible reductions (round 6).  Bias, LayerNorm-weight and token-embedding gradients are sums over every row of a batch taken by
  * many workgroups; added with fp32 atomics they depend on the arrival order, and two runs of one training step differ in their last
@@ -44,7 +45,7 @@ int uniir_abi_version(void);
  * uniir_text_embed_bwd* and the tower entry points that use them -- stores per-workgroup partials there and adds them in a fixed
  * order (one extra small launch each): same inputs, same bits.  Kernels on one stream run one after the other, so one buffer per
  * stream is enough.  A reduction that needs more than the buffer holds keeps its atomics, and is counted (uniir_reduce_stats).  Also
- * covered since ABI 4: the relative-position-bias gradient of uniir_attention_rel_bwd (per-workgroup bucket partials).
+ * covered since ABI 4: the relative-position-bias gradient of uniir_attention_rel_bwd and _rel_bwd_long (per-workgroup bucket partials).
  * Thread safety: the host-side table (64 entries, one per (device, stream); when it is full the entry used longest ago goes) and the
  * counters are guarded by one mutex, so uniir_reduce_scratch, uniir_reduce_stats and the lookups that launches make may run on any
  * threads at once.  NOT covered: the buffer itself -- two threads that launch reductions on the SAME stream share its scratch and
@@ -160,7 +161,10 @@ int uniir_layernorm_bwd_ex(const float* x, int64_t x_stride, const float* gamma,
  *   uniir_attention_fwd_long / _bwd_long       : tq, tk <= 1024: the general form without the causal mask (Q separate from K | V,
  *                                                key_len, dropout, packed query rows), K / V or Q / dO streamed through LDS at
  *                                                every size; bitwise reproducible.  BLIP MED cross-attention over 577 image tokens
- *   Still 512 at most: the causal mask, fully packed rows (_packed, _rows with kv_packed), the relative bias.
+ *   uniir_attention_rel_fwd_long / _rel_bwd_long: seq <= 1024: the relative bias (and dropout) on packed qkv, streamed at every size;
+ *                                                dqkv bitwise reproducible, drel too with scratch on the stream.  The CLIP_FF
+ *                                                fusion stack over the 577 + 77 tokens of ViT-L/14@336px
+ *   Still 512 at most: the causal mask, fully packed rows (_packed, _rows with kv_packed).
  * qkv bf16 [batch*seq][3*heads*64] as produced by nn.MultiheadAttention.in_proj ([q | k | v] per row);
  * out bf16 [batch*seq][heads*64]; lse f32 [batch][heads][seq] (natural log-sum-exp of scaled scores).
  * causal = 1 applies CLIP's build_attention_mask (key <= query).
@@ -551,6 +555,23 @@ int uniir_attention_rel_fwd(const void* qkv, void* out, float* lse, const float*
 int uniir_attention_rel_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                             const float* rel_emb, const int32_t* rel_bucket, int32_t nbuckets, float scale, float* drel,
                             int32_t batch, int32_t seq, int32_t heads, float drop_p, uint32_t drop_seed, void* stream);
+/* The same two calls for 1 <= seq <= 1024 (bf16, rel_bucket [2 seq - 1]).  Every size runs the streaming kernels of
+ * uniir_attention_fwd_long (128 query rows per workgroup, K / V in 128-key chunks; dK / dV: 128 keys per workgroup, Q / dO in 64-query
+ * chunks), nothing is forwarded to the 512-token kernels; the bias of every diagonal sits in LDS.  drel is ACCUMULATED as above.  A dK /
+ * dV workgroup sums dS along the diagonals its 128 keys see and then per bucket in the 64-bit fixed point of uniir_attention_rel_bwd,
+ * and stores its nbuckets sums, zeros included, as the partial of (item, key block) in the stream's scratch: batch * ceil(seq / 128) *
+ * nbuckets * heads floats, added into drel in that fixed order.  Without that much scratch: one float atomic per (item, key block, head,
+ * bucket), counted by uniir_reduce_stats.  dqkv never depends on arrival order.  Dropout coordinates and their wrap beyond 2^32
+ * elements per call: as for uniir_attention_fwd_long.
+ * UNIIR_EINVAL: a NULL operand (drel may be NULL: no bias gradient), heads <= 0, batch < 0, drop_p outside [0, 1), nbuckets outside
+ * 1 .. 64; UNIIR_ESHAPE: seq outside 1 .. 1024; UNIIR_EALIGN: qkv, out, dout or dqkv not 16-byte aligned.  A refused call writes
+ * nothing; batch == 0 is UNIIR_OK. */
+int uniir_attention_rel_fwd_long(const void* qkv, void* out, float* lse, const float* rel_emb, const int32_t* rel_bucket,
+                                 int32_t nbuckets, float scale, int32_t batch, int32_t seq, int32_t heads, float drop_p,
+                                 uint32_t drop_seed, void* stream);
+int uniir_attention_rel_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
+                                 const float* rel_emb, const int32_t* rel_bucket, int32_t nbuckets, float scale, float* drel,
+                                 int32_t batch, int32_t seq, int32_t heads, float drop_p, uint32_t drop_seed, void* stream);
 int uniir_meanpool_fwd(const float* x, float* out, int32_t n, int32_t tokens, int32_t width, void* stream);
 int uniir_meanpool_bwd(const float* dout, float* dx, int32_t n, int32_t tokens, int32_t width, void* stream);
 

@@ -57,6 +57,11 @@ def _table(T, dev):
     return _TABLES[key]
 
 
+def _rel_entry(which, T):
+    """the resident kernels up to 512 tokens, the streaming ones above (ViT-L/14@336px: 77 + 577 = 654 fused tokens)"""
+    return f"uniir_attention_rel_{which}" + ("_long" if T > 512 else "")
+
+
 def _rms(st, x, name, R, D, out_f32=False):
     y16 = torch.empty(R, D, device=x.device, dtype=torch.bfloat16) if not out_f32 else None
     y32 = torch.empty(R, D, device=x.device, dtype=torch.float32) if out_f32 else None
@@ -95,7 +100,7 @@ def t5_forward(st, prefix, x, M, T, heads, layers, save, drop=None, p=T5_DROPOUT
         ao = torch.empty(R, inner, device=dev, dtype=torch.bfloat16)
         lse = torch.empty(M, heads, T, device=dev, dtype=torch.float32)
         sa = nxt()
-        ops.call("uniir_attention_rel_fwd", qkv, ao, lse, rel, table, T5_BUCKETS, 1.0, M, T, heads, p, sa)
+        ops.call(_rel_entry("fwd", T), qkv, ao, lse, rel, table, T5_BUCKETS, 1.0, M, T, heads, p, sa)
         x2, so = branch(ao, st.w16(a + "SelfAttention.o.weight"), x)
         h2 = _rms(st, x2, f + "layer_norm.weight", R, D)
         wi = st.w16(f + "DenseReluDense.wi.weight")
@@ -164,7 +169,7 @@ def t5_backward(st, prefix, dpooled, stash, heads, layers):
         ops.linear_wgrad(dxb, ao, G(a + "SelfAttention.o.weight"))
         dao = ops.linear_dgrad(dxb, st.w16(a + "SelfAttention.o.weight"))
         dqkv = torch.empty_like(qkv)
-        ops.call("uniir_attention_rel_bwd", qkv, ao, dao, lse, dqkv, st.p(rel_name), table, T5_BUCKETS, 1.0, G(rel_name), M, T,
+        ops.call(_rel_entry("bwd", T), qkv, ao, dao, lse, dqkv, st.p(rel_name), table, T5_BUCKETS, 1.0, G(rel_name), M, T,
                  heads, p, sa)
         ops.linear_wgrad(dqkv, h1, G(a + "SelfAttention.q.weight", (3 * inner, D)))
         dh = ops.linear_dgrad(dqkv, st.w16(a + "SelfAttention.q.weight", (3 * inner, D)))

@@ -162,6 +162,12 @@ DEVINL void att_store_tile(const f32x4_t (&acc)[4], float scale, unsigned short*
     }
 }
 
+// Fixed point of the relative-position-bias gradient: 2^-40 per unit, so a (workgroup, bucket) sum holds |x| < 2^23 and resolves
+// 9.1e-13 -- finer than the fp32 rounding of any sum above 1.5e-5, and each term is rounded once (round to nearest) where a float
+// accumulator rounds at every add.  A term beyond the range saturates (__float2ll_rn), a NaN term counts as 0: dqkv carries the NaN.
+#define ATT_DREL_FIX 1099511627776.0f
+DEVINL unsigned long long att_drel_fix(float v) { return (unsigned long long)__float2ll_rn(v * ATT_DREL_FIX); }
+
 // Generalised argument block: self-attention on the packed in_proj layout (q|k|v per token, CLIP / BLIP ViT / BERT self)
 // and rectangular cross-attention (BLIP MED: Tq text tokens attending to Tk image tokens) share the kernels.
 struct AttnArgs {

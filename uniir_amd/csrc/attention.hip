@@ -192,11 +192,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(AttnArgs a) {
 // NT threads: 512 (8 waves, 128 registers) or 384 (6 waves, 168 registers: no spills, and 5 key tiles of a 77-token head keep 5 of
 // 6 waves busy instead of 5 of 8) -- the launcher picks 384 up to 128 tokens (measured: 50 tokens 0.335 -> 0.261 ms, 77 causal
 // 0.518 -> 0.386 ms at 1024 items; 197 / 257 tokens lose 15-20 % with fewer waves).
-// Fixed point of the relative-position-bias gradient: 2^-40 per unit, so a (workgroup, bucket) sum holds |x| < 2^23 and resolves
-// 9.1e-13 -- finer than the fp32 rounding of any sum above 1.5e-5, and each term is rounded once (round to nearest) where a float
-// accumulator rounds at every add.  A term beyond the range saturates (__float2ll_rn), a NaN term counts as 0: dqkv carries the NaN.
-#define ATT_DREL_FIX 1099511627776.0f
-DEVINL unsigned long long att_drel_fix(float v) { return (unsigned long long)__float2ll_rn(v * ATT_DREL_FIX); }
+// (the fixed point of the relative-position-bias gradient, att_drel_fix: attention.h)
 template <bool REL, bool DROP, bool CAUSAL, int NT>
 __global__ __launch_bounds__(NT, NT == 512 ? 4 : 3) void attn_bwd_kernel(AttnArgs a) {
     constexpr int NWAVES = NT / 64;

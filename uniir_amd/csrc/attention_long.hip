@@ -1,9 +1,12 @@
-// Fused attention for sequences of 513 .. 1024 tokens (head_dim 64).  Two families of kernels on the same bodies:
+// Fused attention for sequences of 513 .. 1024 tokens (head_dim 64).  Three families of kernels on the same bodies:
 //   attn_long_*  : plain self-attention (no causal mask, no bias, no dropout, dense rows), forward in bf16 / fp16 and backward in
 //                  bf16.  CLIP ViT-L/14@336px: 577 tokens.
 //   attn_xlong_* : the general form (Q separate from K | V, uniir_attention_fwd_long / _bwd_long) in bf16: per-item key counts
 //                  (key_len), packed query rows (q_row_off) and probability dropout (DROP).  BLIP MED cross-attention over the
 //                  577 image tokens of a 384-pixel ViT.  Every size from 1 x 1 to 1024 x 1024 runs here.
+//   attn_rlong_* : T5-style self-attention on the packed [q | k | v] buffer (uniir_attention_rel_fwd_long / _rel_bwd_long) in bf16:
+//                  logits = scale * q.k + rel_emb[rel_bucket[key - query + seq - 1]][head] (REL), scale a run-time argument,
+//                  probability dropout, the bias gradient drel in a fixed order.  CLIP_FF at ViT-L/14@336px: 577 + 77 = 654 fused tokens.
 //
 // A head of that length no longer fits LDS whole (attention.hip: 2 * 512 * 128 bytes), so one operand is STREAMED: a workgroup
 // (8 waves) owns 128 rows of one (item, head) -- every wave one 16-row tile for the whole sweep, its accumulators in registers --
@@ -20,6 +23,11 @@
 // The bodies are templates: XL = per-item ranges (the queries of item m are rows row_off[m] .. of q / out / dout / dq, its keys stop at
 // kvalid = min(Tk, klen[m]); lse and the dropout coordinates keep the dense [item][head][a.Tq] x a.Tk numbering), DROP = dropout of
 // P.  The attn_long_* kernels are the <XL = false, DROP = false> instantiations.
+// REL (with XL = false, Tq == Tk): the bias of every diagonal key - query sits in LDS, premultiplied by log2 e and filled once per
+// workgroup: the forward and dQ hold the whole table (2 seq - 1 floats, indexed key + (Tq - 1 - query) with the streamed chunk's
+// first key k0 inside `key`), dK / dV the 128 + seq - 1 diagonals its 128 keys see (indexed (key - first key) + Tq - 1 - query with
+// the streamed chunk's first row r0 inside `query`).  Both tables carry 32 zero slots of slack where the dead rows / keys of a last
+// block point, so no index is clamped.  dK / dV also sums dS along the diagonals for drel (the scheme of attn_bwd_kernel).
 #include "attention.h"
 
 #define AL_THREADS 512
@@ -70,6 +78,14 @@ DEVINL void al_delta(float* dl, const u32x4_t (&o)[CH * 8 / AL_THREADS], const u
     }
 }
 
+// REL: tab[j] = rel_emb[rel_bucket[d0 + j]][h] * log2 e for the diagonals d0 + j in [0, nd), zero for the other slots of tab[0 .. n)
+DEVINL void al_fill_bias(float* tab, const AttnArgs& a, int h, int d0, int nd, int n, int tid) {
+    for (int j = tid; j < n; j += AL_THREADS) {
+        const int d = d0 + j;
+        tab[j] = (d >= 0 && d < nd) ? a.rel_emb[a.rel_bucket[d] * a.H + h] * LOG2EF : 0.f;
+    }
+}
+
 // ---------------- forward ----------------
 // the rows of item m: first query row and query count (packed with XL and row_off), the keys a sweep visits
 template <bool XL>
@@ -86,7 +102,7 @@ DEVINL void al_item(const AttnArgs& a, int m, long& qr0, int& Tq, int& kvalid) {
     }
 }
 
-template <bool F16, bool XL, bool DROP>
+template <bool F16, bool XL, bool DROP, bool REL = false>
 DEVINL void al_fwd_body(const AttnArgs& a, int nqb) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int NL = AL_KV * 8 / AL_THREADS;
@@ -107,7 +123,10 @@ DEVINL void al_fwd_body(const AttnArgs& a, int nqb) {
     const int qi = lane & 15, g = lane >> 4;
     const int q0 = qb * AL_ROWS + w * 16, q = q0 + qi;
     const bool active = q0 < Tq;          // wave-uniform; an idle wave still stages and meets the barriers
-    const float sl2 = SCALE_LOG2E;
+    const float sl2 = REL ? a.scale * LOG2EF : SCALE_LOG2E;
+    const float es = REL ? 1.0f : sl2;          // REL: the scale goes in with the bias, the logits are in log2 units from there on
+    const float* dbias = reinterpret_cast<const float*>(lds + 2 * BUF) + (Tq - 1 - min(q, Tq - 1));      // + key: the lane's row of the bias
+    if (REL) al_fill_bias(reinterpret_cast<float*>(lds + 2 * BUF), a, h, 0, Tq + Tk - 1, Tq + Tk + 31, tid);
     bf16x8_t qf[2];
     qf[0] = frag_rows_global(qbase, a.q_ld, q0, 0, lane, Tq);
     qf[1] = frag_rows_global(qbase, a.q_ld, q0, 1, lane, Tq);
@@ -143,6 +162,13 @@ DEVINL void al_fwd_body(const AttnArgs& a, int nqb) {
                 }
             };
             auto softmax_pv = [&](int kb, f32x4_t (&st)[2]) {
+                if (REL) {
+                    const float* bp = dbias + k0 + kb * 32 + 4 * g;
+#pragma unroll
+                    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) st[kt][r] = __builtin_fmaf(st[kt][r], sl2, bp[kt * 16 + r]);
+                }
                 if (k0 + kb * 32 + 32 > Tk) {
 #pragma unroll
                     for (int kt = 0; kt < 2; ++kt)
@@ -157,12 +183,12 @@ DEVINL void al_fwd_body(const AttnArgs& a, int nqb) {
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[kt][r]);
-                const unsigned long long over = __ballot(__builtin_fmaf(mx, sl2, -m_run) > ATT_DEFER);
+                const unsigned long long over = __ballot(__builtin_fmaf(mx, es, -m_run) > ATT_DEFER);
                 unsigned rows_over = (unsigned)(over | (over >> 32));
                 rows_over = (rows_over | (rows_over >> 16)) & 0xffffu;
                 if (rows_over) {
                     const float gm = group_max(mx);
-                    const float m_new = ((rows_over >> qi) & 1u) ? fmaxf(m_run, gm * sl2) : m_run;
+                    const float m_new = ((rows_over >> qi) & 1u) ? fmaxf(m_run, gm * es) : m_run;
                     const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
                     l4 = l4 * alpha;
 #pragma unroll
@@ -171,7 +197,7 @@ DEVINL void al_fwd_body(const AttnArgs& a, int nqb) {
                 }
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt) {
-                    const f32x4_t arg = __builtin_elementwise_fma(st[kt], f32x4_t{sl2, sl2, sl2, sl2}, f32x4_t{-m_run, -m_run, -m_run, -m_run});
+                    const f32x4_t arg = __builtin_elementwise_fma(st[kt], f32x4_t{es, es, es, es}, f32x4_t{-m_run, -m_run, -m_run, -m_run});
 #pragma unroll
                     for (int r = 0; r < 4; ++r) st[kt][r] = __builtin_amdgcn_exp2f(arg[r]);
                     l4 = l4 + st[kt];
@@ -220,6 +246,10 @@ template <bool DROP>
 __global__ __launch_bounds__(AL_THREADS) void attn_xlong_fwd_kernel(AttnArgs a, int nqb) {
     al_fwd_body<false, true, DROP>(a, nqb);
 }
+template <bool DROP>
+__global__ __launch_bounds__(AL_THREADS, 4) void attn_rlong_fwd_kernel(AttnArgs a, int nqb) {
+    al_fwd_body<false, false, DROP, true>(a, nqb);
+}
 
 // the lane parts of the swizzled fragment addresses (attn_bwd_kernel): row fragments of k-step s, transposed fragments of column tile dt
 struct AlOffs {
@@ -249,7 +279,12 @@ DEVINL bf16x8_t al_cols_frag(const char* p) {      // 32-row block: rows 4g.., 1
 // rows add nothing.  A key's dK / dV column depends on that key alone, so the dead keys of the last tile need no mask: they are not stored.
 // XL: the key rows kvalid .. Tk - 1 of an item are masked: their dK / dV rows are written as exact zeros (a tile behind kvalid skips the
 // sweep; in the tile that holds the edge a lane's accumulators belong to its own key alone and are cleared before the store).
-template <bool XL, bool DROP>
+// REL: behind the two buffers sit bsum [64] (the bucket sums) and ddiag [Tq + 164] (the diagonal sums), both 64-bit fixed point
+// (att_drel_fix), and dbias [Tq + 164].  Slot j of ddiag / dbias is the diagonal (first key of the workgroup) + j - 36: the element
+// (key, query) has j = (key - first key) + Tq + 35 - query, 5 <= j <= Tq + 162 over every row and key a block can hold, dead ones
+// included (the pre-summed value of a lane goes three slots lower: >= 2); the live elements (key < Tk, query < Tq) fill 36 .. 162 + Tq.  Dead rows get p = 0 (their Q / dO / lse / delta are zero, but
+// exp2 of a bias alone need not be 1), and dead rows and keys add nothing to ddiag.
+template <bool XL, bool DROP, bool REL = false>
 DEVINL void al_dkdv_body(const AttnArgs& a, int nkblk) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int NL = AL_QC * 8 / AL_THREADS;
@@ -272,6 +307,18 @@ DEVINL void al_dkdv_body(const AttnArgs& a, int nkblk) {
     const unsigned headbase = (unsigned)((((long)m * H + h) * a.Tq) * a.Tk);      // dense coordinates (see the forward)
     const int li = lane & 15, g = lane >> 4;
     const int k0 = kblk * AL_ROWS + w * 16, key = k0 + li;
+    const float sl2 = REL ? a.scale * LOG2EF : SCALE_LOG2E;
+    const float oscale = REL ? a.scale : ATT_SCALE;
+    unsigned long long* bsum = reinterpret_cast<unsigned long long*>(lds + 2 * BUF);
+    unsigned long long* ddiag = bsum + 64;
+    const int nslot = Tq + 164;
+    float* dbias = reinterpret_cast<float*>(ddiag + nslot);
+    const int jl = w * 16 + li + Tq + 35;          // - query: the lane's slot
+    if (REL) {
+        al_fill_bias(dbias, a, h, kblk * AL_ROWS - 36, Tq + Tk - 1, nslot, tid);
+        if (tid < 64) bsum[tid] = 0ull;
+        for (int j = tid; j < nslot; j += AL_THREADS) ddiag[j] = 0ull;
+    }
     const bool stores = k0 < Tk;                                  // wave-uniform
     const bool active = XL ? k0 < kvalid : stores;                // the waves that run the sweep; the others only stage
     const int nch = (XL && kblk * AL_ROWS >= kvalid) ? 0 : (Tq + AL_QC - 1) / AL_QC;      // a workgroup of masked keys streams nothing
@@ -320,6 +367,7 @@ DEVINL void al_dkdv_body(const AttnArgs& a, int nkblk) {
             const int nqblk = min(AL_QC / 32, (Tq - r0 + 31) >> 5);
             for (int qb = 0; qb < nqblk; ++qb) {
                 const int blk = qb * 4096;
+                const bool qedge = REL && r0 + qb * 32 + 32 > Tq;
                 f32x4_t pt[2], dst[2];
 #pragma unroll
                 for (int qt = 0; qt < 2; ++qt) {
@@ -333,9 +381,12 @@ DEVINL void al_dkdv_body(const AttnArgs& a, int nkblk) {
                     const int qv = qb * 32 + qt * 16 + 4 * g;
                     const f32x4_t l4 = *reinterpret_cast<const f32x4_t*>(lse2 + qv);
                     const f32x4_t d4 = *reinterpret_cast<const f32x4_t*>(Dq + qv);
+                    const int js = jl - (r0 + qv);          // REL: the slot of (key, query r0 + qv), the rows behind it one slot lower each
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[r], SCALE_LOG2E, -l4[r]));
+                        float p = REL ? __builtin_amdgcn_exp2f(__builtin_fmaf(sa[r], sl2, dbias[js - r]) - l4[r])
+                                      : __builtin_amdgcn_exp2f(__builtin_fmaf(sa[r], SCALE_LOG2E, -l4[r]));
+                        if (qedge && r0 + qv + r >= Tq) p = 0.f;
                         if (DROP) {
                             const float mk = drop_scale(headbase + (unsigned)(r0 + qv + r) * (unsigned)Tk + (unsigned)key, a.drop_seed, dth, dks);
                             pt[qt][r] = p * mk;
@@ -352,6 +403,31 @@ DEVINL void al_dkdv_body(const AttnArgs& a, int nkblk) {
                     dv[dt] = mfma16(al_cols_frag(bufA + off.t[dt] + dAB + blk), pf, dv[dt]);
                     dk[dt] = mfma16(al_cols_frag(bufA + off.t[dt] + blk), dsf, dk[dt]);
                 }
+                if (REL && a.drel) {
+#pragma unroll 1          // (unrolled, the two halves' sums are live together: 3 / 12 registers spilled at the 128 of two workgroups per CU)
+                    for (int qt = 0; qt < 2; ++qt) {
+                        const int qv = qb * 32 + qt * 16 + 4 * g, js = jl - (r0 + qv);
+                        // d bias = dS summed along the diagonals, by all waves at once, in 64-bit fixed point: the DPP pre-sum of
+                        // attn_bwd_kernel (lane j ends with d(3, j) + d(2, j - 1) + d(1, j - 2) + d(0, j - 3), the diagonal of
+                        // (key_j, row 3); lanes 13 .. 15 hold a second value for the six elements that fall off the row's right edge)
+                        float v[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = (key < Tk && !(qedge && r0 + qv + r >= Tq)) ? dst[qt][r] : 0.f;
+                        auto shr1 = [](float x) {
+                            return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x111, 0xf, 0xf, true));
+                        };
+                        float t = v[0];
+                        t = v[1] + shr1(t);
+                        t = v[2] + shr1(t);
+                        t = v[3] + shr1(t);
+                        if (t != 0.f) atomicAdd(&ddiag[js - 3], att_drel_fix(t));
+                        const float w1 = li >= 14 ? v[1] : 0.f, w2 = li == 15 ? v[2] : 0.f;
+                        float wv = li >= 13 ? v[0] : 0.f;
+                        wv += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, w1), 0x101, 0xf, 0xf, true));   // row_shl:1
+                        wv += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, w2), 0x102, 0xf, 0xf, true));   // row_shl:2
+                        if (li >= 13 && wv != 0.f) atomicAdd(&ddiag[js], att_drel_fix(wv));
+                    }
+                }
             }
         }
         if (c + 1 < nch) put(lds + ((c + 1) & 1) * BUF, r0 + AL_QC);
@@ -367,8 +443,25 @@ DEVINL void al_dkdv_body(const AttnArgs& a, int nkblk) {
         }
         const bool live = key < Tk;
         const long krow = ((long)m * Tk + min(key, Tk - 1)) * a.dkv_ld + h * ATT_D;
-        att_store_tile(dk, ATT_SCALE, a.dk + krow, live, g);
+        att_store_tile(dk, oscale, a.dk + krow, live, g);
         att_store_tile(dv, 1.0f, a.dv + krow, live, g);
+    }
+    if (REL && a.drel) {
+        // diagonals -> buckets, still in fixed point (any order gives the same integer), then ONE conversion to fp32 per bucket.  With a
+        // partial buffer the workgroup stores its nbuckets sums, zeros included, as the partial of (item, key block); the launcher adds
+        // the partials into drel in that order (reduce_partials).  Without one: one float atomic per bucket, a counted lapse.
+        __syncthreads();
+        const int d0 = kblk * AL_ROWS - 36;
+        for (int j = 36 + tid; j < nslot; j += AL_THREADS) {
+            const unsigned long long v = ddiag[j];
+            if (v && d0 + j < Tq + Tk - 1) atomicAdd(&bsum[a.rel_bucket[d0 + j]], v);
+        }
+        __syncthreads();
+        for (int b = tid; b < a.nbuckets; b += AL_THREADS) {
+            const float v = (float)(long long)bsum[b] * (1.0f / ATT_DREL_FIX);
+            if (a.drel_part) a.drel_part[(((long)m * nkblk + kblk) * a.nbuckets + b) * H + h] = v;
+            else if (v != 0.f) atomicAdd(a.drel + b * H + h, v);
+        }
     }
 }
 __global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dkdv_kernel(AttnArgs a, int nkblk) { al_dkdv_body<false, false>(a, nkblk); }
@@ -376,9 +469,13 @@ template <bool DROP>
 __global__ __launch_bounds__(AL_THREADS, 4) void attn_xlong_dkdv_kernel(AttnArgs a, int nkblk) {
     al_dkdv_body<true, DROP>(a, nkblk);
 }
+template <bool DROP>
+__global__ __launch_bounds__(AL_THREADS, 4) void attn_rlong_dkdv_kernel(AttnArgs a, int nkblk) {
+    al_dkdv_body<false, DROP, true>(a, nkblk);
+}
 
 // ---------------- backward: dQ (phase 2 of attn_bwd_kernel, the keys streamed) ----------------
-template <bool XL, bool DROP>
+template <bool XL, bool DROP, bool REL = false>
 DEVINL void al_dq_body(const AttnArgs& a, int nqb) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int NL = AL_KV * 8 / AL_THREADS;
@@ -405,6 +502,10 @@ DEVINL void al_dq_body(const AttnArgs& a, int nqb) {
     const bool active = q0 < Tq;
     float* lse2 = reinterpret_cast<float*>(lds + 2 * BUF);      // [AL_ROWS] lse * log2 e, then [AL_ROWS] delta
     float* Dq = lse2 + AL_ROWS;
+    const float sl2 = REL ? a.scale * LOG2EF : SCALE_LOG2E;
+    const float oscale = REL ? a.scale : ATT_SCALE;
+    const float* dbias = Dq + AL_ROWS + (Tq - 1 - min(q, Tq - 1));      // + key: the lane's row of the bias (see al_fwd_body)
+    if (REL) al_fill_bias(Dq + AL_ROWS, a, h, 0, Tq + Tk - 1, Tq + Tk + 31, tid);
     u32x4_t rk[NL], rv[NL];
     al_load<AL_KV>(rk, kbase, a.kv_ld, 0, Tk, tid);
     al_load<AL_KV>(rv, vbase, a.kv_ld, 0, Tk, tid);
@@ -454,8 +555,11 @@ DEVINL void al_dq_body(const AttnArgs& a, int nqb) {
                         dp = mfma16(al_rows_frag(bufA + off.r[s] + dAB + blk + kt * 2048), dof[s], dp);
                     }
                     // A rows = keys, B cols = queries -> acc[r] = S[key = 4g + r][q = li]
+                    const float* bp = dbias + k0 + kb * 32 + kt * 16 + 4 * g;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) dst[kt][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[r], SCALE_LOG2E, -my_lse));
+                    for (int r = 0; r < 4; ++r)
+                        dst[kt][r] = REL ? __builtin_amdgcn_exp2f(__builtin_fmaf(sa[r], sl2, bp[r]) - my_lse)
+                                         : __builtin_amdgcn_exp2f(__builtin_fmaf(sa[r], SCALE_LOG2E, -my_lse));
                     if (edge) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
@@ -483,12 +587,16 @@ DEVINL void al_dq_body(const AttnArgs& a, int nqb) {
         __syncthreads();
     }
     if (active)
-        att_store_tile(dq, ATT_SCALE, a.dq + (qr0 + min(q, Tq - 1)) * a.dq_ld + h * ATT_D, q < Tq, g);
+        att_store_tile(dq, oscale, a.dq + (qr0 + min(q, Tq - 1)) * a.dq_ld + h * ATT_D, q < Tq, g);
 }
 __global__ __launch_bounds__(AL_THREADS, 4) void attn_long_dq_kernel(AttnArgs a, int nqb) { al_dq_body<false, false>(a, nqb); }
 template <bool DROP>
 __global__ __launch_bounds__(AL_THREADS, 4) void attn_xlong_dq_kernel(AttnArgs a, int nqb) {
     al_dq_body<true, DROP>(a, nqb);
+}
+template <bool DROP>
+__global__ __launch_bounds__(AL_THREADS, 4) void attn_rlong_dq_kernel(AttnArgs a, int nqb) {
+    al_dq_body<false, DROP, true>(a, nqb);
 }
 
 // what the long kernels take: dense rows, no mask, no bias, no dropout, the default scale
@@ -613,4 +721,101 @@ extern "C" int uniir_attention_bwd_long(const void* q, int64_t q_ld, const void*
     a.dq_ld = dq_ld; a.dkv_ld = dkv_ld;
     a.drop_p = drop_p; a.drop_seed = drop_seed;
     return launch_attn_xlong_bwd(a, batch, (hipStream_t)stream);
+}
+
+// ---------------- T5-style self-attention (uniir_attention_rel_fwd_long / _rel_bwd_long) ----------------
+// LDS behind the buffers of the plain kernels: the bias table of the forward and dQ, the fixed-point sums and the bias slice of dK / dV
+static int al_rel_tab_bytes(int seq) { return (2 * seq + 32) * 4; }
+static int al_rel_dkdv_bytes(int seq) { return 64 * 8 + (seq + 164) * 12; }
+
+static int launch_attn_rlong_fwd(const AttnArgs& a, int batch, hipStream_t st) {
+    const int nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
+    const long grid = (long)batch * a.H * nqb;
+    if (grid > 0x7fffffffL) return UNIIR_ESHAPE;
+    static PerDeviceOnce attr;
+    if (attr.first()) {
+        const int mx = AL_FWD_LDS + al_rel_tab_bytes(1024);
+        (void)hipFuncSetAttribute((const void*)attn_rlong_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
+        (void)hipFuncSetAttribute((const void*)attn_rlong_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
+    }
+    const int sm = AL_FWD_LDS + al_rel_tab_bytes(a.Tq);
+    if (a.drop_p > 0.f) hipLaunchKernelGGL(attn_rlong_fwd_kernel<true>, dim3((unsigned)grid), dim3(AL_THREADS), sm, st, a, nqb);
+    else hipLaunchKernelGGL(attn_rlong_fwd_kernel<false>, dim3((unsigned)grid), dim3(AL_THREADS), sm, st, a, nqb);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+static int launch_attn_rlong_bwd(const AttnArgs& a, int batch, int nkblk, hipStream_t st) {
+    const int nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
+    const long gk = (long)batch * a.H * nkblk, gq = (long)batch * a.H * nqb;
+    if (gk > 0x7fffffffL || gq > 0x7fffffffL) return UNIIR_ESHAPE;
+    static PerDeviceOnce attr;
+    if (attr.first()) {
+        const int mk = AL_DKDV_LDS + al_rel_dkdv_bytes(1024), mq = AL_DQ_LDS + al_rel_tab_bytes(1024);
+        (void)hipFuncSetAttribute((const void*)attn_rlong_dkdv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, mk);
+        (void)hipFuncSetAttribute((const void*)attn_rlong_dkdv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mk);
+        (void)hipFuncSetAttribute((const void*)attn_rlong_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, mq);
+        (void)hipFuncSetAttribute((const void*)attn_rlong_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mq);
+    }
+    const int sk = AL_DKDV_LDS + al_rel_dkdv_bytes(a.Tq), sq = AL_DQ_LDS + al_rel_tab_bytes(a.Tq);
+    const bool drop = a.drop_p > 0.f;
+    if (drop) hipLaunchKernelGGL(attn_rlong_dkdv_kernel<true>, dim3((unsigned)gk), dim3(AL_THREADS), sk, st, a, nkblk);
+    else hipLaunchKernelGGL(attn_rlong_dkdv_kernel<false>, dim3((unsigned)gk), dim3(AL_THREADS), sk, st, a, nkblk);
+    HIP_LAUNCH_CHECK();
+    if (drop) hipLaunchKernelGGL(attn_rlong_dq_kernel<true>, dim3((unsigned)gq), dim3(AL_THREADS), sq, st, a, nqb);
+    else hipLaunchKernelGGL(attn_rlong_dq_kernel<false>, dim3((unsigned)gq), dim3(AL_THREADS), sq, st, a, nqb);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+// uniir_attention_rel_fwd / _rel_bwd for 1 <= seq <= 1024: every size runs the streaming kernels above, nothing is forwarded to the
+// 512-token kernels.
+extern "C" int uniir_attention_rel_fwd_long(const void* qkv, void* out, float* lse, const float* rel_emb, const int32_t* rel_bucket,
+                                            int32_t nbuckets, float scale, int32_t batch, int32_t seq, int32_t heads, float drop_p,
+                                            uint32_t drop_seed, void* stream) {
+    if (!qkv || !out || !lse || !rel_emb || !rel_bucket || batch < 0 || heads <= 0 || nbuckets <= 0 || nbuckets > 64)
+        return UNIIR_EINVAL;
+    if (!(drop_p >= 0.f && drop_p < 1.f)) return UNIIR_EINVAL;
+    if (batch == 0) return UNIIR_OK;
+    if (seq < 1 || seq > 1024) return UNIIR_ESHAPE;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
+    const long W = (long)heads * ATT_D;
+    AttnArgs a = {};
+    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
+    a.q_ld = a.kv_ld = 3 * W; a.out = (unsigned short*)out; a.out_ld = W; a.lse = lse;
+    a.Tq = a.Tk = seq; a.H = heads; a.causal = 0; a.scale = scale;
+    a.rel_emb = rel_emb; a.rel_bucket = rel_bucket; a.nbuckets = nbuckets;
+    a.drop_p = drop_p; a.drop_seed = drop_seed;
+    return launch_attn_rlong_fwd(a, batch, (hipStream_t)stream);
+}
+
+extern "C" int uniir_attention_rel_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
+                                            const float* rel_emb, const int32_t* rel_bucket, int32_t nbuckets, float scale,
+                                            float* drel, int32_t batch, int32_t seq, int32_t heads, float drop_p, uint32_t drop_seed,
+                                            void* stream) {
+    if (!qkv || !out || !dout || !lse || !dqkv || !rel_emb || !rel_bucket || batch < 0 || heads <= 0 || nbuckets <= 0 ||
+        nbuckets > 64)
+        return UNIIR_EINVAL;
+    if (!(drop_p >= 0.f && drop_p < 1.f)) return UNIIR_EINVAL;
+    if (batch == 0) return UNIIR_OK;
+    if (seq < 1 || seq > 1024) return UNIIR_ESHAPE;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)dqkv & 15)) return UNIIR_EALIGN;
+    const long W = (long)heads * ATT_D;
+    const int nkblk = (seq + AL_ROWS - 1) / AL_ROWS;
+    if ((long)batch * heads * nkblk > 0x7fffffffL) return UNIIR_ESHAPE;          // before the scratch is asked for: a refused call counts nothing
+    AttnArgs a = {};
+    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
+    a.q_ld = a.kv_ld = 3 * W; a.out = (unsigned short*)const_cast<void*>(out); a.out_ld = W;
+    a.lse = const_cast<float*>(lse); a.dout = (const unsigned short*)dout;
+    a.dq = (unsigned short*)dqkv; a.dk = a.dq + W; a.dv = a.dq + 2 * W; a.dq_ld = a.dkv_ld = 3 * W;
+    a.Tq = a.Tk = seq; a.H = heads; a.causal = 0; a.scale = scale;
+    a.rel_emb = rel_emb; a.rel_bucket = rel_bucket; a.nbuckets = nbuckets; a.drel = drel;
+    a.drop_p = drop_p; a.drop_seed = drop_seed;
+    // one workgroup per (item, key block, head) stores its bucket sums in the stream's scratch as [item][key block][bucket][head]; they
+    // are added into drel in that order below.  drel is accumulated, not overwritten: the layers of a T5 stack share one bias table.
+    const long nparts = (long)batch * nkblk;
+    if (drel) a.drel_part = reduce_scratch((hipStream_t)stream, nparts * heads * nbuckets * 4);
+    const int rc = launch_attn_rlong_bwd(a, batch, nkblk, (hipStream_t)stream);
+    if (rc || !a.drel_part) return rc;
+    return reduce_partials(a.drel_part, (int)nparts, (long)nbuckets * heads, nbuckets * heads, drel, nullptr, nullptr, 0, (hipStream_t)stream);
 }

@@ -2,7 +2,8 @@
 methods, batch / output dictionaries and state-dict keys (`clip_model.*` without `text_projection`, `t5_layers.block...`);
 the towers without pooling, the T5 fusion stack, the mean pooling and the loss run on libuniir_hip.so (MI355X).
 
-Reference lines mirrored: __init__ :63-110 (ViT-B/32 -> T5 d_model 512, ViT-L/14 -> 768; 2 layers, 12 heads, d_kv 64,
+Reference lines mirrored: __init__ :63-110 (ViT-B/32 -> T5 d_model 512, ViT-L/14 -> 768 -- and, beyond the reference,
+ViT-L/14@336px -> 768: 577 image tokens, 654 fused ones, the streaming relative-bias attention; 2 layers, 12 heads, d_kv 64,
 T5Config defaults d_ff 2048 / ReLU / 32 buckets), encode_text :148-156, encode_image :158-159, encode_multimodal_input
 :161-192 (the masks are accepted and unused, like there), compute_inbatch_contrastive_loss :194-265 (identical to
 CLIP_SF's, incl. the hard-negative branch), encode_mbeir_batch :272-298.  T5 dropout 0.1 is not applied.
@@ -16,7 +17,7 @@ from uniir_amd.clipff_model import FusionFn, t5_param_shapes
 from uniir_amd.flat_store import FlatStore
 from uniir_amd.losses import HardNegNCEFn, InBatchNCEFn
 
-_T5_DMODEL = {"ViT-B/32": 512, "ViT-L/14": 768}
+_T5_DMODEL = {"ViT-B/32": 512, "ViT-L/14": 768, "ViT-L/14@336px": 768}      # @336px: 77 + 577 = 654 fused tokens
 
 
 class _T5Group:
@@ -40,7 +41,7 @@ class CLIPFeatureFusion(nn.Module):
         t5.update(t5_config or {})
         self.t5_dropout = float(t5["dropout_rate"])     # T5Config() default; active in train mode only
         if t5["d_model"] is None:
-            raise NotImplementedError("Only ViT-B/32 and ViT-L/14 are supported.")
+            raise NotImplementedError("Only ViT-B/32, ViT-L/14 and ViT-L/14@336px are supported.")
         self.t5_heads, self.t5_layers_n, self._t5_cfg = t5["num_heads"], t5["num_layers"], t5
         self._t5_shapes = t5_param_shapes(t5["d_model"], t5["num_heads"], 64, t5["d_ff"], t5["num_layers"])
         g = torch.Generator().manual_seed(1)
