@@ -588,14 +588,14 @@ class _TowerFn(torch.autograd.Function):
         lib = _lib.load()
         desc = model.tower_desc(which, half=half)
         desc.pool_last_block = model.pool_last_value()
-        if desc.pool_last_block and desc.tokens > 512 and (which, desc.pool_last_block) not in model._full_last_logged:
+        if desc.pool_last_block and desc.tokens > ops.ATT_RESIDENT_MAX and (which, desc.pool_last_block) not in model._full_last_logged:
             model._full_last_logged.add((which, desc.pool_last_block))
             if desc.pool_last_block == 2:
                 model.stash_log.append(f"{which} tower, {desc.tokens} tokens: pooled last block on the one-query streaming path "
                                        f"(pool_last_block_long): same embeddings, 1/{desc.layers} less block work")
             else:
                 # (csrc/tower.hip plan(): the resident one-query attention of the pooled block holds all keys in LDS, 512 at the most)
-                model.stash_log.append(f"{which} tower, {desc.tokens} tokens: full last block (pool_last_block needs <= 512 tokens); "
+                model.stash_log.append(f"{which} tower, {desc.tokens} tokens: full last block (pool_last_block needs <= {ops.ATT_RESIDENT_MAX} tokens); "
                                        f"same embeddings, 1/{desc.layers} more block work")
         # recompute_blocks: only the block inputs are kept (uniir_clip_tower.recompute); a forward-only call has no stash to shrink
         recompute = need_grad and bool(model.recompute_blocks)

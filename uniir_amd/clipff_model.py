@@ -58,8 +58,8 @@ def _table(T, dev):
 
 
 def _rel_entry(which, T):
-    """the resident kernels up to 512 tokens, the streaming ones above (ViT-L/14@336px: 77 + 577 = 654 fused tokens)"""
-    return f"uniir_attention_rel_{which}" + ("_long" if T > 512 else "")
+    """the resident kernels up to ops.ATT_RESIDENT_MAX tokens, the streaming ones above (ViT-L/14@336px: 77 + 577 = 654 fused tokens)"""
+    return f"uniir_attention_rel_{which}" + ("_long" if T > ops.ATT_RESIDENT_MAX else "")
 
 
 def _rms(st, x, name, R, D, out_f32=False):

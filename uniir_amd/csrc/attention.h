@@ -1,5 +1,7 @@
 // Shared definitions of the attention kernels (attention.hip: the general 16-row-tile kernels; attention_pair.hip: the persistent
-// pair-tile kernels for plain self-attention): argument block, LDS tile layout, fragment helpers.
+// pair-tile kernels for plain self-attention; attention_long.hip: the streaming kernels; attention_one.hip: the one-query backward):
+// argument block, LDS tile layout, fragment helpers -- and, at the end, the host layer of all four files and tower.hip: the two
+// sequence limits, the prototypes that cross files, the entry points' check helpers, the AttnArgs builders and the launch helper.
 #pragma once
 #include "common.h"
 #include "../../include/uniir_hip.h"
@@ -224,4 +226,92 @@ extern int g_att_exp;
 #define ATT_STAMP(i) do {} while (0)
 #define ATT_EXP(bit) 0
 #endif
+
+// ---------------- the host layer shared by attention.hip, attention_pair.hip, attention_long.hip, attention_one.hip and tower.hip ----------------
+#define ATT_SEQ_MAX 512           // a head's K / V (Q / dO) whole in LDS: every kernel of attention.hip and attention_pair.hip
+#define ATT_LONG_SEQ_MAX 1024     // the streaming kernels (attention_long.hip) and the one-query backward (attention_one.hip)
+
+// launchers that cross files
+int launch_attn_bwd_pair(const AttnArgs& a, int batch, hipStream_t st);      // attention_pair.hip; 1 = shape not taken
+// attention_long.hip: plain dense self-attention up to ATT_LONG_SEQ_MAX tokens (one operand streamed through LDS); everything else is UNIIR_ESHAPE
+int launch_attn_long_fwd(const AttnArgs& a, int batch, hipStream_t st, bool f16);
+int launch_attn_long_bwd(const AttnArgs& a, int batch, hipStream_t st);
+// attention_one.hip: the backward of ONE dense query row per (item, head) against 1 .. ATT_LONG_SEQ_MAX dense keys in one pass over K and V
+int launch_attn_one_bwd(const AttnArgs& a, int batch, hipStream_t st);
+
+// what tower.hip calls (attention.hip).  The forward: row_off = nullptr for dense rows; f16 = the 16-bit tensors are fp16
+int attention_fwd_impl(const void* qkv, void* out, float* lse, const int32_t* row_off, int32_t batch, int32_t seq, int32_t heads,
+                       int32_t causal, int f16, void* stream);
+// one query row per item: the pooled last block
+int attention_pooled_fwd_impl(const void* q, const void* k, const void* v, int64_t kv_ld, void* out, float* lse, const int32_t* klen,
+                              int32_t klen_add, const int32_t* kv_row_off, int32_t batch, int32_t tk, int32_t heads, int f16,
+                              void* stream);
+int attention_pooled_bwd_impl(const void* q, const void* k, const void* v, int64_t kv_ld, const void* out, const void* dout,
+                              const float* lse, const int32_t* klen, int32_t klen_add, const int32_t* kv_row_off, void* dq,
+                              int64_t dq_ld, void* dk, void* dv, int64_t dkv_ld, int32_t batch, int32_t tk, int32_t heads, void* stream);
+
+// the tail of uniir_attention_rel_bwd and _rel_bwd_long (attention.hip): scratch for the bias gradient's partials, `launch`, their sum
+int attention_rel_bwd_tail(AttnArgs& a, float* drel, long nparts, int batch, hipStream_t st,
+                           int (*launch)(const AttnArgs&, int, hipStream_t));
+
+// The checks of the entry points.  Which of them an entry point makes, and in which order, differs on purpose (DESIGN.md section 3
+// has the table; tests/test_attention_refusals_host.py pins it).
+template <class... P>
+inline bool att_null(const P*... p) { return (!p || ...); }
+template <class... P>
+inline bool att_misaligned16(const P*... p) { return (((uintptr_t)p | ...) & 15) != 0; }
+template <class... L>
+inline bool att_ld_not8(L... ld) { return ((ld | ...) & 7) != 0; }          // 16-byte pieces: leading dimensions in multiples of 8 elements
+inline bool att_bad_drop(float p) { return p < 0.f || p >= 1.f; }            // a NaN passes (and runs the kernels without dropout) ...
+inline bool att_bad_drop_nan(float p) { return !(p >= 0.f && p < 1.f); }     // ... in the older entry points; the _long ones refuse it
+
+// The two layouts of AttnArgs.  Packed [q|k|v] self-attention (in_proj's output), optionally on packed rows (row_off) ...
+inline AttnArgs att_args_packed(const void* qkv, const void* out, const float* lse, int seq, int heads, int causal, float scale,
+                                const int* row_off = nullptr) {
+    const long W = (long)heads * ATT_D;
+    AttnArgs a = {};
+    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
+    a.q_ld = a.kv_ld = 3 * W;
+    a.out = (unsigned short*)const_cast<void*>(out); a.out_ld = W; a.lse = const_cast<float*>(lse);
+    a.Tq = a.Tk = seq; a.H = heads; a.causal = causal; a.scale = scale; a.row_off = row_off;
+    return a;
+}
+inline void att_args_packed_bwd(AttnArgs& a, const void* dout, void* dqkv) {
+    const long W = (long)a.H * ATT_D;
+    a.dout = (const unsigned short*)dout;
+    a.dq = (unsigned short*)dqkv; a.dk = a.dq + W; a.dv = a.dq + 2 * W;
+    a.dq_ld = a.dkv_ld = 3 * W;
+}
+inline void att_args_rel(AttnArgs& a, const float* rel_emb, const int* rel_bucket, int nbuckets) {
+    a.rel_emb = rel_emb; a.rel_bucket = rel_bucket; a.nbuckets = nbuckets;
+}
+// ... and separate Q and K | V (cross-attention, one query row), the default scale
+inline AttnArgs att_args_qkv(const void* q, long q_ld, const void* k, const void* v, long kv_ld, const void* out, long out_ld,
+                             const float* lse, int tq, int tk, int heads, const int* key_len = nullptr, int causal = 0) {
+    AttnArgs a = {};
+    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
+    a.q_ld = q_ld; a.kv_ld = kv_ld;
+    a.out = (unsigned short*)const_cast<void*>(out); a.out_ld = out_ld; a.lse = const_cast<float*>(lse); a.klen = key_len;
+    a.Tq = tq; a.Tk = tk; a.H = heads; a.causal = causal; a.scale = ATT_SCALE;
+    return a;
+}
+inline void att_args_qkv_bwd(AttnArgs& a, const void* dout, void* dq, long dq_ld, void* dk, void* dv, long dkv_ld) {
+    a.dout = (const unsigned short*)dout;
+    a.dq = (unsigned short*)dq; a.dk = (unsigned short*)dk; a.dv = (unsigned short*)dv;
+    a.dq_ld = dq_ld; a.dkv_ld = dkv_ld;
+}
+inline void att_args_q_rows(AttnArgs& a, const int* q_row_off, int q_only) { a.row_off = q_row_off; a.row_off_q_only = q_only; }
+inline void att_args_kv_rows(AttnArgs& a, const int* kv_row_off, int klen_add) { a.kv_row_off = kv_row_off; a.klen_add = klen_add; }
+inline void att_args_drop(AttnArgs& a, float drop_p, unsigned drop_seed) { a.drop_p = drop_p; a.drop_seed = drop_seed; }
+
+// One launch of kernel K.  A kernel with dynamic LDS (max_lds > 0) gets its limit raised to max_lds before its first launch on a
+// device: every kernel, i.e. every instantiation of this template, has its own once-per-device flag.
+template <auto K, class... A>
+inline int att_launch(int max_lds, dim3 grid, dim3 block, int lds, hipStream_t st, const A&... args) {
+    static PerDeviceOnce attr;
+    if (max_lds > 0 && attr.first()) (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
 

@@ -490,73 +490,44 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : 3) void attn_bwd_kernel(AttnArg
 //   forward : 257 tokens 0.783 -> 0.760 ms, 197: 0.488 -> 0.487, 77 causal: 0.146 -> 0.132, 50: 0.116 -> 0.095   => always batched
 //   backward: 257 tokens 2.026 -> 2.021 ms, 197: 1.399 -> 1.446 (worse), 77: 0.388 -> 0.359, 50: 0.336 -> 0.294   => batched up to 128 tokens
 static int attn_legacy_stage(bool backward, int tmax) { return backward && tmax > 128; }
+// dynamic LDS of the two kernels; a kernel's limit is the size at ATT_SEQ_MAX x ATT_SEQ_MAX with the bias
+static int attn_fwd_lds(int Tq, int Tk, bool rel) { return 2 * ((Tk + 31) & ~31) * 128 + (rel ? (Tq + Tk) * 4 : 0); }
+static int attn_bwd_lds(int Tq, int Tk, bool rel) {
+    const int Tqp = (Tq + 31) & ~31, Tkp = (Tk + 31) & ~31;
+    return 2 * (Tqp > Tkp ? Tqp : Tkp) * 128 + 2 * Tqp * 4 + (rel ? 64 * 8 + (Tq + Tk) * 12 : 0);
+}
 static int launch_attn_fwd(const AttnArgs& a0, int batch, hipStream_t st, bool f16 = false) {
     AttnArgs a = a0;
 #ifdef UNIIR_EXP_BUILD
     a.stamps = g_att_stamps; a.exp = g_att_exp;
 #endif
     a.legacy_stage = attn_legacy_stage(false, a.Tk);
-    const int Tkp = (a.Tk + 31) & ~31;
-    const int sm = 2 * Tkp * 128 + (a.rel_emb ? (a.Tq + a.Tk) * 4 : 0);
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-        const int big = 2 * 512 * 128 + 1024 * 4;
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-    }
+    const int sm = attn_fwd_lds(a.Tq, a.Tk, a.rel_emb != nullptr), big = attn_fwd_lds(ATT_SEQ_MAX, ATT_SEQ_MAX, true);
     const dim3 g(batch * a.H), b(ATT_THREADS);
     const bool drop = a.drop_p > 0.f;
-    if (f16) {          // the fp16 forward of the embedding towers: plain / causal / packed rows only
-        if (a.rel_emb || drop) return UNIIR_EUNSUPPORTED;
-        static PerDeviceOnce attr16;
-        if (attr16.first())
-            (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      2 * 512 * 128 + 1024 * 4);
-        hipLaunchKernelGGL((attn_fwd_kernel<false, false, true>), g, b, sm, st, a);
-        HIP_LAUNCH_CHECK();
-        return UNIIR_OK;
+    if (!f16) {
+        if (!a.rel_emb && !drop) return att_launch<attn_fwd_kernel<false, false>>(big, g, b, sm, st, a);
+        if (!a.rel_emb) return att_launch<attn_fwd_kernel<false, true>>(big, g, b, sm, st, a);
+        if (!drop) return att_launch<attn_fwd_kernel<true, false>>(big, g, b, sm, st, a);
+        return att_launch<attn_fwd_kernel<true, true>>(big, g, b, sm, st, a);
     }
-    if (a.rel_emb && drop) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), g, b, sm, st, a);
-    else if (a.rel_emb) hipLaunchKernelGGL((attn_fwd_kernel<true, false>), g, b, sm, st, a);
-    else if (drop) hipLaunchKernelGGL((attn_fwd_kernel<false, true>), g, b, sm, st, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, false>), g, b, sm, st, a);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
+    // the fp16 forward of the embedding towers: plain / causal / packed rows only
+    if (a.rel_emb || drop) return UNIIR_EUNSUPPORTED;
+    return att_launch<attn_fwd_kernel<false, false, true>>(big, g, b, sm, st, a);
 }
 template <int NT>
 static int launch_attn_bwd_nt(const AttnArgs& a, int batch, int sm, hipStream_t st) {
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-        const int big = 2 * 512 * 128 + 2 * 512 * 4 + 64 * 8 + 1024 * 12;      // 147968 of the 163840 bytes of a workgroup
-        (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<false, false, false, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<false, true, false, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<true, false, false, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<true, true, false, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<false, false, true, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<false, true, true, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-    }
+    const int big = attn_bwd_lds(ATT_SEQ_MAX, ATT_SEQ_MAX, true);      // 147968 of the 163840 bytes of a workgroup
     const dim3 g(batch * a.H), b(NT);
     const bool drop = a.drop_p > 0.f;
     if (a.causal && a.rel_emb) return UNIIR_ESHAPE;
-    if (a.causal && drop) hipLaunchKernelGGL((attn_bwd_kernel<false, true, true, NT>), g, b, sm, st, a);
-    else if (a.causal) hipLaunchKernelGGL((attn_bwd_kernel<false, false, true, NT>), g, b, sm, st, a);
-    else if (a.rel_emb && drop) hipLaunchKernelGGL((attn_bwd_kernel<true, true, false, NT>), g, b, sm, st, a);
-    else if (a.rel_emb) hipLaunchKernelGGL((attn_bwd_kernel<true, false, false, NT>), g, b, sm, st, a);
-    else if (drop) hipLaunchKernelGGL((attn_bwd_kernel<false, true, false, NT>), g, b, sm, st, a);
-    else hipLaunchKernelGGL((attn_bwd_kernel<false, false, false, NT>), g, b, sm, st, a);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
+    if (!a.causal && !a.rel_emb && !drop) return att_launch<attn_bwd_kernel<false, false, false, NT>>(big, g, b, sm, st, a);
+    if (!a.causal && !a.rel_emb) return att_launch<attn_bwd_kernel<false, true, false, NT>>(big, g, b, sm, st, a);
+    if (!a.causal && !drop) return att_launch<attn_bwd_kernel<true, false, false, NT>>(big, g, b, sm, st, a);
+    if (!a.causal) return att_launch<attn_bwd_kernel<true, true, false, NT>>(big, g, b, sm, st, a);
+    if (!drop) return att_launch<attn_bwd_kernel<false, false, true, NT>>(big, g, b, sm, st, a);
+    return att_launch<attn_bwd_kernel<false, true, true, NT>>(big, g, b, sm, st, a);
 }
-int launch_attn_bwd_pair(const AttnArgs& a, int batch, hipStream_t st);      // attention_pair.hip; 1 = shape not taken
-// attention_long.hip: plain dense self-attention of 513 .. 1024 tokens (one operand streamed through LDS); everything else is UNIIR_ESHAPE
-int launch_attn_long_fwd(const AttnArgs& a, int batch, hipStream_t st, bool f16);
-int launch_attn_long_bwd(const AttnArgs& a, int batch, hipStream_t st);
-// attention_one.hip: the backward of ONE dense query row per (item, head) against 1 .. 1024 dense keys in one pass over K and V
-int launch_attn_one_bwd(const AttnArgs& a, int batch, hipStream_t st);
-#define ATT_SEQ_MAX 512           // a head's K / V (Q / dO) whole in LDS: every kernel of this file and of attention_pair.hip
-#define ATT_LONG_SEQ_MAX 1024     // the streaming kernels
 static int launch_attn_bwd(const AttnArgs& a0, int batch, hipStream_t st) {
     AttnArgs a = a0;
 #ifdef UNIIR_EXP_BUILD
@@ -568,205 +539,145 @@ static int launch_attn_bwd(const AttnArgs& a0, int batch, hipStream_t st) {
     }
     const int tmax = a.Tq > a.Tk ? a.Tq : a.Tk;
     a.legacy_stage = attn_legacy_stage(true, tmax);
-    const int Tqp = (a.Tq + 31) & ~31, Tkp = (a.Tk + 31) & ~31;
-    const int Tmax = Tqp > Tkp ? Tqp : Tkp;
-    const int sm = 2 * Tmax * 128 + 2 * Tqp * 4 + (a.rel_emb ? 64 * 8 + (a.Tq + a.Tk) * 12 : 0);
+    const int Tmax = (tmax + 31) & ~31;
+    const int sm = attn_bwd_lds(a.Tq, a.Tk, a.rel_emb != nullptr);
     bool six = tmax <= 128;
     if (six && (Tmax * 8 + 383) / 384 > 8) six = false;      // stage_two holds <= 8 loads per thread and slice: 384 threads stop at 384 tokens
     return six ? launch_attn_bwd_nt<384>(a, batch, sm, st) : launch_attn_bwd_nt<512>(a, batch, sm, st);
 }
 
-// tower.hip's forward: row_off = nullptr for dense rows; f16 = the 16-bit tensors are fp16
+// ---------------- packed [q|k|v] self-attention ----------------
+// Dense rows (row_off == nullptr: plain up to ATT_LONG_SEQ_MAX tokens, causal up to ATT_SEQ_MAX) or packed rows (up to ATT_SEQ_MAX):
+// uniir_attention_fwd, _fwd_f16 (f16 = the 16-bit tensors are fp16), _fwd_packed and tower.hip's forward
 int attention_fwd_impl(const void* qkv, void* out, float* lse, const int32_t* row_off, int32_t batch, int32_t seq, int32_t heads,
                        int32_t causal, int f16, void* stream) {
-    if (!qkv || !out || !lse || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_null(qkv, out, lse) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
     if (seq < 1 || seq > ((causal || row_off) ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX)) return UNIIR_ESHAPE;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
-    const long W = (long)heads * ATT_D;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
-    a.q_ld = a.kv_ld = 3 * W;
-    a.out = (unsigned short*)out; a.out_ld = W; a.lse = lse; a.klen = nullptr; a.row_off = row_off;
-    a.Tq = a.Tk = seq; a.H = heads; a.causal = causal; a.scale = ATT_SCALE;
+    if (att_misaligned16(qkv, out)) return UNIIR_EALIGN;
+    const AttnArgs a = att_args_packed(qkv, out, lse, seq, heads, causal, ATT_SCALE, row_off);
     if (seq > ATT_SEQ_MAX) return launch_attn_long_fwd(a, batch, (hipStream_t)stream, f16 != 0);
     return launch_attn_fwd(a, batch, (hipStream_t)stream, f16 != 0);
 }
+// ... and the backward of the same: uniir_attention_bwd, _bwd_packed
+static int attention_bwd_impl(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, const int32_t* row_off,
+                              int32_t batch, int32_t seq, int32_t heads, int32_t causal, void* stream) {
+    if (att_null(qkv, out, dout, lse, dqkv) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (batch == 0) return UNIIR_OK;
+    if (seq < 1 || seq > ((causal || row_off) ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX)) return UNIIR_ESHAPE;
+    if (att_misaligned16(qkv, out, dout, dqkv)) return UNIIR_EALIGN;
+    AttnArgs a = att_args_packed(qkv, out, lse, seq, heads, causal, ATT_SCALE, row_off);
+    att_args_packed_bwd(a, dout, dqkv);
+    if (seq > ATT_SEQ_MAX) return launch_attn_long_bwd(a, batch, (hipStream_t)stream);
+    return launch_attn_bwd(a, batch, (hipStream_t)stream);
+}
+
+extern "C" int uniir_attention_fwd(const void* qkv, void* out, float* lse, int32_t batch, int32_t seq,
+                                   int32_t heads, int32_t causal, void* stream) {
+    return attention_fwd_impl(qkv, out, lse, nullptr, batch, seq, heads, causal, 0, stream);
+}
+// the fp16 forward of the embedding towers on its own (fp16 qkv / out)
+extern "C" int uniir_attention_fwd_f16(const void* qkv, void* out, float* lse, const int32_t* row_off, int32_t batch, int32_t seq,
+                                       int32_t heads, int32_t causal, void* stream) {
+    return attention_fwd_impl(qkv, out, lse, row_off, batch, seq, heads, causal, 1, stream);
+}
+extern "C" int uniir_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
+                                   void* dqkv, int32_t batch, int32_t seq, int32_t heads, int32_t causal,
+                                   void* stream) {
+    return attention_bwd_impl(qkv, out, dout, lse, dqkv, nullptr, batch, seq, heads, causal, stream);
+}
+// packed rows: item m owns rows row_off[m] .. row_off[m + 1] - 1 of qkv / out (lengths <= max_seq); lse stays [batch][heads][max_seq].
+// The CLIP text tower on the live rows of its captions only (rows behind a caption's EOT never reach its pooled feature under the
+// causal mask, clip_sf.py:43-44): every live row's result is bitwise that of the dense call.
+extern "C" int uniir_attention_fwd_packed(const void* qkv, void* out, float* lse, const int32_t* row_off, int32_t batch,
+                                          int32_t max_seq, int32_t heads, int32_t causal, void* stream) {
+    if (!row_off) return UNIIR_EINVAL;
+    return attention_fwd_impl(qkv, out, lse, row_off, batch, max_seq, heads, causal, 0, stream);
+}
+extern "C" int uniir_attention_bwd_packed(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
+                                          const int32_t* row_off, int32_t batch, int32_t max_seq, int32_t heads, int32_t causal,
+                                          void* stream) {
+    if (!row_off) return UNIIR_EINVAL;
+    return attention_bwd_impl(qkv, out, dout, lse, dqkv, row_off, batch, max_seq, heads, causal, stream);
+}
+
+// ---------------- one query row per item ----------------
 // tower.hip's last block when only one row per item is pooled (the class token / the EOT row): ONE query row per item ([batch][W],
 // dense) against the item's keys and values.  K / V are columns of the block's qkv buffer (row stride kv_ld): dense [batch][tk]
 // rows with an optional key count klen[m] + klen_add (the causal text tower: the EOT index + 1), or the item's own packed rows
 // (kv_row_off).  A query row's result does not depend on the rows that share its tile, so out equals that row of the full call.
-// 513 .. 1024 keys (a 577-token vision tower): dense keys only (klen and kv_row_off NULL); the forward is the streaming body of
+// Above ATT_SEQ_MAX keys (a 577-token vision tower): dense keys only (klen and kv_row_off NULL); the forward is the streaming body of
 // attention_long.hip at Tq = 1 (row 0 of the full call, bit for bit), the backward the one-pass kernel of attention_one.hip.
 int attention_pooled_fwd_impl(const void* q, const void* k, const void* v, int64_t kv_ld, void* out, float* lse, const int32_t* klen,
                               int32_t klen_add, const int32_t* kv_row_off, int32_t batch, int32_t tk, int32_t heads, int f16,
                               void* stream) {
-    if (!q || !k || !v || !out || !lse || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_null(q, k, v, out, lse) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (tk < 1 || tk > ((klen || kv_row_off) ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX) || (kv_ld % 8)) return UNIIR_ESHAPE;
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
+    if (tk < 1 || tk > ((klen || kv_row_off) ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX) || att_ld_not8(kv_ld)) return UNIIR_ESHAPE;
+    if (att_misaligned16(q, k, v, out)) return UNIIR_EALIGN;
     const long W = (long)heads * ATT_D;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-    a.q_ld = W; a.kv_ld = kv_ld; a.out = (unsigned short*)out; a.out_ld = W; a.lse = lse;
-    a.klen = klen; a.klen_add = klen_add; a.kv_row_off = kv_row_off;
-    a.Tq = 1; a.Tk = tk; a.H = heads; a.causal = 0; a.scale = ATT_SCALE;
+    AttnArgs a = att_args_qkv(q, W, k, v, kv_ld, out, W, lse, 1, tk, heads, klen);
+    att_args_kv_rows(a, kv_row_off, klen_add);
     if (tk > ATT_SEQ_MAX) return launch_attn_long_fwd(a, batch, (hipStream_t)stream, f16 != 0);
     return launch_attn_fwd(a, batch, (hipStream_t)stream, f16 != 0);
 }
 int attention_pooled_bwd_impl(const void* q, const void* k, const void* v, int64_t kv_ld, const void* out, const void* dout,
                               const float* lse, const int32_t* klen, int32_t klen_add, const int32_t* kv_row_off, void* dq,
                               int64_t dq_ld, void* dk, void* dv, int64_t dkv_ld, int32_t batch, int32_t tk, int32_t heads, void* stream) {
-    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_null(q, k, v, out, dout, lse, dq, dk, dv) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (tk < 1 || tk > ((klen || kv_row_off) ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX) || (kv_ld % 8) || (dkv_ld % 8) || (dq_ld % 8))
-        return UNIIR_ESHAPE;
-    if (((uintptr_t)dq & 15) || ((uintptr_t)dk & 15) || ((uintptr_t)dv & 15)) return UNIIR_EALIGN;
+    if (tk < 1 || tk > ((klen || kv_row_off) ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX) || att_ld_not8(kv_ld, dkv_ld, dq_ld)) return UNIIR_ESHAPE;
+    if (att_misaligned16(dq, dk, dv)) return UNIIR_EALIGN;
     const long W = (long)heads * ATT_D;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-    a.q_ld = W; a.kv_ld = kv_ld; a.out = (unsigned short*)out; a.out_ld = W; a.lse = const_cast<float*>(lse);
-    a.klen = klen; a.klen_add = klen_add; a.kv_row_off = kv_row_off;
-    a.Tq = 1; a.Tk = tk; a.H = heads; a.causal = 0; a.scale = ATT_SCALE;
-    a.dout = (const unsigned short*)dout;
-    a.dq = (unsigned short*)dq; a.dk = (unsigned short*)dk; a.dv = (unsigned short*)dv;
-    a.dq_ld = dq_ld; a.dkv_ld = dkv_ld;
+    AttnArgs a = att_args_qkv(q, W, k, v, kv_ld, out, W, lse, 1, tk, heads, klen);
+    att_args_kv_rows(a, kv_row_off, klen_add);
+    att_args_qkv_bwd(a, dout, dq, dq_ld, dk, dv, dkv_ld);
     if (tk > ATT_SEQ_MAX) return launch_attn_one_bwd(a, batch, (hipStream_t)stream);
     return launch_attn_bwd(a, batch, (hipStream_t)stream);
 }
-
-// One query row per item on its own (include/uniir_hip.h): what the pooled last block of a tower calls, with dense keys.  tk <= 512 is
-// the resident kernel, 513 .. 1024 the streaming body at Tq = 1; the backward (attention_one.hip) is one kernel at every tk.
+// One query row per item on its own (include/uniir_hip.h): what the pooled last block of a tower calls, with dense keys.  The backward
+// (uniir_attention_one_bwd, attention_one.hip) is one kernel at every tk.
 extern "C" int uniir_attention_one_fwd(const void* q, const void* k, const void* v, int64_t kv_ld, void* out, float* lse, int32_t batch,
                                        int32_t tk, int32_t heads, int32_t f16, void* stream) {
-    if (!q || !k || !v || !out || !lse || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_null(q, k, v, out, lse) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
     if (tk < 1 || tk > ATT_LONG_SEQ_MAX) return UNIIR_ESHAPE;
-    if (kv_ld % 8) return UNIIR_EALIGN;
+    if (att_ld_not8(kv_ld)) return UNIIR_EALIGN;          // (the pooled form below would answer UNIIR_ESHAPE)
     return attention_pooled_fwd_impl(q, k, v, kv_ld, out, lse, nullptr, 0, nullptr, batch, tk, heads, f16 != 0, stream);
 }
 
-extern "C" int uniir_attention_fwd(const void* qkv, void* out, float* lse, int32_t batch, int32_t seq,
-                                   int32_t heads, int32_t causal, void* stream) {
-    if (!qkv || !out || !lse || batch < 0 || heads <= 0) return UNIIR_EINVAL;
-    if (batch == 0) return UNIIR_OK;
-    if (seq < 1 || seq > (causal ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX)) return UNIIR_ESHAPE;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
-    const long W = (long)heads * ATT_D;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
-    a.q_ld = a.kv_ld = 3 * W;
-    a.out = (unsigned short*)out; a.out_ld = W; a.lse = lse; a.klen = nullptr;
-    a.Tq = a.Tk = seq; a.H = heads; a.causal = causal; a.scale = ATT_SCALE;
-    if (seq > ATT_SEQ_MAX) return launch_attn_long_fwd(a, batch, (hipStream_t)stream, false);
-    return launch_attn_fwd(a, batch, (hipStream_t)stream);
-}
-
-// the fp16 forward of the embedding towers on its own (fp16 qkv / out): dense rows (row_off == nullptr; plain up to 1024 tokens,
-// causal up to 512) or packed rows (up to 512); the argument checks are attention_fwd_impl's, those of uniir_attention_fwd / _fwd_packed
-extern "C" int uniir_attention_fwd_f16(const void* qkv, void* out, float* lse, const int32_t* row_off, int32_t batch, int32_t seq,
-                                       int32_t heads, int32_t causal, void* stream) {
-    return attention_fwd_impl(qkv, out, lse, row_off, batch, seq, heads, causal, 1, stream);
-}
-
-extern "C" int uniir_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
-                                   void* dqkv, int32_t batch, int32_t seq, int32_t heads, int32_t causal,
-                                   void* stream) {
-    if (!qkv || !out || !dout || !lse || !dqkv || batch < 0 || heads <= 0) return UNIIR_EINVAL;
-    if (batch == 0) return UNIIR_OK;
-    if (seq < 1 || seq > (causal ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX)) return UNIIR_ESHAPE;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)dqkv & 15))
-        return UNIIR_EALIGN;
-    const long W = (long)heads * ATT_D;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
-    a.q_ld = a.kv_ld = 3 * W;
-    a.out = (unsigned short*)out; a.out_ld = W; a.lse = const_cast<float*>(lse); a.klen = nullptr;
-    a.Tq = a.Tk = seq; a.H = heads; a.causal = causal; a.scale = ATT_SCALE;
-    a.dout = (const unsigned short*)dout;
-    a.dq = (unsigned short*)dqkv; a.dk = a.dq + W; a.dv = a.dq + 2 * W;
-    a.dq_ld = a.dkv_ld = 3 * W;
-    if (seq > ATT_SEQ_MAX) return launch_attn_long_bwd(a, batch, (hipStream_t)stream);
-    return launch_attn_bwd(a, batch, (hipStream_t)stream);
-}
-
-// packed rows: item m owns rows row_off[m] .. row_off[m + 1] - 1 of qkv / out (lengths <= max_seq); lse stays [batch][heads][max_seq].
-// The CLIP text tower on the live rows of its captions only (rows behind a caption's EOT never reach its pooled feature under the
-// causal mask, clip_sf.py:43-44): every live row's result is bitwise that of the dense call.
-extern "C" int uniir_attention_fwd_packed(const void* qkv, void* out, float* lse, const int32_t* row_off, int32_t batch,
-                                          int32_t max_seq, int32_t heads, int32_t causal, void* stream) {
-    if (!qkv || !out || !lse || !row_off || batch < 0 || heads <= 0) return UNIIR_EINVAL;
-    if (batch == 0) return UNIIR_OK;
-    if (max_seq < 1 || max_seq > 512) return UNIIR_ESHAPE;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
-    const long W = (long)heads * ATT_D;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
-    a.q_ld = a.kv_ld = 3 * W;
-    a.out = (unsigned short*)out; a.out_ld = W; a.lse = lse; a.klen = nullptr; a.row_off = row_off;
-    a.Tq = a.Tk = max_seq; a.H = heads; a.causal = causal; a.scale = ATT_SCALE;
-    return launch_attn_fwd(a, batch, (hipStream_t)stream);
-}
-extern "C" int uniir_attention_bwd_packed(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
-                                          const int32_t* row_off, int32_t batch, int32_t max_seq, int32_t heads, int32_t causal,
-                                          void* stream) {
-    if (!qkv || !out || !dout || !lse || !dqkv || !row_off || batch < 0 || heads <= 0) return UNIIR_EINVAL;
-    if (batch == 0) return UNIIR_OK;
-    if (max_seq < 1 || max_seq > 512) return UNIIR_ESHAPE;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)dqkv & 15)) return UNIIR_EALIGN;
-    const long W = (long)heads * ATT_D;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
-    a.q_ld = a.kv_ld = 3 * W;
-    a.out = (unsigned short*)out; a.out_ld = W; a.lse = const_cast<float*>(lse); a.klen = nullptr; a.row_off = row_off;
-    a.Tq = a.Tk = max_seq; a.H = heads; a.causal = causal; a.scale = ATT_SCALE;
-    a.dout = (const unsigned short*)dout;
-    a.dq = (unsigned short*)dqkv; a.dk = a.dq + W; a.dv = a.dq + 2 * W;
-    a.dq_ld = a.dkv_ld = 3 * W;
-    return launch_attn_bwd(a, batch, (hipStream_t)stream);
-}
-
+// ---------------- separate Q and K | V, up to ATT_SEQ_MAX x ATT_SEQ_MAX (attention_long.hip has the _long forms) ----------------
 // general form: separate Q and K/V tensors (cross-attention), optional per-item key length (padding mask)
 extern "C" int uniir_attention_fwd_ex(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld,
                                       void* out, int64_t out_ld, float* lse, const int32_t* key_len, int32_t batch,
                                       int32_t tq, int32_t tk, int32_t heads, int32_t causal, float drop_p,
                                       uint32_t drop_seed, void* stream) {
-    if (!q || !k || !v || !out || !lse || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_null(q, k, v, out, lse) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (tq < 1 || tk < 1 || tq > 512 || tk > 512) return UNIIR_ESHAPE;
+    if (tq < 1 || tk < 1 || tq > ATT_SEQ_MAX || tk > ATT_SEQ_MAX) return UNIIR_ESHAPE;
     if (causal && tq != tk) return UNIIR_ESHAPE;
-    if ((q_ld % 8) || (kv_ld % 8) || (out_ld % 8)) return UNIIR_EALIGN;
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-    a.q_ld = q_ld; a.kv_ld = kv_ld; a.out = (unsigned short*)out; a.out_ld = out_ld; a.lse = lse; a.klen = key_len;
-    a.Tq = tq; a.Tk = tk; a.H = heads; a.causal = causal; a.scale = ATT_SCALE;
-    if (drop_p < 0.f || drop_p >= 1.f) return UNIIR_EINVAL;
-    a.drop_p = drop_p; a.drop_seed = drop_seed;
+    if (att_ld_not8(q_ld, kv_ld, out_ld)) return UNIIR_EALIGN;
+    if (att_misaligned16(q, k, v, out)) return UNIIR_EALIGN;
+    if (att_bad_drop(drop_p)) return UNIIR_EINVAL;
+    AttnArgs a = att_args_qkv(q, q_ld, k, v, kv_ld, out, out_ld, lse, tq, tk, heads, key_len, causal);
+    att_args_drop(a, drop_p, drop_seed);
     return launch_attn_fwd(a, batch, (hipStream_t)stream);
 }
-
 extern "C" int uniir_attention_bwd_ex(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld,
                                       const void* out, const void* dout, int64_t out_ld, const float* lse,
                                       const int32_t* key_len, void* dq, int64_t dq_ld, void* dk, void* dv,
                                       int64_t dkv_ld, int32_t batch, int32_t tq, int32_t tk, int32_t heads,
                                       int32_t causal, float drop_p, uint32_t drop_seed, void* stream) {
-    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_null(q, k, v, out, dout, lse, dq, dk, dv) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (tq < 1 || tk < 1 || tq > 512 || tk > 512) return UNIIR_ESHAPE;
+    if (tq < 1 || tk < 1 || tq > ATT_SEQ_MAX || tk > ATT_SEQ_MAX) return UNIIR_ESHAPE;
     if (causal && tq != tk) return UNIIR_ESHAPE;
-    if ((q_ld % 8) || (kv_ld % 8) || (out_ld % 8) || (dq_ld % 8) || (dkv_ld % 8)) return UNIIR_EALIGN;      // 16-byte pieces
-    if (((uintptr_t)dq & 15) || ((uintptr_t)dk & 15) || ((uintptr_t)dv & 15)) return UNIIR_EALIGN;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-    a.q_ld = q_ld; a.kv_ld = kv_ld; a.out = (unsigned short*)out; a.out_ld = out_ld;
-    a.lse = const_cast<float*>(lse); a.klen = key_len;
-    a.Tq = tq; a.Tk = tk; a.H = heads; a.causal = causal; a.scale = ATT_SCALE;
-    a.dout = (const unsigned short*)dout;
-    a.dq = (unsigned short*)dq; a.dk = (unsigned short*)dk; a.dv = (unsigned short*)dv;
-    a.dq_ld = dq_ld; a.dkv_ld = dkv_ld;
-    if (drop_p < 0.f || drop_p >= 1.f) return UNIIR_EINVAL;
-    a.drop_p = drop_p; a.drop_seed = drop_seed;
+    if (att_ld_not8(q_ld, kv_ld, out_ld, dq_ld, dkv_ld)) return UNIIR_EALIGN;
+    if (att_misaligned16(dq, dk, dv)) return UNIIR_EALIGN;          // the gradients only
+    if (att_bad_drop(drop_p)) return UNIIR_EINVAL;
+    AttnArgs a = att_args_qkv(q, q_ld, k, v, kv_ld, out, out_ld, lse, tq, tk, heads, key_len, causal);
+    att_args_qkv_bwd(a, dout, dq, dq_ld, dk, dv, dkv_ld);
+    att_args_drop(a, drop_p, drop_seed);
     return launch_attn_bwd(a, batch, (hipStream_t)stream);
 }
 
@@ -780,19 +691,16 @@ extern "C" int uniir_attention_fwd_rows(const void* q, int64_t q_ld, const void*
                                         int64_t out_ld, float* lse, const int32_t* q_row_off, int32_t kv_packed,
                                         const int32_t* key_len, int32_t batch, int32_t tq, int32_t tk, int32_t heads, float drop_p,
                                         uint32_t drop_seed, void* stream) {
-    if (!q || !k || !v || !out || !lse || !q_row_off || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_null(q, k, v, out, lse, q_row_off) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (tq < 1 || tk < 1 || tq > 512 || tk > 512) return UNIIR_ESHAPE;
+    if (tq < 1 || tk < 1 || tq > ATT_SEQ_MAX || tk > ATT_SEQ_MAX) return UNIIR_ESHAPE;
     if (kv_packed && (tq != tk || key_len)) return UNIIR_EINVAL;
-    if ((q_ld % 8) || (kv_ld % 8) || (out_ld % 8)) return UNIIR_EALIGN;
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
-    if (drop_p < 0.f || drop_p >= 1.f) return UNIIR_EINVAL;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-    a.q_ld = q_ld; a.kv_ld = kv_ld; a.out = (unsigned short*)out; a.out_ld = out_ld; a.lse = lse; a.klen = key_len;
-    a.Tq = tq; a.Tk = tk; a.H = heads; a.causal = 0; a.scale = ATT_SCALE;
-    a.row_off = q_row_off; a.row_off_q_only = kv_packed ? 0 : 1;
-    a.drop_p = drop_p; a.drop_seed = drop_seed;
+    if (att_ld_not8(q_ld, kv_ld, out_ld)) return UNIIR_EALIGN;
+    if (att_misaligned16(q, k, v, out)) return UNIIR_EALIGN;
+    if (att_bad_drop(drop_p)) return UNIIR_EINVAL;
+    AttnArgs a = att_args_qkv(q, q_ld, k, v, kv_ld, out, out_ld, lse, tq, tk, heads, key_len);
+    att_args_q_rows(a, q_row_off, kv_packed ? 0 : 1);
+    att_args_drop(a, drop_p, drop_seed);
     return launch_attn_fwd(a, batch, (hipStream_t)stream);
 }
 extern "C" int uniir_attention_bwd_rows(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, const void* out,
@@ -800,71 +708,61 @@ extern "C" int uniir_attention_bwd_rows(const void* q, int64_t q_ld, const void*
                                         int32_t kv_packed, const int32_t* key_len, void* dq, int64_t dq_ld, void* dk, void* dv,
                                         int64_t dkv_ld, int32_t batch, int32_t tq, int32_t tk, int32_t heads, float drop_p,
                                         uint32_t drop_seed, void* stream) {
-    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !q_row_off || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_null(q, k, v, out, dout, lse, dq, dk, dv, q_row_off) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (tq < 1 || tk < 1 || tq > 512 || tk > 512) return UNIIR_ESHAPE;
+    if (tq < 1 || tk < 1 || tq > ATT_SEQ_MAX || tk > ATT_SEQ_MAX) return UNIIR_ESHAPE;
     if (kv_packed && (tq != tk || key_len)) return UNIIR_EINVAL;
-    if ((q_ld % 8) || (kv_ld % 8) || (out_ld % 8) || (dq_ld % 8) || (dkv_ld % 8)) return UNIIR_EALIGN;
-    if (((uintptr_t)dq & 15) || ((uintptr_t)dk & 15) || ((uintptr_t)dv & 15)) return UNIIR_EALIGN;
-    if (drop_p < 0.f || drop_p >= 1.f) return UNIIR_EINVAL;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-    a.q_ld = q_ld; a.kv_ld = kv_ld; a.out = (unsigned short*)out; a.out_ld = out_ld;
-    a.lse = const_cast<float*>(lse); a.klen = key_len;
-    a.Tq = tq; a.Tk = tk; a.H = heads; a.causal = 0; a.scale = ATT_SCALE;
-    a.row_off = q_row_off; a.row_off_q_only = kv_packed ? 0 : 1;
-    a.dout = (const unsigned short*)dout;
-    a.dq = (unsigned short*)dq; a.dk = (unsigned short*)dk; a.dv = (unsigned short*)dv;
-    a.dq_ld = dq_ld; a.dkv_ld = dkv_ld;
-    a.drop_p = drop_p; a.drop_seed = drop_seed;
+    if (att_ld_not8(q_ld, kv_ld, out_ld, dq_ld, dkv_ld)) return UNIIR_EALIGN;
+    if (att_misaligned16(dq, dk, dv)) return UNIIR_EALIGN;          // the gradients only
+    if (att_bad_drop(drop_p)) return UNIIR_EINVAL;
+    AttnArgs a = att_args_qkv(q, q_ld, k, v, kv_ld, out, out_ld, lse, tq, tk, heads, key_len);
+    att_args_q_rows(a, q_row_off, kv_packed ? 0 : 1);
+    att_args_qkv_bwd(a, dout, dq, dq_ld, dk, dv, dkv_ld);
+    att_args_drop(a, drop_p, drop_seed);
     return launch_attn_bwd(a, batch, (hipStream_t)stream);
 }
 
-// T5-style self-attention for the CLIP_FF fusion stack: logits = scale * q.k + rel_emb[rel_bucket[key - query + seq - 1]][head]
+// ---------------- T5-style self-attention ----------------
+// For the CLIP_FF fusion stack: logits = scale * q.k + rel_emb[rel_bucket[key - query + seq - 1]][head]
 // (transformers T5Attention: scale 1, bucketed relative position bias shared by all layers), packed qkv like
 // uniir_attention_fwd.  bwd adds d loss / d rel_emb into drel (fp32 [buckets][heads], zero it once per step), in a fixed order when
 // the stream has a scratch buffer: fixed-point sums inside a workgroup, the workgroups' partials added in item order.
+// These two test no alignment; their _long forms (attention_long.hip) do.
 extern "C" int uniir_attention_rel_fwd(const void* qkv, void* out, float* lse, const float* rel_emb,
                                        const int32_t* rel_bucket, int32_t nbuckets, float scale, int32_t batch,
                                        int32_t seq, int32_t heads, float drop_p, uint32_t drop_seed, void* stream) {
-    if (!qkv || !out || !lse || !rel_emb || !rel_bucket || batch < 0 || heads <= 0 || nbuckets <= 0 || nbuckets > 64)
-        return UNIIR_EINVAL;
+    if (att_null(qkv, out, lse, rel_emb, rel_bucket) || batch < 0 || heads <= 0 || nbuckets <= 0 || nbuckets > 64) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (seq < 1 || seq > 512) return UNIIR_ESHAPE;
-    const long W = (long)heads * ATT_D;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
-    a.q_ld = a.kv_ld = 3 * W; a.out = (unsigned short*)out; a.out_ld = W; a.lse = lse;
-    a.Tq = a.Tk = seq; a.H = heads; a.causal = 0; a.scale = scale;
-    a.rel_emb = rel_emb; a.rel_bucket = rel_bucket; a.nbuckets = nbuckets;
-    if (drop_p < 0.f || drop_p >= 1.f) return UNIIR_EINVAL;
-    a.drop_p = drop_p; a.drop_seed = drop_seed;
+    if (seq < 1 || seq > ATT_SEQ_MAX) return UNIIR_ESHAPE;
+    if (att_bad_drop(drop_p)) return UNIIR_EINVAL;
+    AttnArgs a = att_args_packed(qkv, out, lse, seq, heads, 0, scale);
+    att_args_rel(a, rel_emb, rel_bucket, nbuckets);
+    att_args_drop(a, drop_p, drop_seed);
     return launch_attn_fwd(a, batch, (hipStream_t)stream);
 }
-
+// The backward's tail, shared with uniir_attention_rel_bwd_long: the workgroups store their bucket sums in the stream's scratch
+// as [part][bucket][head] (nparts of them: one per item here, one per (item, key block) in the streaming form), `launch` runs the
+// kernels, and the partials are added into drel in part order.  drel is accumulated, not overwritten: the layers of a T5 stack share
+// one bias table.  Without scratch (or without drel) the kernels fall back to float atomics / skip the gradient.
+int attention_rel_bwd_tail(AttnArgs& a, float* drel, long nparts, int batch, hipStream_t st, int (*launch)(const AttnArgs&, int, hipStream_t)) {
+    a.drel = drel;
+    if (drel) a.drel_part = reduce_scratch(st, nparts * a.H * a.nbuckets * 4);
+    const int rc = launch(a, batch, st);
+    if (rc || !a.drel_part) return rc;
+    return reduce_partials(a.drel_part, (int)nparts, (long)a.nbuckets * a.H, a.nbuckets * a.H, drel, nullptr, nullptr, 0, st);
+}
 extern "C" int uniir_attention_rel_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                        const float* rel_emb, const int32_t* rel_bucket, int32_t nbuckets, float scale,
                                        float* drel, int32_t batch, int32_t seq, int32_t heads, float drop_p,
                                        uint32_t drop_seed, void* stream) {
-    if (!qkv || !out || !dout || !lse || !dqkv || !rel_emb || !rel_bucket || batch < 0 || heads <= 0 || nbuckets <= 0 ||
-        nbuckets > 64)
+    if (att_null(qkv, out, dout, lse, dqkv, rel_emb, rel_bucket) || batch < 0 || heads <= 0 || nbuckets <= 0 || nbuckets > 64)
         return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (seq < 1 || seq > 512) return UNIIR_ESHAPE;
-    const long W = (long)heads * ATT_D;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
-    a.q_ld = a.kv_ld = 3 * W; a.out = (unsigned short*)const_cast<void*>(out); a.out_ld = W;
-    a.lse = const_cast<float*>(lse); a.dout = (const unsigned short*)dout;
-    a.dq = (unsigned short*)dqkv; a.dk = a.dq + W; a.dv = a.dq + 2 * W; a.dq_ld = a.dkv_ld = 3 * W;
-    a.Tq = a.Tk = seq; a.H = heads; a.causal = 0; a.scale = scale;
-    a.rel_emb = rel_emb; a.rel_bucket = rel_bucket; a.nbuckets = nbuckets; a.drel = drel;
-    if (drop_p < 0.f || drop_p >= 1.f) return UNIIR_EINVAL;
-    a.drop_p = drop_p; a.drop_seed = drop_seed;
-    // one workgroup per (item, head) stores its bucket sums in the stream's scratch as [item][bucket][head]; they are added into drel
-    // in item order below.  drel is accumulated, not overwritten: the layers of a T5 stack share one bias table.
-    if (drel) a.drel_part = reduce_scratch((hipStream_t)stream, (int64_t)batch * heads * nbuckets * 4);
-    const int rc = launch_attn_bwd(a, batch, (hipStream_t)stream);
-    if (rc || !a.drel_part) return rc;
-    return reduce_partials(a.drel_part, batch, (long)nbuckets * heads, nbuckets * heads, drel, nullptr, nullptr, 0, (hipStream_t)stream);
+    if (seq < 1 || seq > ATT_SEQ_MAX) return UNIIR_ESHAPE;
+    if (att_bad_drop(drop_p)) return UNIIR_EINVAL;
+    AttnArgs a = att_args_packed(qkv, out, lse, seq, heads, 0, scale);
+    att_args_packed_bwd(a, dout, dqkv);
+    att_args_rel(a, rel_emb, rel_bucket, nbuckets);
+    att_args_drop(a, drop_p, drop_seed);
+    return attention_rel_bwd_tail(a, drel, batch, batch, (hipStream_t)stream, launch_attn_bwd);
 }

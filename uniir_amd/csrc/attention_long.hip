@@ -599,223 +599,155 @@ __global__ __launch_bounds__(AL_THREADS, 4) void attn_rlong_dq_kernel(AttnArgs a
     al_dq_body<false, DROP, true>(a, nqb);
 }
 
-// what the long kernels take: dense rows, no mask, no bias, no dropout, the default scale
-static bool attn_long_plain(const AttnArgs& a) {
-    return !a.causal && !a.klen && !a.row_off && !a.kv_row_off && !a.rel_emb && a.drop_p == 0.f && a.scale == ATT_SCALE;
-}
+// ---------------- launchers: one forward, one backward for the three families ----------------
+// (instantiated here so that the kernels stand in the code object family by family, as they always have)
+template __global__ void attn_long_fwd_kernel<false>(AttnArgs, int);
+template __global__ void attn_long_fwd_kernel<true>(AttnArgs, int);
+template __global__ void attn_xlong_fwd_kernel<false>(AttnArgs, int);
+template __global__ void attn_xlong_fwd_kernel<true>(AttnArgs, int);
+template __global__ void attn_xlong_dkdv_kernel<false>(AttnArgs, int);
+template __global__ void attn_xlong_dkdv_kernel<true>(AttnArgs, int);
+template __global__ void attn_xlong_dq_kernel<false>(AttnArgs, int);
+template __global__ void attn_xlong_dq_kernel<true>(AttnArgs, int);
+enum AlFamily { AL_PLAIN, AL_XL, AL_REL };
 static const int AL_FWD_LDS = 2 * 2 * AL_KV * 128;
 static const int AL_DKDV_LDS = 2 * (2 * AL_QC * 128 + 2 * AL_QC * 4);
 static const int AL_DQ_LDS = 2 * 2 * AL_KV * 128 + 2 * AL_ROWS * 4;
+// LDS behind these buffers in the REL family: the bias table of the forward and dQ, the fixed-point sums and the bias slice of dK / dV
+static int al_rel_tab_bytes(int seq) { return (2 * seq + 32) * 4; }
+static int al_rel_dkdv_bytes(int seq) { return 64 * 8 + (seq + 164) * 12; }
 
-int launch_attn_long_fwd(const AttnArgs& a, int batch, hipStream_t st, bool f16) {
-    if (!attn_long_plain(a) || a.Tq < 1 || a.Tk < 1 || a.Tq > 1024 || a.Tk > 1024) return UNIIR_ESHAPE;
+// f16: AL_PLAIN only (the fp16 forward of the towers)
+static int al_launch_fwd(AlFamily fam, const AttnArgs& a, int batch, hipStream_t st, bool f16 = false) {
     const int nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
     const long grid = (long)batch * a.H * nqb;
     if (grid > 0x7fffffffL) return UNIIR_ESHAPE;
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-        (void)hipFuncSetAttribute((const void*)attn_long_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_FWD_LDS);
-        (void)hipFuncSetAttribute((const void*)attn_long_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_FWD_LDS);
+    const dim3 g((unsigned)grid), b(AL_THREADS);
+    const bool drop = a.drop_p > 0.f;
+    if (fam == AL_PLAIN) {
+        if (!f16) return att_launch<attn_long_fwd_kernel<false>>(AL_FWD_LDS, g, b, AL_FWD_LDS, st, a, nqb);
+        return att_launch<attn_long_fwd_kernel<true>>(AL_FWD_LDS, g, b, AL_FWD_LDS, st, a, nqb);
     }
-    if (f16) hipLaunchKernelGGL(attn_long_fwd_kernel<true>, dim3((unsigned)grid), dim3(AL_THREADS), AL_FWD_LDS, st, a, nqb);
-    else hipLaunchKernelGGL(attn_long_fwd_kernel<false>, dim3((unsigned)grid), dim3(AL_THREADS), AL_FWD_LDS, st, a, nqb);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
+    if (fam == AL_XL) {
+        if (!drop) return att_launch<attn_xlong_fwd_kernel<false>>(AL_FWD_LDS, g, b, AL_FWD_LDS, st, a, nqb);
+        return att_launch<attn_xlong_fwd_kernel<true>>(AL_FWD_LDS, g, b, AL_FWD_LDS, st, a, nqb);
+    }
+    const int sm = AL_FWD_LDS + al_rel_tab_bytes(a.Tq), mx = AL_FWD_LDS + al_rel_tab_bytes(ATT_LONG_SEQ_MAX);
+    if (!drop) return att_launch<attn_rlong_fwd_kernel<false>>(mx, g, b, sm, st, a, nqb);
+    return att_launch<attn_rlong_fwd_kernel<true>>(mx, g, b, sm, st, a, nqb);
 }
 
-int launch_attn_long_bwd(const AttnArgs& a, int batch, hipStream_t st) {
-    if (!attn_long_plain(a) || a.Tq < 1 || a.Tk < 1 || a.Tq > 1024 || a.Tk > 1024) return UNIIR_ESHAPE;
+// dK / dV, then dQ
+static int al_launch_bwd(AlFamily fam, const AttnArgs& a, int batch, hipStream_t st) {
     const int nkblk = (a.Tk + AL_ROWS - 1) / AL_ROWS, nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
-    const long gk = (long)batch * a.H * nkblk, gq = (long)batch * a.H * nqb;
-    if (gk > 0x7fffffffL || gq > 0x7fffffffL) return UNIIR_ESHAPE;
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-        (void)hipFuncSetAttribute((const void*)attn_long_dkdv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DKDV_LDS);
-        (void)hipFuncSetAttribute((const void*)attn_long_dq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DQ_LDS);
+    const long nk = (long)batch * a.H * nkblk, nq = (long)batch * a.H * nqb;
+    if (nk > 0x7fffffffL || nq > 0x7fffffffL) return UNIIR_ESHAPE;
+    const dim3 gk((unsigned)nk), gq((unsigned)nq), b(AL_THREADS);
+    const bool drop = a.drop_p > 0.f;
+    int rc;
+    if (fam == AL_PLAIN) {
+        rc = att_launch<attn_long_dkdv_kernel>(AL_DKDV_LDS, gk, b, AL_DKDV_LDS, st, a, nkblk);
+        if (rc) return rc;
+        return att_launch<attn_long_dq_kernel>(AL_DQ_LDS, gq, b, AL_DQ_LDS, st, a, nqb);
     }
-    hipLaunchKernelGGL(attn_long_dkdv_kernel, dim3((unsigned)gk), dim3(AL_THREADS), AL_DKDV_LDS, st, a, nkblk);
-    HIP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attn_long_dq_kernel, dim3((unsigned)gq), dim3(AL_THREADS), AL_DQ_LDS, st, a, nqb);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
+    if (fam == AL_XL) {
+        if (!drop) rc = att_launch<attn_xlong_dkdv_kernel<false>>(AL_DKDV_LDS, gk, b, AL_DKDV_LDS, st, a, nkblk);
+        else rc = att_launch<attn_xlong_dkdv_kernel<true>>(AL_DKDV_LDS, gk, b, AL_DKDV_LDS, st, a, nkblk);
+        if (rc) return rc;
+        if (!drop) return att_launch<attn_xlong_dq_kernel<false>>(AL_DQ_LDS, gq, b, AL_DQ_LDS, st, a, nqb);
+        return att_launch<attn_xlong_dq_kernel<true>>(AL_DQ_LDS, gq, b, AL_DQ_LDS, st, a, nqb);
+    }
+    const int sk = AL_DKDV_LDS + al_rel_dkdv_bytes(a.Tq), mk = AL_DKDV_LDS + al_rel_dkdv_bytes(ATT_LONG_SEQ_MAX);
+    const int sq = AL_DQ_LDS + al_rel_tab_bytes(a.Tq), mq = AL_DQ_LDS + al_rel_tab_bytes(ATT_LONG_SEQ_MAX);
+    if (!drop) rc = att_launch<attn_rlong_dkdv_kernel<false>>(mk, gk, b, sk, st, a, nkblk);
+    else rc = att_launch<attn_rlong_dkdv_kernel<true>>(mk, gk, b, sk, st, a, nkblk);
+    if (rc) return rc;
+    if (!drop) return att_launch<attn_rlong_dq_kernel<false>>(mq, gq, b, sq, st, a, nqb);
+    return att_launch<attn_rlong_dq_kernel<true>>(mq, gq, b, sq, st, a, nqb);
+}
+
+// what the plain kernels take: dense rows, no mask, no bias, no dropout, the default scale
+static bool attn_long_plain(const AttnArgs& a) {
+    return !a.causal && !a.klen && !a.row_off && !a.kv_row_off && !a.rel_emb && a.drop_p == 0.f && a.scale == ATT_SCALE && a.Tq >= 1 &&
+           a.Tk >= 1 && a.Tq <= ATT_LONG_SEQ_MAX && a.Tk <= ATT_LONG_SEQ_MAX;
+}
+int launch_attn_long_fwd(const AttnArgs& a, int batch, hipStream_t st, bool f16) {
+    return attn_long_plain(a) ? al_launch_fwd(AL_PLAIN, a, batch, st, f16) : UNIIR_ESHAPE;
+}
+int launch_attn_long_bwd(const AttnArgs& a, int batch, hipStream_t st) {
+    return attn_long_plain(a) ? al_launch_bwd(AL_PLAIN, a, batch, st) : UNIIR_ESHAPE;
 }
 
 // ---------------- the general form (uniir_attention_fwd_long / _bwd_long) ----------------
-static int launch_attn_xlong_fwd(const AttnArgs& a, int batch, hipStream_t st) {
-    const int nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
-    const long grid = (long)batch * a.H * nqb;
-    if (grid > 0x7fffffffL) return UNIIR_ESHAPE;
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-        (void)hipFuncSetAttribute((const void*)attn_xlong_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_FWD_LDS);
-        (void)hipFuncSetAttribute((const void*)attn_xlong_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_FWD_LDS);
-    }
-    if (a.drop_p > 0.f) hipLaunchKernelGGL(attn_xlong_fwd_kernel<true>, dim3((unsigned)grid), dim3(AL_THREADS), AL_FWD_LDS, st, a, nqb);
-    else hipLaunchKernelGGL(attn_xlong_fwd_kernel<false>, dim3((unsigned)grid), dim3(AL_THREADS), AL_FWD_LDS, st, a, nqb);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
-}
-
-static int launch_attn_xlong_bwd(const AttnArgs& a, int batch, hipStream_t st) {
-    const int nkblk = (a.Tk + AL_ROWS - 1) / AL_ROWS, nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
-    const long gk = (long)batch * a.H * nkblk, gq = (long)batch * a.H * nqb;
-    if (gk > 0x7fffffffL || gq > 0x7fffffffL) return UNIIR_ESHAPE;
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-        (void)hipFuncSetAttribute((const void*)attn_xlong_dkdv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DKDV_LDS);
-        (void)hipFuncSetAttribute((const void*)attn_xlong_dkdv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DKDV_LDS);
-        (void)hipFuncSetAttribute((const void*)attn_xlong_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DQ_LDS);
-        (void)hipFuncSetAttribute((const void*)attn_xlong_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, AL_DQ_LDS);
-    }
-    const bool drop = a.drop_p > 0.f;
-    if (drop) hipLaunchKernelGGL(attn_xlong_dkdv_kernel<true>, dim3((unsigned)gk), dim3(AL_THREADS), AL_DKDV_LDS, st, a, nkblk);
-    else hipLaunchKernelGGL(attn_xlong_dkdv_kernel<false>, dim3((unsigned)gk), dim3(AL_THREADS), AL_DKDV_LDS, st, a, nkblk);
-    HIP_LAUNCH_CHECK();
-    if (drop) hipLaunchKernelGGL(attn_xlong_dq_kernel<true>, dim3((unsigned)gq), dim3(AL_THREADS), AL_DQ_LDS, st, a, nqb);
-    else hipLaunchKernelGGL(attn_xlong_dq_kernel<false>, dim3((unsigned)gq), dim3(AL_THREADS), AL_DQ_LDS, st, a, nqb);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
-}
-
-// The general form up to 1024 x 1024: q_row_off == NULL is uniir_attention_fwd_ex / _bwd_ex with causal = 0, otherwise
+// Up to ATT_LONG_SEQ_MAX x ATT_LONG_SEQ_MAX: q_row_off == NULL is uniir_attention_fwd_ex / _bwd_ex with causal = 0, otherwise
 // uniir_attention_fwd_rows / _bwd_rows with kv_packed = 0 (packed query rows, K / V dense [batch][tk]).  Every size runs the
-// streaming kernels above; nothing is forwarded to the 512-token kernels.
+// streaming kernels above; nothing is forwarded to the resident kernels.  Unlike those entry points, these test drop_p BEFORE
+// batch == 0, refuse a NaN drop_p, and the backward tests the alignment of all eight pointers.
 extern "C" int uniir_attention_fwd_long(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, void* out,
                                         int64_t out_ld, float* lse, const int32_t* q_row_off, const int32_t* key_len, int32_t batch,
                                         int32_t tq, int32_t tk, int32_t heads, float drop_p, uint32_t drop_seed, void* stream) {
-    if (!q || !k || !v || !out || !lse || batch < 0 || heads <= 0) return UNIIR_EINVAL;
-    if (!(drop_p >= 0.f && drop_p < 1.f)) return UNIIR_EINVAL;
+    if (att_null(q, k, v, out, lse) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_bad_drop_nan(drop_p)) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (tq < 1 || tk < 1 || tq > 1024 || tk > 1024) return UNIIR_ESHAPE;
-    if ((q_ld % 8) || (kv_ld % 8) || (out_ld % 8)) return UNIIR_EALIGN;
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-    a.q_ld = q_ld; a.kv_ld = kv_ld; a.out = (unsigned short*)out; a.out_ld = out_ld; a.lse = lse; a.klen = key_len;
-    a.Tq = tq; a.Tk = tk; a.H = heads; a.causal = 0; a.scale = ATT_SCALE;
-    a.row_off = q_row_off; a.row_off_q_only = 1;
-    a.drop_p = drop_p; a.drop_seed = drop_seed;
-    return launch_attn_xlong_fwd(a, batch, (hipStream_t)stream);
+    if (tq < 1 || tk < 1 || tq > ATT_LONG_SEQ_MAX || tk > ATT_LONG_SEQ_MAX) return UNIIR_ESHAPE;
+    if (att_ld_not8(q_ld, kv_ld, out_ld)) return UNIIR_EALIGN;
+    if (att_misaligned16(q, k, v, out)) return UNIIR_EALIGN;
+    AttnArgs a = att_args_qkv(q, q_ld, k, v, kv_ld, out, out_ld, lse, tq, tk, heads, key_len);
+    att_args_q_rows(a, q_row_off, 1);
+    att_args_drop(a, drop_p, drop_seed);
+    return al_launch_fwd(AL_XL, a, batch, (hipStream_t)stream);
 }
 extern "C" int uniir_attention_bwd_long(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, const void* out,
                                         const void* dout, int64_t out_ld, const float* lse, const int32_t* q_row_off,
                                         const int32_t* key_len, void* dq, int64_t dq_ld, void* dk, void* dv, int64_t dkv_ld,
                                         int32_t batch, int32_t tq, int32_t tk, int32_t heads, float drop_p, uint32_t drop_seed,
                                         void* stream) {
-    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || batch < 0 || heads <= 0) return UNIIR_EINVAL;
-    if (!(drop_p >= 0.f && drop_p < 1.f)) return UNIIR_EINVAL;
+    if (att_null(q, k, v, out, dout, lse, dq, dk, dv) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_bad_drop_nan(drop_p)) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (tq < 1 || tk < 1 || tq > 1024 || tk > 1024) return UNIIR_ESHAPE;
-    if ((q_ld % 8) || (kv_ld % 8) || (out_ld % 8) || (dq_ld % 8) || (dkv_ld % 8)) return UNIIR_EALIGN;      // 16-byte pieces
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dout & 15) ||
-        ((uintptr_t)dq & 15) || ((uintptr_t)dk & 15) || ((uintptr_t)dv & 15))
-        return UNIIR_EALIGN;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-    a.q_ld = q_ld; a.kv_ld = kv_ld; a.out = (unsigned short*)const_cast<void*>(out); a.out_ld = out_ld;
-    a.lse = const_cast<float*>(lse); a.klen = key_len;
-    a.Tq = tq; a.Tk = tk; a.H = heads; a.causal = 0; a.scale = ATT_SCALE;
-    a.row_off = q_row_off; a.row_off_q_only = 1;
-    a.dout = (const unsigned short*)dout;
-    a.dq = (unsigned short*)dq; a.dk = (unsigned short*)dk; a.dv = (unsigned short*)dv;
-    a.dq_ld = dq_ld; a.dkv_ld = dkv_ld;
-    a.drop_p = drop_p; a.drop_seed = drop_seed;
-    return launch_attn_xlong_bwd(a, batch, (hipStream_t)stream);
+    if (tq < 1 || tk < 1 || tq > ATT_LONG_SEQ_MAX || tk > ATT_LONG_SEQ_MAX) return UNIIR_ESHAPE;
+    if (att_ld_not8(q_ld, kv_ld, out_ld, dq_ld, dkv_ld)) return UNIIR_EALIGN;
+    if (att_misaligned16(q, k, v, out, dout, dq, dk, dv)) return UNIIR_EALIGN;
+    AttnArgs a = att_args_qkv(q, q_ld, k, v, kv_ld, out, out_ld, lse, tq, tk, heads, key_len);
+    att_args_q_rows(a, q_row_off, 1);
+    att_args_qkv_bwd(a, dout, dq, dq_ld, dk, dv, dkv_ld);
+    att_args_drop(a, drop_p, drop_seed);
+    return al_launch_bwd(AL_XL, a, batch, (hipStream_t)stream);
 }
 
 // ---------------- T5-style self-attention (uniir_attention_rel_fwd_long / _rel_bwd_long) ----------------
-// LDS behind the buffers of the plain kernels: the bias table of the forward and dQ, the fixed-point sums and the bias slice of dK / dV
-static int al_rel_tab_bytes(int seq) { return (2 * seq + 32) * 4; }
-static int al_rel_dkdv_bytes(int seq) { return 64 * 8 + (seq + 164) * 12; }
-
-static int launch_attn_rlong_fwd(const AttnArgs& a, int batch, hipStream_t st) {
-    const int nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
-    const long grid = (long)batch * a.H * nqb;
-    if (grid > 0x7fffffffL) return UNIIR_ESHAPE;
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-        const int mx = AL_FWD_LDS + al_rel_tab_bytes(1024);
-        (void)hipFuncSetAttribute((const void*)attn_rlong_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        (void)hipFuncSetAttribute((const void*)attn_rlong_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-    }
-    const int sm = AL_FWD_LDS + al_rel_tab_bytes(a.Tq);
-    if (a.drop_p > 0.f) hipLaunchKernelGGL(attn_rlong_fwd_kernel<true>, dim3((unsigned)grid), dim3(AL_THREADS), sm, st, a, nqb);
-    else hipLaunchKernelGGL(attn_rlong_fwd_kernel<false>, dim3((unsigned)grid), dim3(AL_THREADS), sm, st, a, nqb);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
-}
-
-static int launch_attn_rlong_bwd(const AttnArgs& a, int batch, int nkblk, hipStream_t st) {
-    const int nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
-    const long gk = (long)batch * a.H * nkblk, gq = (long)batch * a.H * nqb;
-    if (gk > 0x7fffffffL || gq > 0x7fffffffL) return UNIIR_ESHAPE;
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-        const int mk = AL_DKDV_LDS + al_rel_dkdv_bytes(1024), mq = AL_DQ_LDS + al_rel_tab_bytes(1024);
-        (void)hipFuncSetAttribute((const void*)attn_rlong_dkdv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, mk);
-        (void)hipFuncSetAttribute((const void*)attn_rlong_dkdv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mk);
-        (void)hipFuncSetAttribute((const void*)attn_rlong_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, mq);
-        (void)hipFuncSetAttribute((const void*)attn_rlong_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mq);
-    }
-    const int sk = AL_DKDV_LDS + al_rel_dkdv_bytes(a.Tq), sq = AL_DQ_LDS + al_rel_tab_bytes(a.Tq);
-    const bool drop = a.drop_p > 0.f;
-    if (drop) hipLaunchKernelGGL(attn_rlong_dkdv_kernel<true>, dim3((unsigned)gk), dim3(AL_THREADS), sk, st, a, nkblk);
-    else hipLaunchKernelGGL(attn_rlong_dkdv_kernel<false>, dim3((unsigned)gk), dim3(AL_THREADS), sk, st, a, nkblk);
-    HIP_LAUNCH_CHECK();
-    if (drop) hipLaunchKernelGGL(attn_rlong_dq_kernel<true>, dim3((unsigned)gq), dim3(AL_THREADS), sq, st, a, nqb);
-    else hipLaunchKernelGGL(attn_rlong_dq_kernel<false>, dim3((unsigned)gq), dim3(AL_THREADS), sq, st, a, nqb);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
-}
-
-// uniir_attention_rel_fwd / _rel_bwd for 1 <= seq <= 1024: every size runs the streaming kernels above, nothing is forwarded to the
-// 512-token kernels.
+// uniir_attention_rel_fwd / _rel_bwd for 1 <= seq <= ATT_LONG_SEQ_MAX: every size runs the streaming kernels above, nothing is
+// forwarded to the resident kernels.  drop_p before batch == 0 and NaN as above; and these test alignment, which rel_fwd / rel_bwd do not.
 extern "C" int uniir_attention_rel_fwd_long(const void* qkv, void* out, float* lse, const float* rel_emb, const int32_t* rel_bucket,
                                             int32_t nbuckets, float scale, int32_t batch, int32_t seq, int32_t heads, float drop_p,
                                             uint32_t drop_seed, void* stream) {
-    if (!qkv || !out || !lse || !rel_emb || !rel_bucket || batch < 0 || heads <= 0 || nbuckets <= 0 || nbuckets > 64)
-        return UNIIR_EINVAL;
-    if (!(drop_p >= 0.f && drop_p < 1.f)) return UNIIR_EINVAL;
+    if (att_null(qkv, out, lse, rel_emb, rel_bucket) || batch < 0 || heads <= 0 || nbuckets <= 0 || nbuckets > 64) return UNIIR_EINVAL;
+    if (att_bad_drop_nan(drop_p)) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (seq < 1 || seq > 1024) return UNIIR_ESHAPE;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return UNIIR_EALIGN;
-    const long W = (long)heads * ATT_D;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
-    a.q_ld = a.kv_ld = 3 * W; a.out = (unsigned short*)out; a.out_ld = W; a.lse = lse;
-    a.Tq = a.Tk = seq; a.H = heads; a.causal = 0; a.scale = scale;
-    a.rel_emb = rel_emb; a.rel_bucket = rel_bucket; a.nbuckets = nbuckets;
-    a.drop_p = drop_p; a.drop_seed = drop_seed;
-    return launch_attn_rlong_fwd(a, batch, (hipStream_t)stream);
+    if (seq < 1 || seq > ATT_LONG_SEQ_MAX) return UNIIR_ESHAPE;
+    if (att_misaligned16(qkv, out)) return UNIIR_EALIGN;
+    AttnArgs a = att_args_packed(qkv, out, lse, seq, heads, 0, scale);
+    att_args_rel(a, rel_emb, rel_bucket, nbuckets);
+    att_args_drop(a, drop_p, drop_seed);
+    return al_launch_fwd(AL_REL, a, batch, (hipStream_t)stream);
 }
-
+static int al_launch_rel_bwd(const AttnArgs& a, int batch, hipStream_t st) { return al_launch_bwd(AL_REL, a, batch, st); }
 extern "C" int uniir_attention_rel_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                             const float* rel_emb, const int32_t* rel_bucket, int32_t nbuckets, float scale,
                                             float* drel, int32_t batch, int32_t seq, int32_t heads, float drop_p, uint32_t drop_seed,
                                             void* stream) {
-    if (!qkv || !out || !dout || !lse || !dqkv || !rel_emb || !rel_bucket || batch < 0 || heads <= 0 || nbuckets <= 0 ||
-        nbuckets > 64)
+    if (att_null(qkv, out, dout, lse, dqkv, rel_emb, rel_bucket) || batch < 0 || heads <= 0 || nbuckets <= 0 || nbuckets > 64)
         return UNIIR_EINVAL;
-    if (!(drop_p >= 0.f && drop_p < 1.f)) return UNIIR_EINVAL;
+    if (att_bad_drop_nan(drop_p)) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (seq < 1 || seq > 1024) return UNIIR_ESHAPE;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)dqkv & 15)) return UNIIR_EALIGN;
-    const long W = (long)heads * ATT_D;
+    if (seq < 1 || seq > ATT_LONG_SEQ_MAX) return UNIIR_ESHAPE;
+    if (att_misaligned16(qkv, out, dout, dqkv)) return UNIIR_EALIGN;
     const int nkblk = (seq + AL_ROWS - 1) / AL_ROWS;
     if ((long)batch * heads * nkblk > 0x7fffffffL) return UNIIR_ESHAPE;          // before the scratch is asked for: a refused call counts nothing
-    AttnArgs a = {};
-    a.q = (const unsigned short*)qkv; a.k = a.q + W; a.v = a.q + 2 * W;
-    a.q_ld = a.kv_ld = 3 * W; a.out = (unsigned short*)const_cast<void*>(out); a.out_ld = W;
-    a.lse = const_cast<float*>(lse); a.dout = (const unsigned short*)dout;
-    a.dq = (unsigned short*)dqkv; a.dk = a.dq + W; a.dv = a.dq + 2 * W; a.dq_ld = a.dkv_ld = 3 * W;
-    a.Tq = a.Tk = seq; a.H = heads; a.causal = 0; a.scale = scale;
-    a.rel_emb = rel_emb; a.rel_bucket = rel_bucket; a.nbuckets = nbuckets; a.drel = drel;
-    a.drop_p = drop_p; a.drop_seed = drop_seed;
-    // one workgroup per (item, key block, head) stores its bucket sums in the stream's scratch as [item][key block][bucket][head]; they
-    // are added into drel in that order below.  drel is accumulated, not overwritten: the layers of a T5 stack share one bias table.
-    const long nparts = (long)batch * nkblk;
-    if (drel) a.drel_part = reduce_scratch((hipStream_t)stream, nparts * heads * nbuckets * 4);
-    const int rc = launch_attn_rlong_bwd(a, batch, nkblk, (hipStream_t)stream);
-    if (rc || !a.drel_part) return rc;
-    return reduce_partials(a.drel_part, (int)nparts, (long)nbuckets * heads, nbuckets * heads, drel, nullptr, nullptr, 0, (hipStream_t)stream);
+    AttnArgs a = att_args_packed(qkv, out, lse, seq, heads, 0, scale);
+    att_args_packed_bwd(a, dout, dqkv);
+    att_args_rel(a, rel_emb, rel_bucket, nbuckets);
+    att_args_drop(a, drop_p, drop_seed);
+    // one partial per (item, key block): [item][key block][bucket][head]
+    return attention_rel_bwd_tail(a, drel, (long)batch * nkblk, batch, (hipStream_t)stream, al_launch_rel_bwd);
 }

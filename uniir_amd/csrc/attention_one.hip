@@ -1,4 +1,4 @@
-// One-query attention backward (head_dim 64, bf16, scale 1/8): ONE query row per (item, head) against 1 .. 1024 dense keys, no mask,
+// One-query attention backward (head_dim 64, bf16, scale 1/8): ONE query row per (item, head) against 1 .. ATT_LONG_SEQ_MAX (1024) dense keys, no mask,
 // no dropout, no bias.  The pooled last block of a tower (tower.hip: the class token is all that leaves a vision tower) and
 // uniir_attention_one_bwd.
 //
@@ -116,34 +116,26 @@ __global__ __launch_bounds__(AO_WAVES * 64) void attn_one_bwd_kernel(AttnArgs a,
 // a: Tq = 1, dense q / out / dout rows [batch][H * 64] (q_ld, out_ld), lse [batch][H], K / V rows [batch * Tk] (kv_ld), dq rows [batch]
 // (dq_ld), dk / dv rows [batch * Tk] (dkv_ld); no key counts, no packed rows, no bias, no dropout, the default scale
 int launch_attn_one_bwd(const AttnArgs& a, int batch, hipStream_t st) {
-    if (a.Tq != 1 || a.Tk < 1 || a.Tk > 1024 || a.causal || a.klen || a.row_off || a.kv_row_off || a.rel_emb || a.drop_p != 0.f ||
-        a.scale != ATT_SCALE)
+    if (a.Tq != 1 || a.Tk < 1 || a.Tk > ATT_LONG_SEQ_MAX || a.causal || a.klen || a.row_off || a.kv_row_off || a.rel_emb ||
+        a.drop_p != 0.f || a.scale != ATT_SCALE)
         return UNIIR_ESHAPE;
-    if ((a.q_ld % 8) || (a.out_ld % 8) || (a.kv_ld % 8) || (a.dq_ld % 8) || (a.dkv_ld % 8)) return UNIIR_EALIGN;      // 16-byte pieces
-    if (((uintptr_t)a.q & 15) || ((uintptr_t)a.k & 15) || ((uintptr_t)a.v & 15) || ((uintptr_t)a.out & 15) || ((uintptr_t)a.dout & 15) ||
-        ((uintptr_t)a.dq & 15) || ((uintptr_t)a.dk & 15) || ((uintptr_t)a.dv & 15))
-        return UNIIR_EALIGN;
+    if (att_ld_not8(a.q_ld, a.out_ld, a.kv_ld, a.dq_ld, a.dkv_ld)) return UNIIR_EALIGN;      // 16-byte pieces
+    if (att_misaligned16(a.q, a.k, a.v, a.out, a.dout, a.dq, a.dk, a.dv)) return UNIIR_EALIGN;
     const int nhb = (a.H + AO_WAVES - 1) / AO_WAVES;
     const long grid = (long)batch * nhb;
     if (grid > 0x7fffffffL) return UNIIR_ESHAPE;
-    hipLaunchKernelGGL(attn_one_bwd_kernel, dim3((unsigned)grid), dim3(AO_WAVES * 64), 0, st, a, nhb);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
+    return att_launch<attn_one_bwd_kernel>(0, dim3((unsigned)grid), dim3(AO_WAVES * 64), 0, st, a, nhb);      // no LDS
 }
 
+// the alignment checks are the launcher's: UNIIR_EALIGN for a leading dimension as well
 extern "C" int uniir_attention_one_bwd(const void* q, const void* k, const void* v, int64_t kv_ld, const void* out, const void* dout,
                                        const float* lse, void* dq, int64_t dq_ld, void* dk, void* dv, int64_t dkv_ld, int32_t batch,
                                        int32_t tk, int32_t heads, void* stream) {
-    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_null(q, k, v, out, dout, lse, dq, dk, dv) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
-    if (tk < 1 || tk > 1024) return UNIIR_ESHAPE;
+    if (tk < 1 || tk > ATT_LONG_SEQ_MAX) return UNIIR_ESHAPE;
     const long W = (long)heads * ATT_D;
-    AttnArgs a = {};
-    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-    a.q_ld = W; a.kv_ld = kv_ld; a.out = (unsigned short*)const_cast<void*>(out); a.out_ld = W; a.lse = const_cast<float*>(lse);
-    a.Tq = 1; a.Tk = tk; a.H = heads; a.causal = 0; a.scale = ATT_SCALE;
-    a.dout = (const unsigned short*)dout;
-    a.dq = (unsigned short*)dq; a.dk = (unsigned short*)dk; a.dv = (unsigned short*)dv;
-    a.dq_ld = dq_ld; a.dkv_ld = dkv_ld;
+    AttnArgs a = att_args_qkv(q, W, k, v, kv_ld, out, W, lse, 1, tk, heads);
+    att_args_qkv_bwd(a, dout, dq, dq_ld, dk, dv, dkv_ld);
     return launch_attn_one_bwd(a, batch, (hipStream_t)stream);
 }

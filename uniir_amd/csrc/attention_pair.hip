@@ -691,6 +691,7 @@ __global__ __launch_bounds__(AP_THREADS, 2) void attn_bwd_pair_kernel(AttnArgs a
 }
 
 // LDS bytes of the backward for TP padded rows and nvl valid rows in the odd tile
+static const int AP_LDS_MAX = 160 * 1024;          // all of a workgroup's LDS
 static int ap_bwd_lds(int TP, int nvl) { return 4 * TP * 128 + 4 * TP * 4 + AP_WAVES * 3 * nvl * 64 * 4; }
 
 // can the pair kernels take this call?  plain self-attention (the caller checks mask / dropout / bias), 129 .. 288 tokens in one of
@@ -708,7 +709,7 @@ static bool ap_geom(int T, ApGeom* gm, int* TP) {
     if (gm->npair > AP_WAVES) return false;
     if (32 * gm->npair > T) return false;                 // every pair is full (no key mask in the pair loops) ...
     if (T % 32 == 0) return false;                        // ... and exactly the last 32-row block holds padding
-    if (ap_bwd_lds(tp, gm->nvl) > 160 * 1024) return false;
+    if (ap_bwd_lds(tp, gm->nvl) > AP_LDS_MAX) return false;
     *TP = tp;
     return true;
 }
@@ -731,14 +732,7 @@ int launch_attn_bwd_pair(const AttnArgs& a, int batch, hipStream_t st) {      //
     if (g_att_exp & 64) return 1;          // experiments: force the general kernel
 #endif
     const int sm = ap_bwd_lds(TP, gm.nvl);
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd_pair_kernel<288>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_pair_kernel<224>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-    const int grid = gm.total_heads < ncu ? gm.total_heads : ncu;
-    if (TP == 288) hipLaunchKernelGGL(attn_bwd_pair_kernel<288>, dim3(grid), dim3(AP_THREADS), sm, st, a, gm);
-    else hipLaunchKernelGGL(attn_bwd_pair_kernel<224>, dim3(grid), dim3(AP_THREADS), sm, st, a, gm);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
+    const dim3 g(gm.total_heads < ncu ? gm.total_heads : ncu), b(AP_THREADS);
+    if (TP == 288) return att_launch<attn_bwd_pair_kernel<288>>(AP_LDS_MAX, g, b, sm, st, a, gm);
+    return att_launch<attn_bwd_pair_kernel<224>>(AP_LDS_MAX, g, b, sm, st, a, gm);
 }

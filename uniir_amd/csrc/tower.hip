@@ -5,8 +5,7 @@
 // op-level entry points of this library on the caller's stream, never allocates, never synchronises.  Weights and
 // gradients are raw device pointers in a POD description; activations live in ONE caller-provided workspace whose layout
 // (plan()) is a pure function of the description and the batch size, so forward and backward agree on it.
-#include "common.h"
-#include "../../include/uniir_hip.h"
+#include "attention.h"          // attention_fwd_impl, attention_pooled_{fwd,bwd}_impl, ATT_SEQ_MAX / ATT_LONG_SEQ_MAX
 #include <string.h>
 
 // the forward's ops with the 16-bit storage type as a parameter (defined next to their extern "C" bf16 entry points)
@@ -15,15 +14,7 @@ int vit_assemble_impl(const void* patch_out, const float* class_emb, const float
                       int32_t width, int f16, void* stream);
 int layernorm_fwd_impl(const float* x, int64_t x_stride, const float* gamma, const float* beta, void* y_16, float* y_f32,
                        int32_t rows, int32_t width, float eps, int f16, void* stream);
-int attention_fwd_impl(const void* qkv, void* out, float* lse, const int32_t* row_off, int32_t batch, int32_t seq, int32_t heads,
-                       int32_t causal, int f16, void* stream);
-// one query row per item (attention.hip) and raw row gather / scatter-overwrite (elementwise.hip): the pooled last block below
-int attention_pooled_fwd_impl(const void* q, const void* k, const void* v, int64_t kv_ld, void* out, float* lse, const int32_t* klen,
-                              int32_t klen_add, const int32_t* kv_row_off, int32_t batch, int32_t tk, int32_t heads, int f16,
-                              void* stream);
-int attention_pooled_bwd_impl(const void* q, const void* k, const void* v, int64_t kv_ld, const void* out, const void* dout,
-                              const float* lse, const int32_t* klen, int32_t klen_add, const int32_t* kv_row_off, void* dq,
-                              int64_t dq_ld, void* dk, void* dv, int64_t dkv_ld, int32_t batch, int32_t tk, int32_t heads, void* stream);
+// raw row gather / scatter-overwrite (elementwise.hip): the pooled last block below
 int rows_copy_impl(const void* src, const int32_t* idx, void* dst, int32_t n, int32_t seq, int32_t row_bytes, int64_t big_pitch,
                    int64_t small_pitch, int32_t scatter, void* stream);
 
@@ -103,7 +94,7 @@ Plan plan(const uniir_clip_tower* t, int batch, bool save, int rows = -1, const 
     p.x_last = take(R * W * 4);          // with !save the stream ping-pongs between o_x of the single layer set and this
     // value 1: the resident one-query attention holds all keys in LDS, so above 512 tokens the full last block runs (same embeddings);
     // value 2: pooled at every token count (513 .. 1024: the streaming forward at one query, the one-pass backward of attention_one.hip)
-    p.pool_last = t->pool_last_block != 0 && (t->tokens <= 512 || t->pool_last_block == 2);
+    p.pool_last = t->pool_last_block != 0 && (t->tokens <= ATT_SEQ_MAX || t->pool_last_block == 2);
     if (p.pool_last) {
         p.pl_q = take(M * W * 2); p.pl_h1 = take(M * W * 2); p.pl_x = take(M * W * 4); p.pl_ao = take(M * W * 2);
         p.pl_lse = take(M * (int64_t)p.H * 4); p.pl_x2 = take(M * W * 4); p.pl_h2 = take(M * W * 2);
@@ -143,7 +134,8 @@ int check_tower(const uniir_clip_tower* t, int batch) {
     if (t->layers <= 0 || t->width <= 0 || t->heads <= 0 || t->tokens < 2 || t->embed_dim <= 0) return UNIIR_EINVAL;
     if (t->recompute != 0 && t->recompute != 1) return UNIIR_EINVAL;
     // (a vision tower's plain attention streams up to 1024 tokens, attention_long.hip; the causal / packed text forms hold a head in LDS)
-    if (t->width != t->heads * 64 || t->width % 64 || t->embed_dim % 8 || t->tokens > (t->is_text ? 512 : 1024)) return UNIIR_ESHAPE;
+    if (t->width != t->heads * 64 || t->width % 64 || t->embed_dim % 8) return UNIIR_ESHAPE;
+    if (t->tokens > (t->is_text ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX)) return UNIIR_ESHAPE;
     if (!t->pos_emb || !t->ln_post_w || !t->ln_post_b || !t->proj16) return UNIIR_EINVAL;
     if (t->is_text) {
         if (!t->token_emb || t->vocab <= 0) return UNIIR_EINVAL;

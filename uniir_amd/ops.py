@@ -311,9 +311,15 @@ def attention_one_bwd(q, k, v, kv_ld, out, dout, lse, dq, dq_ld, dk, dv, dkv_ld,
                                               dkv_ld, batch, tk, heads, _stream()), "attention_one_bwd")
 
 
+# The most tokens whose keys the resident kernels hold in LDS: csrc/attention.h ATT_SEQ_MAX.  Above it the streaming entry points
+# (`_long`, csrc/attention_long.hip) run, up to ATT_LONG_SEQ_MAX = 1024; the library refuses what neither takes.
+ATT_RESIDENT_MAX = 512
+
+
 def _attention_long(tq, tk, causal, kv_packed):
-    """the general form goes to uniir_attention_fwd_long / _bwd_long: more than 512 queries or keys, no causal mask, dense K / V"""
-    return max(tq, tk) > 512 and not causal and not kv_packed
+    """the general form goes to uniir_attention_fwd_long / _bwd_long: more than ATT_RESIDENT_MAX queries or keys, no causal mask,
+    dense K / V"""
+    return max(tq, tk) > ATT_RESIDENT_MAX and not causal and not kv_packed
 
 
 def attention_fwd_ex(q, q_ld, k, v, kv_ld, batch, tq, tk, heads, *, key_len=None, causal=False, drop_p=0.0, drop_seed=0,
