@@ -108,6 +108,9 @@ typedef struct {
 } uniir_gemm_desc;
 
 int uniir_gemm(const uniir_gemm_desc* d, void* stream);
+/* k_splits for a weight gradient dW += dy^T x over `rows` rows whose output has `tiles` 256 x 256 tiles: the smallest count that
+ * fills the 256 compute units to 90 % while every split keeps >= 16 K steps of 64 rows (host arithmetic, no device involved) */
+int32_t uniir_gemm_wgrad_splits(int32_t rows, int32_t tiles);
 /* measurement hook (bench.py): stride > 0 brackets every stride-th uniir_gemm call -- from any caller, the tower entry
  * points included -- with HIP events on its launch stream; 0 switches it off.  uniir_gemm_timing_read (after a stream
  * synchronise) returns the sums over the sampled launches: 2 M N K, elapsed ms, count.  Single measuring thread.

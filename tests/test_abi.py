@@ -191,9 +191,10 @@ def test_tower_workspace_query_sees_the_pooled_last_block_flag():
         assert lib.uniir_clip_tower_workspace_bytes(ctypes.byref(t), M, 1) > pooled
 
 
-# uniir_gemm's descriptor validation (csrc/gemm.hip gemm_impl) runs before the library touches the HIP runtime: every malformed
+# uniir_gemm's descriptor validation (csrc/gemm.hip gemm_check) runs before the library touches the HIP runtime: every malformed
 # descriptor below is rejected here, on a machine without a GPU, with its own code.  The addresses are never dereferenced.
 _OK_GEMM = dict(A=0x10000, B=0x20000, C=0x30000, M=256, N=128, K=128, lda=128, ldb=128, ldc=128, epilogue=0, k_splits=1, alpha=1.0)
+_HT = dict(epilogue=5, a_tmaj=1, b_tmaj=1, lda=256, K=1100)          # the head + tail shape
 _GEMM_REJECTS = [
     # (what, changes, expected code name)
     ("null A", dict(A=None), "EINVAL"),
@@ -237,7 +238,79 @@ _GEMM_REJECTS = [
     ("bias with ATOMIC_F32, 256-tile shape", dict(epilogue=5, bias=0x80000, K=192), "EUNSUPPORTED"),
     ("bias with ATOMIC_F32, split-K", dict(epilogue=5, bias=0x80000, K=1024, k_splits=4), "EUNSUPPORTED"),
     ("bias with ATOMIC_F32, head + tail", dict(epilogue=5, bias=0x80000, a_tmaj=1, b_tmaj=1, lda=256, K=1100), "EUNSUPPORTED"),
+    ("epilogue < 0", dict(epilogue=-1), "EINVAL"),
+    # the late refusals (128-tile problems: K % 64, M < 256 or N < 128): after every check above, before anything is launched
+    ("colsum with F32, K % 64", dict(epilogue=4, colsum=0x60000, K=72), "EUNSUPPORTED"),
+    ("colsum with RESID_F32, M < 256", dict(epilogue=2, colsum=0x60000, M=128), "EUNSUPPORTED"),
+    ("colsum with F32, N < 128", dict(epilogue=4, colsum=0x60000, N=64, ldc=64), "EUNSUPPORTED"),
+    ("colsum with DACT, 128-tile, ldc % 8", dict(epilogue=3, aux=0x70000, ldaux=128, colsum=0x60000, K=72, ldc=132), "EUNSUPPORTED"),
+    ("DACT with C2, 128-tile, ldaux != N", dict(epilogue=3, aux=0x70000, ldaux=136, C2=0x40000, K=72), "EUNSUPPORTED"),
+    ("bad dtype, split-K", dict(dtype=2, epilogue=5, K=1024, k_splits=4), "EINVAL"),
+    # two neighbouring checks failing together: the earlier one answers (the pairs no descriptor can fail together -- BIAS_ACT
+    # without C2 and DACT without aux, DACT without aux and colsum, colsum and the fp16 epilogues -- have no row)
+    ("null A and M = 0", dict(A=None, M=0), "EINVAL"),
+    ("K = 0 and bad epilogue", dict(K=0, epilogue=7), "EINVAL"),
+    ("bad epilogue and split-K", dict(epilogue=7, k_splits=2), "EINVAL"),
+    ("split-K ACT_ONLY with C2", dict(k_splits=2, epilogue=6, C2=0x40000), "EINVAL"),
+    ("ACT_ONLY with C2 and row_scale", dict(epilogue=6, C2=0x40000, row_scale=0x50000), "EINVAL"),
+    ("BIAS_ACT with row_scale, without C2", dict(epilogue=1, row_scale=0x50000), "EINVAL"),
+    ("fp16 DACT and N % 8", dict(dtype=1, epilogue=3, aux=0x70000, ldaux=132, N=132, ldc=132), "EUNSUPPORTED"),
+    ("N % 8 and K % 8, K-major A", dict(N=132, ldc=132, K=100, b_tmaj=1, ldb=128), "ESHAPE"),
+    ("K % 8, K-major A and B", dict(K=100), "ESHAPE"),
+    ("K % 8, K-major B and M % 8, T-major A", dict(K=100, M=252, a_tmaj=1, lda=256), "ESHAPE"),
+    ("M % 8, T-major A and lda % 8", dict(M=252, a_tmaj=1, lda=260), "ESHAPE"),
+    ("lda % 8 and A not 16-B aligned", dict(lda=132, A=0x10008), "EALIGN"),
+    ("C and aux not aligned", dict(C=0x30004, epilogue=3, aux=0x70004, ldaux=128), "EALIGN"),
+    ("ldaux % 4 and bias not 16-B aligned", dict(epilogue=3, aux=0x70000, ldaux=130, bias=0x80008), "EALIGN"),
+    ("bias not 16-B aligned with ATOMIC_F32", dict(epilogue=5, bias=0x80008), "EALIGN"),
+    ("bias with ATOMIC_F32 and a_rowsum without a_tmaj", dict(epilogue=5, bias=0x80000, a_rowsum=0x90000), "EUNSUPPORTED"),
+    ("a_rowsum without a_tmaj and colsum with F32, 128-tile", dict(epilogue=4, a_rowsum=0x90000, colsum=0x60000, K=72), "EUNSUPPORTED"),
+    ("colsum with F32, 128-tile, and ldc % 8", dict(epilogue=4, colsum=0x60000, K=72, ldc=132), "EUNSUPPORTED"),
+    ("colsum with DACT, 128-tile, ldc % 8 and C2 with ldaux != N",
+     dict(epilogue=3, aux=0x70000, ldaux=136, C2=0x40000, colsum=0x60000, K=72, ldc=132), "EUNSUPPORTED"),
+    ("DACT with C2, 128-tile, ldaux != N and bad dtype", dict(dtype=2, epilogue=3, aux=0x70000, ldaux=136, C2=0x40000, K=72), "EUNSUPPORTED"),
+    # a late refusal against an early one of another code, and the dtype check (the last of all) against the others
+    ("colsum with F32, 128-tile, and ldc % 4", dict(epilogue=4, colsum=0x60000, K=72, ldc=130), "EALIGN"),
+    ("a_rowsum with a bad dtype", dict(epilogue=5, a_tmaj=1, b_tmaj=1, lda=256, dtype=2, a_rowsum=0x90000), "EUNSUPPORTED"),
+    ("bad dtype and N % 8", dict(dtype=2, N=132, ldc=132), "ESHAPE"),
+    ("bad dtype and colsum with F32, 128-tile", dict(dtype=2, epilogue=4, colsum=0x60000, K=72), "EUNSUPPORTED"),
+    # the head + tail shape (ATOMIC_F32, both operands T-major, K % 64, K >= 1024): every refusal comes before the head is launched
+    ("head + tail, k_splits = 0", dict(_HT, k_splits=0), "EINVAL"),
+    ("head + tail, colsum", dict(_HT, colsum=0x60000), "EUNSUPPORTED"),
+    ("head + tail, M % 8", dict(_HT, M=260, lda=264), "ESHAPE"),
+    ("head + tail, lda % 8", dict(_HT, lda=260), "EALIGN"),
+    ("head + tail, C not 16-B aligned", dict(_HT, C=0x30004), "EALIGN"),
+    ("head + tail, a_rowsum with fp16", dict(_HT, dtype=1, a_rowsum=0x90000), "EUNSUPPORTED"),
+    ("head + tail, a_rowsum with a bad dtype", dict(_HT, dtype=2, a_rowsum=0x90000), "EUNSUPPORTED"),
+    ("head + tail, bad dtype", dict(_HT, dtype=2), "EINVAL"),
+    ("head + tail, bad dtype, split-K", dict(_HT, dtype=2, k_splits=4), "EINVAL"),
 ]
+
+
+def _wgrad_splits_oracle(rows, tiles, n_cu=256):
+    """the split-K rule as ops.wgrad_splits stated it before the library exported it: tiles * splits just under a multiple of the 256
+    compute units, every split keeping >= 16 K steps of 64 rows"""
+    max_s = max(1, rows // (64 * 16))
+    best, best_eff = 1, 0.0
+    for s in range(1, min(max_s, 64) + 1):
+        blocks = tiles * s
+        rounds = -(-blocks // n_cu)
+        eff = blocks / (rounds * n_cu)
+        if blocks >= 0.9 * n_cu and eff >= 0.9:
+            return s
+        if eff > best_eff + 1e-9:
+            best, best_eff = s, eff
+    return best
+
+
+def test_wgrad_splits_of_the_library_equal_the_rule_everywhere():
+    """uniir_gemm_wgrad_splits is the one body of the heuristic (ops.wgrad_splits and the C towers call it): equal to the oracle above
+    for every row count around its thresholds and 1 .. 600 output tiles"""
+    from uniir_amd import _lib, ops
+    lib = _lib.load()
+    wrong = [(rows, tiles) for rows in (1, 63, 1023, 1024, 1025, 4096, 33280, 35000, 263168, 590848) for tiles in range(1, 601)
+             if not lib.uniir_gemm_wgrad_splits(rows, tiles) == ops.wgrad_splits(rows, tiles) == _wgrad_splits_oracle(rows, tiles)]
+    assert not wrong, wrong[:10]
 
 
 def test_gemm_rejects_malformed_descriptors_before_touching_the_device():

@@ -78,6 +78,7 @@ SIGNATURES = {
     "uniir_reduce_scratch": (c_int, [c_void_p, c_i64, c_void_p]),
     "uniir_reduce_stats": (c_int, [C.POINTER(c_i64), C.POINTER(c_i64), c_int]),
     "uniir_gemm": (c_int, [C.POINTER(GemmDesc), S]),
+    "uniir_gemm_wgrad_splits": (c_int, [c_int, c_int]),
     "uniir_gemm_timing": (c_int, [c_int]),
     "uniir_gemm_timing_on": (c_int, [c_int, c_void_p]),
     "uniir_gemm_timing_read": (c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(c_int)]),

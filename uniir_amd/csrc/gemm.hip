@@ -40,7 +40,7 @@ struct GemmKArgs {
     int skip_f;                 // EPI_BIAS_ACT without the pre-activation store (UNIIR_EPI_ACT_ONLY: forward-only passes)
     const float* row_scale;     // EPI_RESID_F32: (v + bias) * row_scale[m] + resid (DropPath factor of the row's item), or nullptr
     float* a_rowsum;            // optional [M]: += sum_k A^T[m][k] (transposed-A ping-pong kernel only, see gemm_core_pp.h)
-    float* colsum_part;         // deterministic form of colsum: row panel mt STORES its column partial at [mt][N] (gemm_impl reduces)
+    float* colsum_part;         // deterministic form of colsum: row panel mt STORES its column partial at [mt][N] (gemm_run reduces)
     float* rowsum_part;         // ... of a_rowsum: block (split, nt) stores its row partial at [split * tiles_n + nt][M]
 };
 
@@ -796,132 +796,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_glds_kernel(GemmKArgs p)
     gemm_epilogue_dispatch<8, 4, Elem::F16>(p, acc, m0, n0, wm, wn);
 }
 
-template <typename Elem, int WM, int WN, int BK, int ASM>
-static int launch_glds(GemmKArgs a, int a_tmaj, int b_tmaj, hipStream_t st) {
-    using S = GldsShape<WM, WN, BK>;
-    a.tiles_m = (a.M + S::BM - 1) / S::BM;
-    a.tiles_n = (a.N + S::BN - 1) / S::BN;
-    a.raster_gm = 8;          // 2-D tile rasterisation: 8 row panels x 4 column panels per XCD working set (round-3 sweep, tools/r3)
-    a.raster_cw = 4;
-    const int grid = a.tiles_m * a.tiles_n * a.k_splits;
-    dim3 g(grid), b(S::T);
-    const size_t sm = S::LDS_BYTES;
-#define LAUNCHG(AT, BT)                                                                           \
-    do {                                                                                          \
-        static PerDeviceOnce attr_set;                                                            \
-        if (attr_set.first()) {                                                                   \
-            (void)hipFuncSetAttribute((const void*)gemm_glds_kernel<Elem, AT, BT, WM, WN, BK, ASM>,    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);       \
-        }                                                                                         \
-        hipLaunchKernelGGL((gemm_glds_kernel<Elem, AT, BT, WM, WN, BK, ASM>), g, b, sm, st, a);        \
-    } while (0)
-#ifdef UNIIR_EXP_BUILD   // fast experimental build (tools/build_exp.sh): NT ping-pong kernel only
-    if (!a_tmaj && !b_tmaj && ASM == 2) LAUNCHG(false, false);
-    else return UNIIR_EUNSUPPORTED;
-#else
-    if (!a_tmaj && !b_tmaj) LAUNCHG(false, false);
-    else if (!a_tmaj && b_tmaj) LAUNCHG(false, true);
-    else if (a_tmaj && !b_tmaj) LAUNCHG(true, false);
-    else LAUNCHG(true, true);
-#endif
-#undef LAUNCHG
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
-}
-
-// shape choice: 0 = general 128x128 register-staged kernel, 1 = 256x256x64 LDS-DMA kernel (1 workgroup / CU)
-static int gemm_shape(const GemmKArgs& a, int a_tmaj, int b_tmaj) {
-    if (a.K % 64) return 0;
-    if (a.M < 256 || a.N < 128) return 0;    // small problems: the 128-tile kernel fills the chip better
-    return 1;
-}
-
-// does this problem run the ping-pong loop?
-static bool pp_eligible(const GemmKArgs& a, int a_tmaj, int b_tmaj) {
-    if (gemm_shape(a, a_tmaj, b_tmaj) != 1 || a.asm_loop != 2) return false;
-    // the ping-pong loop needs >= 3 K steps in every split
-    const int ksteps = a.K / 64, per = (ksteps + a.k_splits - 1) / a.k_splits;
-    const int last = ksteps - per * (a.k_splits - 1);
-    // ... and addresses the K advance of a T-major operand as a 32-bit byte offset
-    const bool k32 = (!a_tmaj || (uint64_t)a.K * a.lda * 2 < (1ull << 32)) &&
-                     (!b_tmaj || (uint64_t)a.K * a.ldb * 2 < (1ull << 32));
-    return last >= 3 && k32;
-}
-// the transposed-A / transposed-B ping-pong kernel with the row sums of A^T (bf16 only: v_dot2c_f32_bf16)
-static int launch_glds_rowsum(GemmKArgs a, hipStream_t st) {
-    using S = GldsShape<2, 4, 64>;
-    a.tiles_m = (a.M + S::BM - 1) / S::BM;
-    a.tiles_n = (a.N + S::BN - 1) / S::BN;
-    a.raster_gm = 0;
-    a.raster_cw = 4;
-    static PerDeviceOnce attr_set;
-    if (attr_set.first())
-        (void)hipFuncSetAttribute((const void*)gemm_glds_kernel<ElemBF16, true, true, 2, 4, 64, 3>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS_BYTES);
-    hipLaunchKernelGGL((gemm_glds_kernel<ElemBF16, true, true, 2, 4, 64, 3>), dim3(a.tiles_m * a.tiles_n * a.k_splits), dim3(S::T),
-                       S::LDS_BYTES, st, a);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
-}
-
-// dx = (dy @ w) * act'(f) [act(f) out] [column sums] on the ping-pong kernel with the 8-column copy-out (bf16, dy K-contiguous, w
-// K-major: the towers' c_proj dgrad)
-static int launch_glds_dact(GemmKArgs a, hipStream_t st) {
-    using S = GldsShape<2, 4, 64>;
-    a.tiles_m = (a.M + S::BM - 1) / S::BM;
-    a.tiles_n = (a.N + S::BN - 1) / S::BN;
-    a.raster_gm = 8;
-    a.raster_cw = 4;
-    static PerDeviceOnce attr_set;
-    if (attr_set.first())
-        (void)hipFuncSetAttribute((const void*)gemm_glds_kernel<ElemBF16, false, true, 2, 4, 64, 4>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS_BYTES);
-    hipLaunchKernelGGL((gemm_glds_kernel<ElemBF16, false, true, 2, 4, 64, 4>), dim3(a.tiles_m * a.tiles_n), dim3(S::T), S::LDS_BYTES, st, a);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
-}
-
-template <typename Elem>
-static int launch_gemm(const GemmKArgs& a, int a_tmaj, int b_tmaj, hipStream_t st) {
-    const int shape = gemm_shape(a, a_tmaj, b_tmaj);
-    if (shape == 1) {
-        if (pp_eligible(a, a_tmaj, b_tmaj)) {
-#ifndef UNIIR_EXP_BUILD
-            if (a.a_rowsum && std::is_same<Elem, ElemBF16>::value) return launch_glds_rowsum(a, st);
-            if (a.epilogue == UNIIR_EPI_DACT && std::is_same<Elem, ElemBF16>::value && !a_tmaj && b_tmaj && a.k_splits == 1 &&
-                !a.slab && !a.bias && a.N % 8 == 0 && a.ldc % 8 == 0 && a.ldaux % 8 == 0 && !((uintptr_t)a.aux & 15) &&
-                (!a.C2 || !((uintptr_t)a.C2 & 15)))
-                return launch_glds_dact(a, st);
-#endif
-            return launch_glds<Elem, 2, 4, 64, 2>(a, a_tmaj, b_tmaj, st);
-        }
-        return launch_glds<Elem, 2, 4, 64, 1>(a, a_tmaj, b_tmaj, st);
-    }
-    const int grid = a.tiles_m * a.tiles_n * a.k_splits;
-    dim3 g(grid), b(256);
-    const size_t sm = GEMM_LDS_BYTES;
-#define LAUNCH(AT, BT)                                                                            \
-    do {                                                                                          \
-        static PerDeviceOnce attr_set;                                                            \
-        if (attr_set.first()) {                                                                   \
-            (void)hipFuncSetAttribute((const void*)gemm_kernel<Elem, AT, BT>,                           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);             \
-        }                                                                                         \
-        hipLaunchKernelGGL((gemm_kernel<Elem, AT, BT>), g, b, sm, st, a);                         \
-    } while (0)
-#ifdef UNIIR_EXP_BUILD
-    return UNIIR_EUNSUPPORTED;
-#else
-    if (!a_tmaj && !b_tmaj) LAUNCH(false, false);
-    else if (!a_tmaj && b_tmaj) LAUNCH(false, true);
-    else if (a_tmaj && !b_tmaj) LAUNCH(true, false);
-    else LAUNCH(true, true);
-#endif
-#undef LAUNCH
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
-}
-
 // C[m][n] (+)= sum_s slab[s][m][n]
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slab, int splits, long mn, int N,
                                                             float* __restrict__ C, long ldc) {
@@ -933,6 +807,306 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         f32x4_t* dst = reinterpret_cast<f32x4_t*>(C + m * ldc + n);
         *dst = *dst + s;
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the host side
+// uniir_gemm = gemm_check (every refusal) -> head + tail split (P6) -> gemm_plan (every dispatch decision, each made once) ->
+// gemm_run (the launches, which only read the plan).  DESIGN.md section 3 has the table of the paths.
+#ifdef UNIIR_EXP_BUILD   // fast experimental build (tools/build_exp.sh): bf16 NT ping-pong kernel only
+constexpr bool GEMM_EXP_BUILD = true;
+#else
+constexpr bool GEMM_EXP_BUILD = false;
+#endif
+using Glds = GldsShape<2, 4, 64>;       // the 256 x 256 x 64 LDS-DMA kernel: 8 waves, one workgroup per CU
+static_assert(Glds::BM == 256 && Glds::BN == 256, "gemm_plan sizes the partials by 256-row and 256-column panels");
+
+// shape choice: 0 = general 128x128 register-staged kernel, 1 = 256x256x64 LDS-DMA kernel
+static int gemm_shape(int M, int N, int K) {
+    if (K % 64) return 0;
+    if (M < 256 || N < 128) return 0;    // small problems: the 128-tile kernel fills the chip better
+    return 1;
+}
+
+// does a 256-tile problem of `splits` splits run the ping-pong loop?
+static bool pp_eligible(const uniir_gemm_desc* d, int splits) {
+    // the ping-pong loop needs >= 3 K steps in every split
+    const int ksteps = d->K / 64, per = (ksteps + splits - 1) / splits;
+    const int last = ksteps - per * (splits - 1);
+    // ... and addresses the K advance of a T-major operand as a 32-bit byte offset
+    const bool k32 = (!d->a_tmaj || (uint64_t)d->K * d->lda * 2 < (1ull << 32)) &&
+                     (!d->b_tmaj || (uint64_t)d->K * d->ldb * 2 < (1ull << 32));
+    return last >= 3 && k32;
+}
+
+// Every refusal, before anything is launched.  shape = gemm_shape() of the descriptor: colsum and the DACT epilogue's second
+// output act(aux) exist in the LDS-staged epilogue of the 256-tile kernel only, and what replaces them on a 128-tile problem
+// (gemm_plan) does not take every descriptor.
+static int gemm_check(const uniir_gemm_desc* d, int shape) {
+    if (!d->A || !d->B || !d->C) return UNIIR_EINVAL;
+    if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->k_splits < 1) return UNIIR_EINVAL;
+    if (d->epilogue < 0 || d->epilogue > UNIIR_EPI_ACT_ONLY) return UNIIR_EINVAL;
+    if (d->k_splits > 1 && d->epilogue != UNIIR_EPI_ATOMIC_F32) return UNIIR_EINVAL;
+    if (d->epilogue == UNIIR_EPI_ACT_ONLY && d->C2) return UNIIR_EINVAL;
+    if (d->row_scale && d->epilogue != UNIIR_EPI_RESID_F32) return UNIIR_EINVAL;
+    if (d->epilogue == UNIIR_EPI_BIAS_ACT && !d->C2) return UNIIR_EINVAL;
+    if (d->epilogue == UNIIR_EPI_DACT && !d->aux) return UNIIR_EINVAL;
+    // column sums of the result ride the fp32 copy-out passes only (DACT / RESID_F32 / F32 epilogues)
+    if (d->colsum && d->epilogue != UNIIR_EPI_DACT && d->epilogue != UNIIR_EPI_RESID_F32 && d->epilogue != UNIIR_EPI_F32)
+        return UNIIR_EUNSUPPORTED;
+    // fp16 operands (the forward-only embedding towers): the 16-bit outputs of EPI_BF16 / BIAS_ACT / ACT_ONLY are fp16 as well; the
+    // backward-side epilogues (activation gradient, the bf16 copy of a residual output) exist for bf16 only
+    if (d->dtype == UNIIR_DT_F16 && (d->epilogue == UNIIR_EPI_DACT || (d->epilogue == UNIIR_EPI_RESID_F32 && d->C2))) return UNIIR_EUNSUPPORTED;
+    if (d->N % 8) return UNIIR_ESHAPE;
+    if (!d->a_tmaj && (d->K % 8)) return UNIIR_ESHAPE;
+    if (!d->b_tmaj && (d->K % 8)) return UNIIR_ESHAPE;
+    if (d->a_tmaj && (d->M % 8)) return UNIIR_ESHAPE;
+    if ((d->lda % 8) || (d->ldb % 8) || (d->ldc % 4)) return UNIIR_EALIGN;
+    if (((uintptr_t)d->A & 15) || ((uintptr_t)d->B & 15) || ((uintptr_t)d->C & 15)) return UNIIR_EALIGN;
+    if (d->aux && ((d->ldaux % 4) || ((uintptr_t)d->aux & 7))) return UNIIR_EALIGN;
+    if (d->bias && ((uintptr_t)d->bias & 15)) return UNIIR_EALIGN;
+    // a bias has no single meaning for an accumulating product that may run as several splits, slabs or a head and a tail
+    if (d->bias && d->epilogue == UNIIR_EPI_ATOMIC_F32) return UNIIR_EUNSUPPORTED;
+    // row sums of A^T: the transposed ping-pong kernel and the separate pass over A both read bf16
+    if (d->a_rowsum && (!d->a_tmaj || d->dtype != UNIIR_DT_BF16)) return UNIIR_EUNSUPPORTED;
+    if (shape == 0) {
+        if (d->colsum && d->epilogue != UNIIR_EPI_DACT) return UNIIR_EUNSUPPORTED;     // fp32 outputs: no separate column-sum pass exists
+        if (d->colsum && (d->ldc % 8)) return UNIIR_EUNSUPPORTED;                      // the pass reads 16-B row pieces
+        if (d->epilogue == UNIIR_EPI_DACT && d->C2 && d->ldaux != d->N) return UNIIR_EUNSUPPORTED;     // the act(aux) pass is elementwise
+    }
+    if (d->dtype != UNIIR_DT_BF16 && (GEMM_EXP_BUILD || d->dtype != UNIIR_DT_F16)) return UNIIR_EINVAL;
+    return UNIIR_OK;
+}
+
+// P6.  A weight gradient (C += A^T B, both operands K-major) whose reduction length is not a multiple of the 64-row K step -- the
+// packed text tower: K = the live rows of the batch -- would fall to the general 128-tile kernel for the WHOLE product (measured,
+// round 4: 188 us instead of ~45 us per text-tower weight gradient, 9 ms per train step).  The last K % 64 rows are a second,
+// tiny accumulating product instead; the multiple-of-64 part keeps the LDS-DMA kernel.  Every output element still receives its
+// additions in one fixed order (slab sum, then one add from the tail's only K step): deterministic.
+static bool gemm_head_tail(const uniir_gemm_desc* d, uniir_gemm_desc* head, uniir_gemm_desc* tail) {
+    if (!(d->a_tmaj && d->b_tmaj && d->epilogue == UNIIR_EPI_ATOMIC_F32 && (d->K % 64) && d->K >= 64 * 16 && d->M >= 256 && d->N >= 128))
+        return false;
+    *head = *tail = *d;
+    const int km = d->K / 64 * 64;
+    head->K = km;
+    tail->K = d->K - km;
+    tail->A = (const char*)d->A + (int64_t)km * d->lda * 2;
+    tail->B = (const char*)d->B + (int64_t)km * d->ldb * 2;
+    tail->k_splits = 1;
+    tail->splitk_ws = nullptr;
+    tail->splitk_ws_bytes = 0;
+    return true;
+}
+
+// P1 .. P5 of tests/test_gemm_paths_gpu.py: the kernel that runs the product
+enum GemmPath {
+    GEMM_P1,      // gemm_kernel, 128 x 128 tiles
+    GEMM_P2,      // gemm_glds_kernel<.., 1>: 256 x 256 tiles, counted loop
+    GEMM_P3,      // gemm_glds_kernel<.., 2>: ping-pong loop
+    GEMM_P4,      // gemm_glds_kernel<.., 3>: P3 with the row sums of A^T (bf16, both operands T-major)
+    GEMM_P5       // gemm_glds_kernel<.., 4>: P3 with the DACT 8-column copy-out (bf16, NT: the towers' c_proj dgrad)
+};
+// a side output (colsum, a_rowsum): inside the main kernel -- through order-fixed partials in the stream's reduction scratch that
+// gemm_run adds up, or by fp32 atomics when the scratch does not hold them -- or by uniir_colsum_bf16 after it
+enum GemmSide { SIDE_NONE, SIDE_FUSED, SIDE_PASS };
+struct GemmPlan {
+    GemmPath path;
+    int splits;            // k_splits, clamped so that no split is empty (an empty split would leave its slab unwritten)
+    bool slab;             // the splits store fp32 slabs in splitk_ws and splitk_reduce_kernel adds them to C; else fp32 atomics
+    GemmSide rowsum;       // SIDE_PASS: column sums of A as stored, after the product
+    GemmSide colsum;       // SIDE_PASS: column sums of the rounded bf16 result, after the product (P1 with DACT)
+    bool act_before;       // P1 with DACT and C2: act(aux) -> C2 by uniir_act_fwd before the product
+    // ONE request of the stream's scratch: the 256-row panels' column partials at its start, one row partial per (split, column
+    // panel) block at the next 256-B boundary.  When the two together do not fit, both keep their atomics.
+    int64_t col_bytes, row_off, row_bytes;
+};
+
+static GemmPlan gemm_plan(const uniir_gemm_desc* d, int shape) {
+    GemmPlan p = {};
+    p.splits = 1;
+    if (d->k_splits > 1) {
+        const int ksteps = (d->K + GEMM_BK - 1) / GEMM_BK;          // 64: every kernel shape splits K on multiples of 64
+        const int splits = d->k_splits > ksteps ? ksteps : d->k_splits;
+        const int per = (ksteps + splits - 1) / splits;
+        p.splits = (ksteps + per - 1) / per;
+        p.slab = d->splitk_ws && !((uintptr_t)d->splitk_ws & 15) && d->splitk_ws_bytes >= (int64_t)p.splits * d->M * d->N * 4;
+    }
+    const bool staged = shape == 1, bf16 = d->dtype == UNIIR_DT_BF16;
+    const bool pp = staged && pp_eligible(d, p.splits);
+    if (d->a_rowsum) p.rowsum = bf16 && d->b_tmaj && pp ? SIDE_FUSED : SIDE_PASS;
+    if (d->colsum) p.colsum = staged ? SIDE_FUSED : SIDE_PASS;
+    p.act_before = !staged && d->epilogue == UNIIR_EPI_DACT && d->C2;
+    // P5: DACT has one split, no slab and N % 8 == 0 by gemm_check; these are the terms a descriptor can still fail
+    const bool dact8 = d->epilogue == UNIIR_EPI_DACT && bf16 && !d->a_tmaj && d->b_tmaj && !d->bias && d->ldc % 8 == 0 &&
+                       d->ldaux % 8 == 0 && !((uintptr_t)d->aux & 15) && !((uintptr_t)d->C2 & 15);
+    p.path = !staged ? GEMM_P1 : !pp ? GEMM_P2 : GEMM_EXP_BUILD ? GEMM_P3 : p.rowsum == SIDE_FUSED ? GEMM_P4 : dact8 ? GEMM_P5 : GEMM_P3;
+    p.col_bytes = p.colsum == SIDE_FUSED ? (int64_t)((d->M + 255) / 256) * d->N * 4 : 0;
+    p.row_bytes = p.rowsum == SIDE_FUSED ? (int64_t)p.splits * ((d->N + 255) / 256) * d->M * 4 : 0;
+    p.row_off = (p.col_bytes + 255) / 256 * 256;
+    return p;
+}
+
+// what the main kernel reads
+static GemmKArgs gemm_args(const uniir_gemm_desc* d, const GemmPlan& p) {
+    GemmKArgs a = {};
+    a.A = (const unsigned short*)d->A;
+    a.B = (const unsigned short*)d->B;
+    a.C = d->C;
+    a.C2 = p.act_before ? nullptr : d->C2;
+    a.bias = d->bias;
+    a.resid = d->resid;
+    a.aux = (const unsigned short*)d->aux;
+    a.M = d->M; a.N = d->N; a.K = d->K;
+    a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc; a.ldaux = d->ldaux;
+    a.epilogue = d->epilogue; a.act = d->act; a.k_splits = p.splits;
+    a.row_scale = d->epilogue == UNIIR_EPI_RESID_F32 ? d->row_scale : nullptr;
+    if (d->epilogue == UNIIR_EPI_ACT_ONLY) {      // the BIAS_ACT epilogue without its first output: C receives act(v + bias)
+        a.epilogue = UNIIR_EPI_BIAS_ACT;
+        a.C2 = d->C;
+        a.skip_f = 1;
+    }
+    const int bm = p.path == GEMM_P1 ? GEMM_BM : Glds::BM, bn = p.path == GEMM_P1 ? GEMM_BN : Glds::BN;
+    a.tiles_m = (d->M + bm - 1) / bm;
+    a.tiles_n = (d->N + bn - 1) / bn;
+    if (p.path != GEMM_P1) {      // 2-D tile rasterisation: 8 row panels x 4 column panels per XCD working set (round-3 sweep, tools/r3)
+        a.raster_gm = p.path == GEMM_P4 ? 0 : 8;
+        a.raster_cw = 4;
+    }
+    a.alpha = d->alpha;
+    a.slab = p.slab ? (float*)d->splitk_ws : nullptr;
+    a.asm_loop = 2;
+    a.colsum = p.colsum == SIDE_FUSED ? d->colsum : nullptr;
+    a.a_rowsum = p.rowsum == SIDE_FUSED ? d->a_rowsum : nullptr;
+    return a;
+}
+
+// One launch of Kernel, the only place that raises a kernel's dynamic-LDS limit: before its first launch on a device (every
+// kernel, i.e. every instantiation of this template, has its own once-per-device flag).
+template <auto Kernel>
+static int gemm_launch(const GemmKArgs& a, int grid, int threads, int lds_bytes, hipStream_t st) {
+    static PerDeviceOnce attr_set;
+    if (attr_set.first()) (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(threads), lds_bytes, st, a);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+// the layout ladders of the 256-tile kernel (LOOP 1 counted, 2 ping-pong) and of the 128-tile kernel
+template <typename Elem, int LOOP>
+static int launch_glds(const GemmKArgs& a, bool at, bool bt, int grid, hipStream_t st) {
+    constexpr int T = Glds::T, L = Glds::LDS_BYTES;
+    if constexpr (GEMM_EXP_BUILD) {
+        if constexpr (LOOP == 2)
+            if (!at && !bt) return gemm_launch<gemm_glds_kernel<Elem, false, false, 2, 4, 64, 2>>(a, grid, T, L, st);
+        return UNIIR_EUNSUPPORTED;
+    } else {
+        if (!at && !bt) return gemm_launch<gemm_glds_kernel<Elem, false, false, 2, 4, 64, LOOP>>(a, grid, T, L, st);
+        if (!at) return gemm_launch<gemm_glds_kernel<Elem, false, true, 2, 4, 64, LOOP>>(a, grid, T, L, st);
+        if (!bt) return gemm_launch<gemm_glds_kernel<Elem, true, false, 2, 4, 64, LOOP>>(a, grid, T, L, st);
+        return gemm_launch<gemm_glds_kernel<Elem, true, true, 2, 4, 64, LOOP>>(a, grid, T, L, st);
+    }
+}
+template <typename Elem>
+static int launch_tile128(const GemmKArgs& a, bool at, bool bt, int grid, hipStream_t st) {
+    if constexpr (GEMM_EXP_BUILD) {
+        return UNIIR_EUNSUPPORTED;
+    } else {
+        if (!at && !bt) return gemm_launch<gemm_kernel<Elem, false, false>>(a, grid, 256, GEMM_LDS_BYTES, st);
+        if (!at) return gemm_launch<gemm_kernel<Elem, false, true>>(a, grid, 256, GEMM_LDS_BYTES, st);
+        if (!bt) return gemm_launch<gemm_kernel<Elem, true, false>>(a, grid, 256, GEMM_LDS_BYTES, st);
+        return gemm_launch<gemm_kernel<Elem, true, true>>(a, grid, 256, GEMM_LDS_BYTES, st);
+    }
+}
+// the main kernel of the plan's path; P4 and P5 exist for bf16 in one layout each
+template <typename Elem>
+static int launch_path(GemmPath path, const GemmKArgs& a, bool at, bool bt, hipStream_t st) {
+    const int tiles = a.tiles_m * a.tiles_n, grid = tiles * a.k_splits;
+    if constexpr (!GEMM_EXP_BUILD) {
+        if (path == GEMM_P4) return gemm_launch<gemm_glds_kernel<ElemBF16, true, true, 2, 4, 64, 3>>(a, grid, Glds::T, Glds::LDS_BYTES, st);
+        if (path == GEMM_P5) return gemm_launch<gemm_glds_kernel<ElemBF16, false, true, 2, 4, 64, 4>>(a, tiles, Glds::T, Glds::LDS_BYTES, st);
+    }
+    if (path == GEMM_P3) return launch_glds<Elem, 2>(a, at, bt, grid, st);
+    if (path == GEMM_P2) return launch_glds<Elem, 1>(a, at, bt, grid, st);
+    return launch_tile128<Elem>(a, at, bt, grid, st);
+}
+
+// the launches of one checked descriptor, in this order: act(aux) pass, main kernel, column partial reduce, row partial reduce,
+// column-sum pass, row-sum pass, slab reduce
+static int gemm_run(const uniir_gemm_desc* d, const GemmPlan& p, hipStream_t st) {
+    if (p.act_before) {
+        const int rc = uniir_act_fwd(d->aux, d->C2, (int64_t)d->M * d->N, d->act, st);
+        if (rc) return rc;
+    }
+    GemmKArgs a = gemm_args(d, p);
+    if (p.col_bytes || p.row_bytes) {
+        float* part = reduce_scratch(st, p.row_off + p.row_bytes);
+        if (part && p.col_bytes) a.colsum_part = part;
+        if (part && p.row_bytes) a.rowsum_part = (float*)((char*)part + p.row_off);
+    }
+    int rc;
+    if (d->dtype == UNIIR_DT_BF16) rc = launch_path<ElemBF16>(p.path, a, d->a_tmaj, d->b_tmaj, st);
+    else if constexpr (!GEMM_EXP_BUILD) rc = launch_path<ElemF16>(p.path, a, d->a_tmaj, d->b_tmaj, st);
+    else rc = UNIIR_EINVAL;
+    if (rc) return rc;
+    if (a.colsum_part) {
+        rc = reduce_partials(a.colsum_part, a.tiles_m, d->N, d->N, d->colsum, nullptr, nullptr, 0, st);
+        if (rc) return rc;
+    }
+    if (a.rowsum_part) {
+        rc = reduce_partials(a.rowsum_part, p.splits * a.tiles_n, d->M, d->M, d->a_rowsum, nullptr, nullptr, 0, st);
+        if (rc) return rc;
+    }
+    if (p.colsum == SIDE_PASS) {
+        rc = uniir_colsum_bf16(d->C, d->ldc, d->colsum, d->M, d->N, st);
+        if (rc) return rc;
+    }
+    if (p.rowsum == SIDE_PASS) {
+        rc = uniir_colsum_bf16(d->A, d->lda, d->a_rowsum, d->K, d->M, st);
+        if (rc) return rc;
+    }
+    if (p.slab) {
+        const long mn = (long)d->M * d->N;
+        long g = (mn / 4 + 255) / 256;
+        if (g > 4096) g = 4096;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, st, a.slab, p.splits, mn, d->N,
+                           (float*)d->C, (long)d->ldc);
+        HIP_LAUNCH_CHECK();
+    }
+    return UNIIR_OK;
+}
+
+static int gemm_one(const uniir_gemm_desc* d, hipStream_t st) {
+    const int shape = gemm_shape(d->M, d->N, d->K);
+    const int rc = gemm_check(d, shape);
+    return rc ? rc : gemm_run(d, gemm_plan(d, shape), st);
+}
+// the head and the tail of P6 are checked like every descriptor: whatever the whole is refused for, the head is refused for too
+// (they differ in K alone, which stays a positive multiple of 64), before anything runs
+static int gemm_impl(const uniir_gemm_desc* d, void* stream) {
+    if (!d) return UNIIR_EINVAL;
+    uniir_gemm_desc head, tail;
+    if (!gemm_head_tail(d, &head, &tail)) return gemm_one(d, (hipStream_t)stream);
+    const int rc = gemm_one(&head, (hipStream_t)stream);
+    return rc ? rc : gemm_one(&tail, (hipStream_t)stream);
+}
+
+// The split-K factor of a weight gradient over `rows` rows with `tiles` 256 x 256 output tiles: tiles * splits lands just under a
+// multiple of the CU count (no nearly-empty last round) while every split keeps >= 16 K steps of 64 rows.  The one body of the
+// rule: the C towers and the Python layers both call it, so the same layer is summed in the same order on either.
+extern "C" int32_t uniir_gemm_wgrad_splits(int32_t rows, int32_t tiles) {
+    const int ncu = 256;        // MI355X compute units; the 256 x 256 kernel runs one workgroup per CU
+    int max_s = rows / (64 * 16);
+    if (max_s < 1) max_s = 1;
+    if (max_s > 64) max_s = 64;
+    int best = 1;
+    double best_eff = 0.0;
+    for (int s = 1; s <= max_s; ++s) {
+        const int blocks = tiles * s;
+        const int rounds = (blocks + ncu - 1) / ncu;
+        const double eff = (double)blocks / ((double)rounds * ncu);
+        if (blocks >= 0.9 * ncu && eff >= 0.9) return s;      // the smallest split count that fills the chip (least slab traffic)
+        if (eff > best_eff + 1e-9) { best = s; best_eff = eff; }
+    }
+    return best;
 }
 
 // Measurement hook (bench.py roofline): every `stride`-th uniir_gemm call is bracketed by a pair of HIP events on the stream
@@ -1033,7 +1207,6 @@ extern "C" int uniir_gemm_timing_filter(const float* windows, int32_t nwin, cons
     return kept;
 }
 
-static int gemm_impl(const uniir_gemm_desc* d, void* stream);
 extern "C" int uniir_gemm(const uniir_gemm_desc* d, void* stream) {
     if (g_gt.stride > 0 && d && g_gt.filter && g_gt.only != (hipStream_t)stream) {          // another stream while one is measured
         if (g_gt.nf >= GT_FMAX) return gemm_impl(d, stream);
@@ -1054,162 +1227,4 @@ extern "C" int uniir_gemm(const uniir_gemm_desc* d, void* stream) {
         g_gt.n = i + 1;
     }
     return rc;
-}
-
-static int gemm_impl(const uniir_gemm_desc* d, void* stream) {
-    if (!d || !d->A || !d->B || !d->C) return UNIIR_EINVAL;
-    if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->k_splits < 1) return UNIIR_EINVAL;
-    if (d->epilogue < 0 || d->epilogue > UNIIR_EPI_ACT_ONLY) return UNIIR_EINVAL;
-    if (d->k_splits > 1 && d->epilogue != UNIIR_EPI_ATOMIC_F32) return UNIIR_EINVAL;
-    if (d->epilogue == UNIIR_EPI_ACT_ONLY && d->C2) return UNIIR_EINVAL;
-    if (d->row_scale && d->epilogue != UNIIR_EPI_RESID_F32) return UNIIR_EINVAL;
-    if (d->epilogue == UNIIR_EPI_BIAS_ACT && !d->C2) return UNIIR_EINVAL;
-    if (d->epilogue == UNIIR_EPI_DACT && !d->aux) return UNIIR_EINVAL;
-    // column sums of the result ride the fp32 copy-out passes only (DACT / RESID_F32 / F32 epilogues)
-    if (d->colsum && d->epilogue != UNIIR_EPI_DACT && d->epilogue != UNIIR_EPI_RESID_F32 && d->epilogue != UNIIR_EPI_F32)
-        return UNIIR_EUNSUPPORTED;
-    // fp16 operands (the forward-only embedding towers): the 16-bit outputs of EPI_BF16 / BIAS_ACT / ACT_ONLY are fp16 as well; the
-    // backward-side epilogues (activation gradient, the bf16 copy of a residual output) exist for bf16 only
-    if (d->dtype == UNIIR_DT_F16 && (d->epilogue == UNIIR_EPI_DACT || (d->epilogue == UNIIR_EPI_RESID_F32 && d->C2))) return UNIIR_EUNSUPPORTED;
-    if (d->N % 8) return UNIIR_ESHAPE;
-    if (!d->a_tmaj && (d->K % 8)) return UNIIR_ESHAPE;
-    if (!d->b_tmaj && (d->K % 8)) return UNIIR_ESHAPE;
-    if (d->a_tmaj && (d->M % 8)) return UNIIR_ESHAPE;
-    if ((d->lda % 8) || (d->ldb % 8) || (d->ldc % 4)) return UNIIR_EALIGN;
-    if (((uintptr_t)d->A & 15) || ((uintptr_t)d->B & 15) || ((uintptr_t)d->C & 15)) return UNIIR_EALIGN;
-    if (d->aux && ((d->ldaux % 4) || ((uintptr_t)d->aux & 7))) return UNIIR_EALIGN;
-    if (d->bias && ((uintptr_t)d->bias & 15)) return UNIIR_EALIGN;
-    // a bias has no single meaning for an accumulating product that may run as several splits, slabs or a head and a tail
-    if (d->bias && d->epilogue == UNIIR_EPI_ATOMIC_F32) return UNIIR_EUNSUPPORTED;
-    // A weight gradient (C += A^T B, both operands K-major) whose reduction length is not a multiple of the 64-row K step -- the
-    // packed text tower: K = the live rows of the batch -- would fall to the general 128-tile kernel for the WHOLE product (measured,
-    // round 4: 188 us instead of ~45 us per text-tower weight gradient, 9 ms per train step).  The last K % 64 rows are a second,
-    // tiny accumulating product instead; the multiple-of-64 part keeps the LDS-DMA kernel.  Every output element still receives its
-    // additions in one fixed order (slab sum, then one add from the tail's only K step): deterministic.
-    if (d->a_tmaj && d->b_tmaj && d->epilogue == UNIIR_EPI_ATOMIC_F32 && (d->K % 64) && d->K >= 64 * 16 && d->M >= 256 && d->N >= 128) {
-        uniir_gemm_desc head = *d, tail = *d;
-        const int km = d->K / 64 * 64;
-        head.K = km;
-        tail.K = d->K - km;
-        tail.A = (const char*)d->A + (int64_t)km * d->lda * 2;
-        tail.B = (const char*)d->B + (int64_t)km * d->ldb * 2;
-        tail.k_splits = 1;
-        tail.splitk_ws = nullptr;
-        tail.splitk_ws_bytes = 0;
-        const int rc = gemm_impl(&head, stream);
-        return rc ? rc : gemm_impl(&tail, stream);
-    }
-    GemmKArgs a;
-    a.A = (const unsigned short*)d->A;
-    a.B = (const unsigned short*)d->B;
-    a.C = d->C;
-    a.C2 = d->C2;
-    a.bias = d->bias;
-    a.resid = d->resid;
-    a.aux = (const unsigned short*)d->aux;
-    a.M = d->M; a.N = d->N; a.K = d->K;
-    a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc; a.ldaux = d->ldaux;
-    a.epilogue = d->epilogue; a.act = d->act; a.k_splits = d->k_splits;
-    a.skip_f = 0;
-    a.row_scale = d->epilogue == UNIIR_EPI_RESID_F32 ? d->row_scale : nullptr;
-    if (d->epilogue == UNIIR_EPI_ACT_ONLY) {      // the BIAS_ACT epilogue without its first output: C receives act(v + bias)
-        a.epilogue = UNIIR_EPI_BIAS_ACT;
-        a.C2 = d->C;
-        a.skip_f = 1;
-    }
-
-    a.tiles_m = (d->M + GEMM_BM - 1) / GEMM_BM;
-    a.tiles_n = (d->N + GEMM_BN - 1) / GEMM_BN;
-    a.alpha = d->alpha;
-    a.slab = nullptr;
-    a.colsum = d->colsum;
-    a.a_rowsum = nullptr;
-    a.colsum_part = nullptr;
-    a.rowsum_part = nullptr;
-    a.asm_loop = 2;
-    hipStream_t st = (hipStream_t)stream;
-    if (d->k_splits > 1) {
-        // never leave a split empty (an empty split would leave its slab unwritten)
-        const int bk = GEMM_BK;  // 64: every kernel shape splits K on multiples of 64
-        const int ksteps = (d->K + bk - 1) / bk;
-        int splits = d->k_splits > ksteps ? ksteps : d->k_splits;
-        const int per = (ksteps + splits - 1) / splits;
-        splits = (ksteps + per - 1) / per;
-        a.k_splits = splits;
-        if (d->splitk_ws && !((uintptr_t)d->splitk_ws & 15) && (d->N % 4 == 0) &&
-            d->splitk_ws_bytes >= (int64_t)splits * d->M * d->N * 4)
-            a.slab = (float*)d->splitk_ws;
-    }
-    // row sums of A^T (the bias gradient of a weight-gradient GEMM): inside the transposed ping-pong kernel when the problem
-    // runs it, otherwise as a separate pass over A
-    bool rowsum_fused = false;
-    if (d->a_rowsum) {
-        if (!d->a_tmaj || d->dtype != UNIIR_DT_BF16) return UNIIR_EUNSUPPORTED;     // (the separate pass reads bf16 too)
-        rowsum_fused = d->dtype == UNIIR_DT_BF16 && d->b_tmaj && pp_eligible(a, d->a_tmaj, d->b_tmaj);
-        if (rowsum_fused) a.a_rowsum = d->a_rowsum;
-    }
-    int rc;
-    // colsum and the DACT epilogue's second output act(aux) exist in the LDS-staged epilogue of the 256-tile kernel only; when the
-    // problem runs the general 128-tile kernel they are produced HERE by separate passes (bf16 column sums of the stored result,
-    // act(aux) elementwise), so that callers need not mirror gemm_shape()
-    const bool staged = gemm_shape(a, d->a_tmaj, d->b_tmaj) == 1;
-    bool colsum_after = false;
-    if (!staged) {
-        if (d->colsum) {
-            if (d->epilogue != UNIIR_EPI_DACT) return UNIIR_EUNSUPPORTED;      // fp32 outputs: no separate column-sum pass exists
-            if (d->ldc % 8) return UNIIR_EUNSUPPORTED;         // the pass reads 16-B row pieces: rejected before anything runs
-            a.colsum = nullptr;
-            colsum_after = true;
-        }
-        if (d->epilogue == UNIIR_EPI_DACT && d->C2) {
-            if (d->ldaux != d->N) return UNIIR_EUNSUPPORTED;
-            rc = uniir_act_fwd(d->aux, d->C2, (int64_t)d->M * d->N, d->act, stream);
-            if (rc) return rc;
-            a.C2 = nullptr;
-        }
-    }
-    // deterministic partials out of ONE request of the stream's scratch: the 256-row panels' column partials at its start, one row
-    // partial per (split, column panel) block of the fused row sums (the 256 x 256 kernel's own panel counts: launch_glds_rowsum) at
-    // the next 256-B boundary; both reduced in order below.  When the two together do not fit, both keep their atomics.
-    {
-        const int64_t cbytes = (staged && a.colsum && (d->N % 4 == 0)) ? (int64_t)((d->M + 255) / 256) * d->N * 4 : 0;
-        const int64_t rbytes = rowsum_fused ? (int64_t)a.k_splits * ((d->N + 255) / 256) * d->M * 4 : 0;
-        const int64_t roff = (cbytes + 255) / 256 * 256;
-        if (cbytes || rbytes) {
-            float* part = reduce_scratch(st, roff + rbytes);
-            if (part && cbytes) a.colsum_part = part;
-            if (part && rbytes) a.rowsum_part = (float*)((char*)part + roff);
-        }
-    }
-    if (d->dtype == UNIIR_DT_BF16) rc = launch_gemm<ElemBF16>(a, d->a_tmaj, d->b_tmaj, st);
-#ifndef UNIIR_EXP_BUILD
-    else if (d->dtype == UNIIR_DT_F16) rc = launch_gemm<ElemF16>(a, d->a_tmaj, d->b_tmaj, st);
-#endif
-    else return UNIIR_EINVAL;
-    if (rc) return rc;
-    if (a.colsum_part) {
-        rc = reduce_partials(a.colsum_part, (d->M + 255) / 256, d->N, d->N, d->colsum, nullptr, nullptr, 0, st);
-        if (rc) return rc;
-    }
-    if (a.rowsum_part) {
-        rc = reduce_partials(a.rowsum_part, a.k_splits * ((d->N + 255) / 256), d->M, d->M, d->a_rowsum, nullptr, nullptr, 0, st);
-        if (rc) return rc;
-    }
-    if (colsum_after) {
-        rc = uniir_colsum_bf16(d->C, d->ldc, d->colsum, d->M, d->N, stream);
-        if (rc) return rc;
-    }
-    if (d->a_rowsum && !rowsum_fused) {
-        rc = uniir_colsum_bf16(d->A, d->lda, d->a_rowsum, d->K, d->M, stream);
-        if (rc) return rc;
-    }
-    if (a.slab) {
-        const long mn = (long)d->M * d->N;
-        long g = (mn / 4 + 255) / 256;
-        if (g > 4096) g = 4096;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, st, a.slab, a.k_splits, mn, d->N,
-                           (float*)d->C, (long)d->ldc);
-        HIP_LAUNCH_CHECK();
-    }
-    return UNIIR_OK;
 }

@@ -188,33 +188,18 @@ int linear_dgrad(const void* dy, const void* w, void* out, int M, int N, int K, 
     return UNIIR_OK;
 }
 
-int wgrad_splits(int rows, int tiles) {     // ops.wgrad_splits: fill the 256 CUs, >= 16 K steps per split
-    const int ncu = 256;
-    int max_s = rows / (64 * 16);
-    if (max_s < 1) max_s = 1;
-    if (max_s > 64) max_s = 64;
-    int best = 1;
-    double best_eff = 0.0;
-    for (int s = 1; s <= max_s; ++s) {
-        const int blocks = tiles * s;
-        const int rounds = (blocks + ncu - 1) / ncu;
-        const double eff = (double)blocks / ((double)rounds * ncu);
-        if (blocks >= 0.9 * ncu && eff >= 0.9) return s;
-        if (eff > best_eff + 1e-9) { best = s; best_eff = eff; }
-    }
-    return best;
-}
-
-// dw[N,K] (fp32) += dy[M,N]^T @ x[M,K]
+// dw[N,K] (fp32) += dy[M,N]^T @ x[M,K], dy with leading dimension lddy (its N columns may be a column range of wider rows)
 // dbias (optional): += column sums of dy, from the same pass over dy
+// The slab workspace is offered only when it holds the split count ASKED for, which is stricter than uniir_gemm's own rule when the
+// library clamps the splits (520 K steps at 32 splits run as 31): such products keep their atomics.
 int linear_wgrad(const uniir_clip_tower* t, const void* dy, const void* x, float* dw, int M, int N, int K, void* st,
-                 float* dbias = nullptr) {
+                 float* dbias = nullptr, int64_t lddy = 0) {
     uniir_gemm_desc d;
     base_desc(d);
     d.A = dy; d.B = x; d.C = dw; d.a_rowsum = dbias;
-    d.M = N; d.N = K; d.K = M; d.lda = N; d.ldb = K; d.ldc = K; d.a_tmaj = 1; d.b_tmaj = 1;
+    d.M = N; d.N = K; d.K = M; d.lda = lddy ? lddy : N; d.ldb = K; d.ldc = K; d.a_tmaj = 1; d.b_tmaj = 1;
     d.epilogue = UNIIR_EPI_ATOMIC_F32;
-    d.k_splits = wgrad_splits(M, ((N + 255) / 256) * ((K + 255) / 256));
+    d.k_splits = uniir_gemm_wgrad_splits(M, ((N + 255) / 256) * ((K + 255) / 256));
     if (d.k_splits > 1 && t->splitk_ws && t->splitk_ws_bytes >= (int64_t)4 * d.k_splits * N * K) {
         d.splitk_ws = t->splitk_ws;
         d.splitk_ws_bytes = t->splitk_ws_bytes;
@@ -465,17 +450,9 @@ int last_block_bwd_pooled(const uniir_clip_tower* t, const Plan& p, char* ws, vo
     TRY(attention_pooled_bwd_impl(ws + p.pl_q, (char*)l.qkv + (int64_t)W * 2, (char*)l.qkv + (int64_t)W * 4, 3 * W, ws + p.pl_ao, pdh,
                                   (float*)(ws + p.pl_lse), px.klen, px.klen_add, px.kv_row_off, pdqkv, 3 * W,
                                   (char*)dqkv + (int64_t)W * 2, (char*)dqkv + (int64_t)W * 4, 3 * W, M, p.T, p.H, st));
+    // in_proj weight / bias gradient, K | V rows: over every row
+    TRY(linear_wgrad(t, (char*)dqkv + (int64_t)W * 2, l.h1, b.g_wqkv + (int64_t)W * W, R, 2 * W, W, st, b.g_bqkv + W, 3 * W));
     uniir_gemm_desc d;
-    base_desc(d);       // in_proj weight / bias gradient, K | V rows: over every row
-    d.A = (char*)dqkv + (int64_t)W * 2; d.B = l.h1; d.C = b.g_wqkv + (int64_t)W * W; d.a_rowsum = b.g_bqkv + W;
-    d.M = 2 * W; d.N = W; d.K = R; d.lda = 3 * W; d.ldb = W; d.ldc = W; d.a_tmaj = 1; d.b_tmaj = 1;
-    d.epilogue = UNIIR_EPI_ATOMIC_F32;
-    d.k_splits = wgrad_splits(R, ((2 * W + 255) / 256) * ((W + 255) / 256));
-    if (d.k_splits > 1 && t->splitk_ws && t->splitk_ws_bytes >= (int64_t)4 * d.k_splits * 2 * W * W) {
-        d.splitk_ws = t->splitk_ws;
-        d.splitk_ws_bytes = t->splitk_ws_bytes;
-    }
-    TRY(uniir_gemm(&d, st));
     base_desc(d);       // ... Q rows: over the pooled rows
     d.A = pdqkv; d.B = ws + p.pl_h1; d.C = b.g_wqkv; d.a_rowsum = b.g_bqkv;
     d.M = W; d.N = W; d.K = M; d.lda = 3 * W; d.ldb = W; d.ldc = W; d.a_tmaj = 1; d.b_tmaj = 1; d.epilogue = UNIIR_EPI_ATOMIC_F32;

@@ -149,12 +149,6 @@ def _splitk_workspace(device, nbytes, tag=None):
     return ws
 
 
-def uses_tile256(M, N, K):
-    """mirror of gemm_shape() in csrc/gemm.hip: the 256x256 LDS-DMA kernel (the only one with the fused column-sum
-    epilogue) runs when K % 64 == 0 and the problem is not tiny"""
-    return K % 64 == 0 and M >= 256 and N >= 128
-
-
 def gemm(A, B, C_out, M, N, K, lda, ldb, ldc, *, a_tmaj=False, b_tmaj=False, epilogue=EPI_BF16, bias=None,
          resid=None, aux=None, ldaux=0, C2=None, act=ACT_QUICKGELU, k_splits=1, alpha=1.0, dtype=DT_BF16,
          colsum=None, row_scale=None, a_rowsum=None):
@@ -191,42 +185,25 @@ def linear_fwd(x, w, bias=None, *, out=None, epilogue=EPI_BF16, resid=None, C2=N
 def linear_dgrad(dy, w, *, out=None, aux=None, act=ACT_QUICKGELU, act_out=None, colsum=None):
     """dx[M,K] = dy[M,N] @ w[N,K]  (optionally * act'(aux)).
     act_out (bf16 [M,K]): also receives act(aux), the recomputed activation (needs aux).
-    colsum (fp32 [K]): += column sums of dx (the bias gradient of the layer that produced aux); fused into the GEMM
-    epilogue when the 256-tile kernel runs, otherwise done by the colsum kernel on the bf16 result."""
+    colsum (fp32 [K]): += column sums of dx (the bias gradient of the layer that produced aux).  With aux the library produces
+    act_out and colsum itself whichever kernel the problem runs (fused in the 256-tile epilogue, separate passes otherwise);
+    without aux the product has the plain bf16 epilogue, which takes no colsum: the colsum kernel sums the bf16 result."""
     M, N = dy.shape
     K = w.shape[1]
     if out is None:
         out = torch.empty(M, K, device=dy.device, dtype=torch.bfloat16)
-    fused = colsum is not None and aux is not None and uses_tile256(M, K, N)
-    if act_out is not None and not (aux is not None and uses_tile256(M, K, N)):
-        call("uniir_act_fwd", aux, act_out, aux.numel(), act)
-        act_out_arg = None
-    else:
-        act_out_arg = act_out
+    if act_out is not None and aux is None:
+        raise ValueError("act_out needs aux")
     gemm(dy, w, out, M, K, N, N, K, K, b_tmaj=True, epilogue=EPI_DACT if aux is not None else EPI_BF16,
-         aux=aux, ldaux=K, act=act, C2=act_out_arg, colsum=colsum if fused else None)
-    if colsum is not None and not fused:
+         aux=aux, ldaux=K, act=act, C2=act_out, colsum=colsum if aux is not None else None)
+    if colsum is not None and aux is None:
         call("uniir_colsum_bf16", out, K, colsum, M, K)
     return out
 
 
-N_CU = 256  # MI355X compute units; the 256x256 GEMM kernel runs one workgroup per CU
-
-
 def wgrad_splits(rows, tiles):
-    """split-K factor for dW (256x256 output tiles): make tiles*splits land just under a multiple of the CU count
-    (no nearly-empty last round) while every split keeps >= 16 K steps of 64 rows."""
-    max_s = max(1, rows // (64 * 16))
-    best, best_eff = 1, 0.0
-    for s in range(1, min(max_s, 64) + 1):
-        blocks = tiles * s
-        rounds = -(-blocks // N_CU)
-        eff = blocks / (rounds * N_CU)
-        if blocks >= 0.9 * N_CU and eff >= 0.9:
-            return s            # smallest split count that fills the chip (least slab traffic)
-        if eff > best_eff + 1e-9:
-            best, best_eff = s, eff
-    return best
+    """split-K factor for dW (256x256 output tiles): uniir_gemm_wgrad_splits, the rule the C towers use too"""
+    return _lib.load().uniir_gemm_wgrad_splits(int(rows), int(tiles))
 
 
 def linear_wgrad(dy, x, dw, *, dbias=None):
