@@ -169,6 +169,8 @@ int uniir_layernorm_bwd_ex(const float* x, int64_t x_stride, const float* gamma,
  *                                                fusion stack over the 577 + 77 tokens of ViT-L/14@336px
  *   uniir_attention_one_fwd / _one_bwd         : ONE query row per item against tk <= 1024 dense keys (the pooled last block of a
  *                                                tower); the backward is one pass over K and V, bitwise reproducible
+ *   uniir_onequery_fwd / _bwd                  : ONE query row per item against tk <= 1024 keys with key_len or packed keys and dropout
+ *                                                at the coordinates of the full call (the class row of BLIP's last BERT layer)
  *   Still 512 at most: the causal mask, fully packed rows (_packed, _rows with kv_packed).
  * qkv bf16 [batch*seq][3*heads*64] as produced by nn.MultiheadAttention.in_proj ([q | k | v] per row);
  * out bf16 [batch*seq][heads*64]; lse f32 [batch][heads][seq] (natural log-sum-exp of scaled scores).
@@ -264,6 +266,37 @@ int uniir_attention_one_fwd(const void* q, const void* k, const void* v, int64_t
 int uniir_attention_one_bwd(const void* q, const void* k, const void* v, int64_t kv_ld, const void* out, const void* dout,
                             const float* lse, void* dq, int64_t dq_ld, void* dk, void* dv, int64_t dkv_ld, int32_t batch, int32_t tk,
                             int32_t heads, void* stream);
+/* ONE query row per item that STANDS FOR ROW drop_q OF A CALL WITH drop_tq QUERY ROWS (bf16, head_dim 64, scale 1/8, no causal mask, no
+ * bias): per-item key counts, packed keys and probability dropout in the one-query form.  BLIP's last BERT layer on the class row
+ * (BLIPFeatureFusion.pool_last_layer): only row 0 of every caption leaves the encoder.
+ * q / out / dout: [batch] rows with leading dimensions q_ld / out_ld (a dense BERT passes row m*L of its [q | k | v] buffer with q_ld =
+ * L*3*heads*64 and copies nothing); lse [batch][heads]; dq [batch] rows with leading dimension dq_ld.
+ * Keys, one of two forms (both given: UNIIR_EINVAL):
+ *   dense : k / v / dk / dv are [batch][tk] rows (kv_ld / dkv_ld), key_len optional: 1 <= key_len[m], values above tk count as tk,
+ *           keys at or behind it are masked as in uniir_attention_fwd_ex; the backward writes exact zeros to their dk / dv rows;
+ *   packed: kv_row_off[batch + 1]: item m's keys are the rows kv_row_off[m] .. kv_row_off[m + 1] - 1 of k / v / dk / dv, its key count
+ *           its own length (1 <= length <= tk).  No row of another item is read or written.
+ * 1 <= tk <= 1024.  Dropout: the factor of key j is drawn at the dense coordinate ((m * heads + h) * drop_tq + drop_q) * tk + j (modulo
+ * 2^32) -- the coordinate of that row in uniir_attention_fwd_ex / _fwd_rows / _fwd_long with tq = drop_tq; the softmax statistics come
+ * from the undropped P.  1 <= drop_tq, 0 <= drop_q < drop_tq.
+ * _fwd: out and lse are bitwise row drop_q of the full call on the same operands and seed with tq = drop_tq: uniir_attention_fwd_ex
+ * (key_len) or uniir_attention_fwd_rows (kv_packed = 1 for packed keys, 0 for dense ones) up to 512 keys, uniir_attention_fwd_long
+ * above.  Kernels by key range: tk <= 512 the resident kernel of those entry points at one query row (a head's keys whole in LDS);
+ * 513 .. 1024 the streaming kernel of uniir_attention_fwd_long at one query row (keys in 128-key chunks), which alone also takes
+ * packed keys here.  A query row's result never depends on the rows that share its tile.
+ * _bwd: the one-pass kernel of uniir_attention_one_bwd at every tk, extended by the key count and the dropout factor (dV[j] = p_j f_j
+ * dO, dP_j = f_j dO . v_j, delta = dO . O): one wave per (item, head), no LDS, no atomics, every sum in a fixed order -- two calls
+ * give the same bits.  Without key_len, kv_row_off and dropout it launches the kernel of uniir_attention_one_bwd itself.
+ * UNIIR_EINVAL: a NULL operand (key_len and kv_row_off may be NULL), heads <= 0, batch < 0, drop_p outside [0, 1) (a NaN included),
+ * drop_tq < 1, drop_q outside 0 .. drop_tq - 1, both key forms; UNIIR_ESHAPE: tk outside 1 .. 1024; UNIIR_EALIGN: a leading
+ * dimension that is no multiple of 8 or a pointer that is not 16-byte aligned.  A refused call writes nothing; batch == 0 is UNIIR_OK. */
+int uniir_onequery_fwd(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, void* out, int64_t out_ld, float* lse,
+                       const int32_t* key_len, const int32_t* kv_row_off, int32_t batch, int32_t tk, int32_t heads, float drop_p,
+                       uint32_t drop_seed, int32_t drop_tq, int32_t drop_q, void* stream);
+int uniir_onequery_bwd(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, const void* out, const void* dout,
+                       int64_t out_ld, const float* lse, const int32_t* key_len, const int32_t* kv_row_off, void* dq, int64_t dq_ld,
+                       void* dk, void* dv, int64_t dkv_ld, int32_t batch, int32_t tk, int32_t heads, float drop_p, uint32_t drop_seed,
+                       int32_t drop_tq, int32_t drop_q, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * [ENC] small fused pieces of the towers.

@@ -47,6 +47,33 @@ def attn_only(items):
     print(f"cross attn 100x197 fwd: {t*1e3:.3f} ms {4*b*H*tq*tk*64/t/1e12:.1f} TF/s")
 
 
+def onequery_only(items):
+    """the one-query backward at BLIP's cross-attention shape (577 keys x 12 heads, K | V in a [k | v] buffer): uniir_attention_one_bwd
+    against uniir_onequery_bwd without and with dropout, and with per-item key counts; four alternating rounds, median of 20 calls
+    each (profiles/blip_pooled_last_layer.txt)"""
+    torch.manual_seed(0)
+    b, T, H = items, int(os.environ.get("MB_TOKENS", "577")), 12
+    W = H * 64
+    q = torch.randn(b, W, device=dev).bfloat16()
+    kv = torch.randn(b * T, 2 * W, device=dev).bfloat16()
+    out, lse = ops.attention_one_fwd(q, kv, kv[:, W:], 2 * W, b, T, H)
+    do = torch.randn_like(out)
+    dq = torch.empty_like(q)
+    dkv = torch.empty_like(kv)
+    klen = torch.randint(5, T + 1, (b,), device=dev, dtype=torch.int32)
+    new = lambda **kw: ops.onequery_bwd(q, W, kv, kv[:, W:], 2 * W, out, do, lse, dq, W, dkv, dkv[:, W:], 2 * W, b, T, H, drop_tq=100, **kw)  # noqa: E731
+    arms = [("uniir_attention_one_bwd", lambda: ops.attention_one_bwd(q, kv, kv[:, W:], 2 * W, out, do, lse, dq, W, dkv, dkv[:, W:], 2 * W, b, T, H)),
+            ("uniir_onequery_bwd plain (the same kernel)", lambda: new()),
+            ("uniir_onequery_bwd drop_p 0.1", lambda: new(drop_p=0.1, drop_seed=7)),
+            ("uniir_onequery_bwd key_len U{5..T}", lambda: new(key_len=klen)),
+            ("uniir_onequery_bwd key_len + drop_p 0.1", lambda: new(key_len=klen, drop_p=0.1, drop_seed=7))]
+    mb = (4 * b * T * W * 2 + 4 * b * W * 2) / 1e6
+    for rnd in range(4):
+        for name, fn in arms:
+            t = timeit(fn, iters=20)
+            print(f"onequery bwd T={T} H={H} b={b} round {rnd} {name}: {t*1e6:.1f} us  ({mb / t / 1e6:.2f} TB/s of the dense K, V, dK, dV bytes)")
+
+
 def main():
     items = int(os.environ.get("MB_ITEMS", "256"))
     R = items * 257
@@ -54,6 +81,8 @@ def main():
     only = os.environ.get("MB_ONLY", "")
     if only == "attn":
         return attn_only(items)
+    if only == "onequery":
+        return onequery_only(items)
     for (N, K, name) in ([] if os.environ.get("MB_SKIP_GEMM") else [(3072, 1024, "qkv"), (1024, 1024, "out"), (4096, 1024, "fc"), (1024, 4096, "proj")]):
         x = torch.randn(R, K, device=dev).bfloat16()
         w = torch.randn(N, K, device=dev).bfloat16()

@@ -108,6 +108,9 @@ SIGNATURES = {
                                          c_int, c_int, c_float, C.c_uint32, S]),
     "uniir_attention_one_fwd": (c_int, [P, P, P, c_i64, P, P, c_int, c_int, c_int, c_int, S]),
     "uniir_attention_one_bwd": (c_int, [P, P, P, c_i64, P, P, P, P, c_i64, P, P, c_i64, c_int, c_int, c_int, S]),
+    "uniir_onequery_fwd": (c_int, [P, c_i64, P, P, c_i64, P, c_i64, P, P, P, c_int, c_int, c_int, c_float, C.c_uint32, c_int, c_int, S]),
+    "uniir_onequery_bwd": (c_int, [P, c_i64, P, P, c_i64, P, P, c_i64, P, P, P, P, c_i64, P, P, c_i64, c_int, c_int, c_int, c_float,
+                                   C.c_uint32, c_int, c_int, S]),
     "uniir_patchify": (c_int, [P, P, c_int, c_int, c_int, c_int, S]),
     "uniir_vit_assemble": (c_int, [P, P, P, P, c_int, c_int, c_int, S]),
     "uniir_vit_assemble_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, S]),

@@ -18,6 +18,7 @@ stash.  Differences from the reference, stated once:
 """
 import json
 import logging
+import os
 
 import torch
 from torch import nn
@@ -200,7 +201,8 @@ class TextPack:
         return TextPack(lens, L, dev)
 
 
-def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, pool=True, drop=None, pack=None):
+def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, pool=True, drop=None, pack=None, pool_last=False,
+                 log=None):
     """src/models/uniir_blip/backbone/med.py BertModel.forward(mode="multimodal") -> pooler_output fp32 [M,W] + stash.
     ids int32 [M,L]; key_len int32 [M]; img16 bf16 [M*Ti, enc_width] (image attention mask all ones, blip_ff.py:98,108).
     cross=False: mode "text" (the cross-attention sublayer is skipped, BLIP_SF); pool=False: add_pooling_layer=False, the
@@ -208,7 +210,10 @@ def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, poo
     drop (ops.DropSeeds, train mode): hidden dropout after the embedding LayerNorm and after each of the three output
     dense layers (before the residual add), attention-probability dropout inside both attention kernels.
     pack (TextPack): run on the rows up to each caption's valid length only -- same pooled output bit for bit (train mode included),
-    parameter gradients equal up to the order of the fp32 additions in the weight-gradient reductions."""
+    parameter gradients equal up to the order of the fp32 additions in the weight-gradient reductions.
+    pool_last (BLIPFeatureFusion.pool_last_layer): only the class row of every item leaves the encoder, so the LAST layer runs on
+    those M rows (_bert_last_layer_pooled): the same class row bit for bit, train mode included.  log: a list that gets a line
+    when it does."""
     W, I, eps = cfg["hidden_size"], cfg["intermediate_size"], cfg["layer_norm_eps"]
     heads, layers = cfg["num_attention_heads"], cfg["num_hidden_layers"]
     M, L = ids.shape
@@ -235,18 +240,18 @@ def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, poo
     self_kw = dict(key_len=key_len) if pack is None else dict(row_off=roff, kv_packed=True, rows=R)
     cross_kw = {} if pack is None else dict(row_off=roff, kv_packed=False, rows=R)
 
-    def out_dense(x16, name, resid):
+    def out_dense(x16, name, resid, row_map=rmap):
         """dense -> dropout -> + residual (BertSelfOutput / BertOutput, med.py:196-200,339-343), pre-LayerNorm sum"""
         if not ph:
             return ops.linear_fwd(x16, st.w16(name + "weight"), st.p(name + "bias"), epilogue=ops.EPI_RESID_F32,
                                   resid=resid), 0
         t = ops.linear_fwd(x16, st.w16(name + "weight"), st.p(name + "bias"), epilogue=ops.EPI_RESID_F32)
         sd = drop.next()
-        ops.dropout_f32(t, ph, sd, resid=resid, out_f32=t, row_map=rmap)
+        ops.dropout_f32(t, ph, sd, resid=resid, out_f32=t, row_map=row_map)
         return t, sd
 
-    g = torch.empty(R, I, device=dev, dtype=torch.bfloat16)
-    for i in range(layers):
+    g = torch.empty(R, I, device=dev, dtype=torch.bfloat16) if not (pool_last and layers == 1) else None
+    for i in range(layers - 1 if pool_last else layers):
         b = f"{prefix}encoder.layer.{i}."
         s, c = b + "attention.self.", b + "crossattention.self."
         qkv = ops.linear_fwd(h16, st.w16(s + "query.weight", (3 * W, W)), st.p(s + "query.bias", (3 * W,)))
@@ -274,11 +279,20 @@ def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, poo
             stash["layers"].append(dict(h16=h16, qkv=qkv, ao=ao, lse1=lse1, t1=t1, a16=a16, cq=cq, ckv=ckv, co=co,
                                         lse2=lse2, t2=t2, c16=c16, f=f, t3=t3, seeds=(sa1, so1, sa2, so2, so3)))
         h32, h16 = _ln2(st, t3, b + "output.LayerNorm.", eps, R, W)
-    rows = torch.empty(M, W, device=dev, dtype=torch.float32)
-    if pack is None:
-        ops.call("uniir_gather_rows", h32, None, rows, M, L, W)
+    if pool_last:
+        rows, sv = _bert_last_layer_pooled(st, prefix, cfg, h32, h16, key_len, img16, Ti, M, L, R, cross, drop, ph, pa, pack, out_dense)
+        if save:
+            stash["layers"].append(sv)
+        if log is not None:
+            log.append(f"BERT last layer {layers - 1} on the {M} class rows (pool_last_layer): K | V from {R} "
+                       f"{'packed' if pack is not None else 'dense'} rows, {'self- and cross-' if cross else 'self-'}attention in the "
+                       f"one-query form, {'stash of M-row tensors' if save else 'no stash'}")
     else:
-        ops.call("uniir_gather_rows", h32, roff, rows, M, 0, W)          # the class token = the first row of every item
+        rows = torch.empty(M, W, device=dev, dtype=torch.float32)
+        if pack is None:
+            ops.call("uniir_gather_rows", h32, None, rows, M, L, W)
+        else:
+            ops.call("uniir_gather_rows", h32, roff, rows, M, 0, W)          # the class token = the first row of every item
     if not pool:
         return rows, stash
     rows16 = torch.empty(M, W, device=dev, dtype=torch.bfloat16)
@@ -290,6 +304,142 @@ def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, poo
     if save:
         stash.update(rows16=rows16, pooled=pooled)
     return pooled, stash
+
+
+def _class_rows(pack, M, L, dev):
+    """of the class token of every item: its row in the (dense or packed) row numbering as an index tensor, and the int32 row_map
+    that gives each of these M rows its DENSE row m * L (the coordinates of hidden dropout)"""
+    cmap = torch.arange(M, device=dev, dtype=torch.int32) * L
+    return (cmap.long() if pack is None else pack.row_off[:M].long()), cmap
+
+
+def _bert_last_layer_pooled(st, prefix, cfg, h32, h16, key_len, img16, Ti, M, L, R, cross, drop, ph, pa, pack, out_dense):
+    """The last BERT layer when only the class row of every item leaves the encoder (blip_ff.py:82-116 reads pooler_output,
+    blip_sf.py the class token): what that row needs from the other rows is their KEYS AND VALUES, so the q | k | v projection still
+    runs on all R rows -- the same GEMM as in the full layer, so K | V have its bits, a dense BERT passes row m * L of that buffer as
+    the query without a copy, and the backward's weight-gradient and d h32 products keep their shape -- and everything behind it on
+    the M class rows: the one-query self-attention (ops.onequery_fwd with key_len or the packed rows), attention.output.dense +
+    LayerNorm, the cross query, the one-query cross-attention over the Ti image tokens, its output dense + LayerNorm, the FFN and
+    output.LayerNorm.  The dropout seeds are drawn in the full layer's order; attention dropout sits at the coordinates of query 0 of
+    L (drop_tq = L, drop_q = 0), hidden dropout at the dense rows m * L (row_map).  -> the class rows fp32 [M, W], the layer's stash."""
+    W, I, eps = cfg["hidden_size"], cfg["intermediate_size"], cfg["layer_norm_eps"]
+    heads, i = cfg["num_attention_heads"], cfg["num_hidden_layers"] - 1
+    dev = h32.device
+    b = f"{prefix}encoder.layer.{i}."
+    s, c = b + "attention.self.", b + "crossattention.self."
+    cls, cmap = _class_rows(pack, M, L, dev)
+    qkv = ops.linear_fwd(h16, st.w16(s + "query.weight", (3 * W, W)), st.p(s + "query.bias", (3 * W,)))
+    sa1 = drop.next() if pa else 0
+    if pack is None:
+        q, q_ld, kw = qkv, L * 3 * W, dict(key_len=key_len)
+    else:
+        q, q_ld, kw = qkv[cls, :W], W, dict(kv_row_off=pack.row_off)          # a copy of M rows
+    ao, lse1 = ops.onequery_fwd(q, q_ld, qkv[:, W:], qkv[:, 2 * W:], 3 * W, M, L, heads, drop_p=pa, drop_seed=sa1, drop_tq=L, drop_q=0, **kw)
+    h32c = torch.empty(M, W, device=dev, dtype=torch.float32)
+    ops.call("uniir_gather_rows", h32, None if pack is None else pack.row_off, h32c, M, L if pack is None else 0, W)
+    t1, so1 = out_dense(ao, b + "attention.output.dense.", h32c, cmap)
+    a32, a16 = _ln2(st, t1, b + "attention.output.LayerNorm.", eps, M, W)
+    cq = ckv = co = lse2 = t2 = None
+    sa2 = so2 = 0
+    if cross:
+        cq = ops.linear_fwd(a16, st.w16(c + "query.weight"), st.p(c + "query.bias"))
+        ckv = ops.linear_fwd(img16, st.w16(c + "key.weight", (2 * W, img16.shape[1])), st.p(c + "key.bias", (2 * W,)))
+        sa2 = drop.next() if pa else 0
+        co, lse2 = ops.onequery_fwd(cq, W, ckv, ckv[:, W:], 2 * W, M, Ti, heads, drop_p=pa, drop_seed=sa2, drop_tq=L, drop_q=0)
+        t2, so2 = out_dense(co, b + "crossattention.output.dense.", a32, cmap)
+        c32, c16 = _ln2(st, t2, b + "crossattention.output.LayerNorm.", eps, M, W)
+    else:
+        c32, c16 = a32, a16
+    f = torch.empty(M, I, device=dev, dtype=torch.bfloat16)
+    g = torch.empty(M, I, device=dev, dtype=torch.bfloat16)
+    ops.linear_fwd(c16, st.w16(b + "intermediate.dense.weight"), st.p(b + "intermediate.dense.bias"), out=f,
+                   epilogue=ops.EPI_BIAS_ACT, C2=g, act=ops.ACT_GELU_ERF)
+    t3, so3 = out_dense(g, b + "output.dense.", c32, cmap)
+    rows, _ = _ln2(st, t3, b + "output.LayerNorm.", eps, M, W)
+    sv = dict(pooled=True, h16=h16, qkv=qkv, q=q, q_ld=q_ld, ao=ao, lse1=lse1, t1=t1, a16=a16, cq=cq, ckv=ckv, co=co, lse2=lse2, t2=t2,
+              c16=c16, f=f, t3=t3, seeds=(sa1, so1, sa2, so2, so3))
+    return rows, sv
+
+
+def _bert_last_layer_pooled_backward(st, prefix, cfg, drows, dimg, sv, stash, cross, colsum):
+    """backward of _bert_last_layer_pooled.  drows fp32 [M, W]: the gradient of the class rows.  Everything up to the self-attention
+    runs on M rows; the one-query backward writes dk | dv of EVERY key row (exact zeros behind a dense item's key_len) and dq of the
+    class rows into a zeroed [R, 3W] buffer -- the rows whose query gradient the full layer finds to be zero -- so the q | k | v
+    weight gradient and d h32 = dqkv @ Wqkv + dt1 are the full layer's products; dt1 is scattered into zeroed R rows.
+    -> d h32 fp32 [R, W]"""
+    W, I, eps = cfg["hidden_size"], cfg["intermediate_size"], cfg["layer_norm_eps"]
+    heads, i = cfg["num_attention_heads"], cfg["num_hidden_layers"] - 1
+    M, L, Ti, key_len, img16 = stash["M"], stash["L"], stash["Ti"], stash["key_len"], stash["img16"]
+    pack = stash.get("pack")
+    R, dev = (pack.R if pack is not None else M * L), drows.device
+    G = st.grad_view
+    f32 = dict(device=dev, dtype=torch.float32)
+    b16 = dict(device=dev, dtype=torch.bfloat16)
+    ph, pa = stash["ph"], stash["pa"]
+    b = f"{prefix}encoder.layer.{i}."
+    s, c = b + "attention.self.", b + "crossattention.self."
+    sa1, so1, sa2, so2, so3 = sv["seeds"]
+    cls, cmap = _class_rows(pack, M, L, dev)
+    # ---- feed-forward sublayer
+    d16 = torch.empty(M, W, **b16)
+    dt3 = ops.layernorm_bwd(sv["t3"], st.p(b + "output.LayerNorm.weight"), drows, G(b + "output.LayerNorm.weight"),
+                            G(b + "output.LayerNorm.bias"), eps, dx_bf16=d16, rows=M, width=W)
+    if ph:
+        ops.dropout_bf16_(d16, ph, so3, row_map=cmap)
+    df, g = torch.empty(M, I, **b16), torch.empty(M, I, **b16)
+    ops.linear_dgrad(d16, st.w16(b + "output.dense.weight"), out=df, aux=sv["f"], act_out=g,
+                     colsum=G(b + "intermediate.dense.bias"), act=ops.ACT_GELU_ERF)
+    ops.linear_wgrad(d16, g, G(b + "output.dense.weight"), dbias=G(b + "output.dense.bias"))
+    ops.linear_wgrad(df, sv["c16"], G(b + "intermediate.dense.weight"))
+    dc = torch.empty(M, W, **f32)
+    ops.gemm(df, st.w16(b + "intermediate.dense.weight"), dc, M, W, I, I, W, W, b_tmaj=True, epilogue=ops.EPI_RESID_F32, resid=dt3)
+    if not cross:
+        da = dc
+    else:
+        # ---- cross-attention sublayer
+        dt2 = ops.layernorm_bwd(sv["t2"], st.p(b + "crossattention.output.LayerNorm.weight"), dc,
+                                G(b + "crossattention.output.LayerNorm.weight"), G(b + "crossattention.output.LayerNorm.bias"), eps,
+                                dx_bf16=d16, rows=M, width=W)
+        if ph:
+            ops.dropout_bf16_(d16, ph, so2, row_map=cmap)
+        ops.linear_wgrad(d16, sv["co"], G(b + "crossattention.output.dense.weight"), dbias=G(b + "crossattention.output.dense.bias"))
+        dco = ops.linear_dgrad(d16, st.w16(b + "crossattention.output.dense.weight"))
+        dcq = torch.empty(M, W, **b16)
+        dckv = torch.empty(M * Ti, 2 * W, **b16)
+        ckv = sv["ckv"]
+        ops.onequery_bwd(sv["cq"], W, ckv, ckv[:, W:], 2 * W, sv["co"], dco, sv["lse2"], dcq, W, dckv, dckv[:, W:], 2 * W, M, Ti, heads,
+                         drop_p=pa, drop_seed=sa2, drop_tq=L, drop_q=0)
+        Ew = img16.shape[1]
+        ops.linear_wgrad(dckv, img16, G(c + "key.weight", (2 * W, Ew)), dbias=G(c + "key.bias", (2 * W,)))
+        ops.gemm(dckv, st.w16(c + "key.weight", (2 * W, Ew)), dimg, M * Ti, Ew, 2 * W, 2 * W, Ew, Ew, b_tmaj=True,
+                 epilogue=ops.EPI_RESID_F32, resid=dimg)
+        ops.linear_wgrad(dcq, sv["a16"], G(c + "query.weight"), dbias=G(c + "query.bias"))
+        da = torch.empty(M, W, **f32)
+        ops.gemm(dcq, st.w16(c + "query.weight"), da, M, W, W, W, W, W, b_tmaj=True, epilogue=ops.EPI_RESID_F32, resid=dt2)
+    # ---- self-attention sublayer
+    dt1 = ops.layernorm_bwd(sv["t1"], st.p(b + "attention.output.LayerNorm.weight"), da, G(b + "attention.output.LayerNorm.weight"),
+                            G(b + "attention.output.LayerNorm.bias"), eps, dx_bf16=d16, rows=M, width=W)
+    if ph:
+        ops.dropout_bf16_(d16, ph, so1, row_map=cmap)
+    ops.linear_wgrad(d16, sv["ao"], G(b + "attention.output.dense.weight"), dbias=G(b + "attention.output.dense.bias"))
+    dao = ops.linear_dgrad(d16, st.w16(b + "attention.output.dense.weight"))
+    qkv = sv["qkv"]
+    dqkv = torch.zeros(R, 3 * W, **b16)
+    if pack is None:
+        ops.onequery_bwd(qkv, L * 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, sv["ao"], dao, sv["lse1"], dqkv, L * 3 * W, dqkv[:, W:],
+                         dqkv[:, 2 * W:], 3 * W, M, L, heads, key_len=key_len, drop_p=pa, drop_seed=sa1, drop_tq=L, drop_q=0)
+    else:
+        dq = torch.empty(M, W, **b16)
+        ops.onequery_bwd(sv["q"], W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, sv["ao"], dao, sv["lse1"], dq, W, dqkv[:, W:], dqkv[:, 2 * W:],
+                         3 * W, M, L, heads, kv_row_off=pack.row_off, drop_p=pa, drop_seed=sa1, drop_tq=L, drop_q=0)
+        dqkv[cls, :W] = dq          # a copy of M rows
+    ops.linear_wgrad(dqkv, sv["h16"], G(s + "query.weight", (3 * W, W)), dbias=G(s + "query.bias", (3 * W,)))
+    dt1r = torch.zeros(R, W, **f32)
+    ops.call("uniir_scatter_rows", dt1, None if pack is None else pack.row_off, dt1r, M, L if pack is None else 0, W)
+    do = torch.empty(R, W, **f32)
+    ops.gemm(dqkv, st.w16(s + "query.weight", (3 * W, W)), do, R, W, 3 * W, 3 * W, W, W, b_tmaj=True, epilogue=ops.EPI_RESID_F32,
+             resid=dt1r)
+    return do
 
 
 def bert_backward(st, prefix, cfg, dpooled, stash, cross=True, pool=True):
@@ -311,13 +461,16 @@ def bert_backward(st, prefix, cfg, dpooled, stash, cross=True, pool=True):
         drows = dpooled.contiguous().float()
     else:
         drows = _pooler_backward(st, prefix, dpooled, stash, M, W, colsum)
-    do = torch.zeros(R, W, **f32)
-    if pack is None:
-        ops.call("uniir_scatter_rows", drows, None, do, M, L, W)
+    if stash["layers"][-1].get("pooled"):
+        do = drows          # the last layer ran on the class rows: the scatter to R rows happens below it (_bert_layers_backward)
     else:
-        ops.call("uniir_scatter_rows", drows, pack.row_off, do, M, 0, W)
+        do = torch.zeros(R, W, **f32)
+        if pack is None:
+            ops.call("uniir_scatter_rows", drows, None, do, M, L, W)
+        else:
+            ops.call("uniir_scatter_rows", drows, pack.row_off, do, M, 0, W)
     dimg = torch.zeros(M * Ti, img16.shape[1], **f32) if cross else None
-    g = torch.empty(R, I, **b16)
+    g = torch.empty(R, I, **b16) if not (layers == 1 and stash["layers"][-1].get("pooled")) else None
     return _bert_layers_backward(st, prefix, cfg, do, dimg, g, stash, cross, colsum)
 
 
@@ -357,6 +510,9 @@ def _bert_layers_backward(st, prefix, cfg, do, dimg, g, stash, cross, colsum):
         s, c = b + "attention.self.", b + "crossattention.self."
         sv = stash["layers"][i]
         stash["layers"][i] = None
+        if sv.get("pooled"):          # the last layer on the class rows: do is [M, W] coming in, [R, W] going out
+            do = _bert_last_layer_pooled_backward(st, prefix, cfg, do, dimg, sv, stash, cross, colsum)
+            continue
         sa1, so1, sa2, so2, so3 = sv["seeds"]
         # ---- feed-forward sublayer: o = LN(g @ Wout^T + bout + c32), g = gelu(c16 @ Wi^T + bi)
         d16 = torch.empty(R, W, **b16)
@@ -438,7 +594,8 @@ class _EncodeFn(torch.autograd.Function):
         drop = model._drop_seeds()
         tok, Ti, vst = vit_forward(st, model._conv16, "visual_encoder.", model.vit_cfg, model.image_size, images, save,
                                    drop=drop, recompute_from=model._vit_boundary(save))
-        pooled, bst = bert_forward(st, "text_encoder.", model.med_cfg, ids, key_len, tok, Ti, save, drop=drop, pack=pack)
+        pooled, bst = bert_forward(st, "text_encoder.", model.med_cfg, ids, key_len, tok, Ti, save, drop=drop, pack=pack,
+                                   pool_last=model.pool_last_layer, log=model._path_log())
         ctx.model, ctx.vst, ctx.bst = model, vst, bst
         return pooled
 
@@ -618,6 +775,19 @@ class BLIPFeatureFusion(nn.Module):
         # changed between steps (A/B runs); must be the same on every rank.
         self.vit_recompute_from = vit_recompute_from(self.vit_cfg["depth"], vit_grad_ckpt, vit_ckpt_layer)
         self._vit_recompute_logged = False
+        # Only the class row of every caption leaves the BERT (pooler_output / the class token), so its LAST layer needs the other
+        # rows' keys and values only: with this on, that layer runs its attention in the one-query form and everything behind the
+        # q | k | v projection on the M class rows (_bert_last_layer_pooled) -- online, momentum and no-grad passes, BLIP_SF too.
+        # Embeddings, train-mode outputs and the loss are bitwise those of the full layer; weight gradients are the same sums over
+        # fewer rows.  Off by default (profiles/blip_pooled_last_layer.txt has the measurement): UNIIR_BLIP_POOL_LAST_LAYER=1
+        # switches it on at construction.  A plain attribute: may be changed between steps; must be the same on every rank.
+        self.pool_last_layer = os.environ.get("UNIIR_BLIP_POOL_LAST_LAYER", "0") not in ("", "0")
+        self.path_log = []                # one line per BERT pass whose last layer ran on the class rows (the newest 64)
+
+    def _path_log(self):
+        """the list bert_forward reports to when pool_last_layer is on (trimmed here: it grows by one line per encoder pass)"""
+        del self.path_log[:-63]
+        return self.path_log
 
     def _vit_boundary(self, save):
         """recompute_from of a ViT forward of the online encoder; the first training forward that recomputes says so once"""
@@ -773,7 +943,7 @@ class BLIPFeatureFusion(nn.Module):
                 tok, Ti, _ = vit_forward(self._mom, self._conv16_m, "visual_encoder.", self.vit_cfg, self.image_size,
                                          image_batched, False, drop=drop)
                 return bert_forward(self._mom, "text_encoder.", self.med_cfg, ids, key_len, tok, Ti, False, drop=drop,
-                                    pack=pack)[0]
+                                    pack=pack, pool_last=self.pool_last_layer, log=self._path_log())[0]
         anchor = torch.zeros(1, device=ids.device, requires_grad=torch.is_grad_enabled())
         return _EncodeFn.apply(self, ids, key_len, image_batched, anchor, pack)
 
@@ -901,7 +1071,7 @@ class BLIPScoreFusion(BLIPFeatureFusion):
                                   recompute_from=self._vit_boundary(save))
         ifeat16 = tok.view(M, T, -1)[:, 0].contiguous()                     # class-token rows (a copy)
         tfeat, bst = bert_forward(st, "text_encoder.", self.med_cfg, ids, key_len, None, 0, save, cross=False, pool=False,
-                                  drop=drop, pack=pack)
+                                  drop=drop, pack=pack, pool_last=self.pool_last_layer, log=self._path_log())
         tfeat16 = torch.empty(M, tfeat.shape[1], device=dev, dtype=torch.bfloat16)
         ops.call("uniir_cast_f32_to_bf16", tfeat, tfeat16, tfeat.numel())
         temb = ops.linear_fwd(tfeat16, st.w16("text_proj.weight"), st.p("text_proj.bias"), epilogue=ops.EPI_RESID_F32)

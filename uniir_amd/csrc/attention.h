@@ -205,6 +205,9 @@ struct AttnArgs {
     const int* kv_row_off;        // optional [batch + 1]: the KEY / VALUE side alone is packed (item m = rows kv_row_off[m] ..): the
                                   // pooled-row attention of a packed text tower's last block (tower.hip): one dense query row per item
     int klen_add;                 // added to klen[m] (the EOT index + 1 = the key count of a pooled causal query)
+    // the query part of the dropout coordinate ((m H + h) drop_tq + drop_q0 + q) Tk + key: the builders set Tq and 0 (the call's own
+    // rows); a one-query call that stands for row drop_q0 of a call with drop_tq queries sets those (uniir_onequery_fwd / _bwd)
+    int drop_tq, drop_q0;
 #ifdef UNIIR_EXP_BUILD
     unsigned long long* stamps;   // timing build: [64 workgroups][8 waves][8] s_memtime stamps
     int exp;                      // knock-out bits: 1 phase 1 / compute, 2 phase 2, 4 stage A, 8 stage B, 16 stores
@@ -238,6 +241,8 @@ int launch_attn_long_fwd(const AttnArgs& a, int batch, hipStream_t st, bool f16)
 int launch_attn_long_bwd(const AttnArgs& a, int batch, hipStream_t st);
 // attention_one.hip: the backward of ONE dense query row per (item, head) against 1 .. ATT_LONG_SEQ_MAX dense keys in one pass over K and V
 int launch_attn_one_bwd(const AttnArgs& a, int batch, hipStream_t st);
+// attention_long.hip: the streaming forward of the general form (attn_xlong_fwd_kernel) for uniir_onequery_fwd above ATT_SEQ_MAX keys
+int launch_attn_xlong_fwd(const AttnArgs& a, int batch, hipStream_t st);
 
 // what tower.hip calls (attention.hip).  The forward: row_off = nullptr for dense rows; f16 = the 16-bit tensors are fp16
 int attention_fwd_impl(const void* qkv, void* out, float* lse, const int32_t* row_off, int32_t batch, int32_t seq, int32_t heads,
@@ -274,6 +279,7 @@ inline AttnArgs att_args_packed(const void* qkv, const void* out, const float* l
     a.q_ld = a.kv_ld = 3 * W;
     a.out = (unsigned short*)const_cast<void*>(out); a.out_ld = W; a.lse = const_cast<float*>(lse);
     a.Tq = a.Tk = seq; a.H = heads; a.causal = causal; a.scale = scale; a.row_off = row_off;
+    a.drop_tq = seq;
     return a;
 }
 inline void att_args_packed_bwd(AttnArgs& a, const void* dout, void* dqkv) {
@@ -293,6 +299,7 @@ inline AttnArgs att_args_qkv(const void* q, long q_ld, const void* k, const void
     a.q_ld = q_ld; a.kv_ld = kv_ld;
     a.out = (unsigned short*)const_cast<void*>(out); a.out_ld = out_ld; a.lse = const_cast<float*>(lse); a.klen = key_len;
     a.Tq = tq; a.Tk = tk; a.H = heads; a.causal = causal; a.scale = ATT_SCALE;
+    a.drop_tq = tq;
     return a;
 }
 inline void att_args_qkv_bwd(AttnArgs& a, const void* dout, void* dq, long dq_ld, void* dk, void* dv, long dkv_ld) {
@@ -303,6 +310,7 @@ inline void att_args_qkv_bwd(AttnArgs& a, const void* dout, void* dq, long dq_ld
 inline void att_args_q_rows(AttnArgs& a, const int* q_row_off, int q_only) { a.row_off = q_row_off; a.row_off_q_only = q_only; }
 inline void att_args_kv_rows(AttnArgs& a, const int* kv_row_off, int klen_add) { a.kv_row_off = kv_row_off; a.klen_add = klen_add; }
 inline void att_args_drop(AttnArgs& a, float drop_p, unsigned drop_seed) { a.drop_p = drop_p; a.drop_seed = drop_seed; }
+inline void att_args_drop_at(AttnArgs& a, int drop_tq, int drop_q) { a.drop_tq = drop_tq; a.drop_q0 = drop_q; }
 
 // One launch of kernel K.  A kernel with dynamic LDS (max_lds > 0) gets its limit raised to max_lds before its first launch on a
 // device: every kernel, i.e. every instantiation of this template, has its own once-per-device flag.

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(AttnArgs a) {
                 l4 = l4 + st[kt];
             }
             if (DROP) {
-                const unsigned rowbase = (unsigned)((((long)m * H + h) * a.Tq + q) * a.Tk);      // dense coordinates: packed rows draw the dense call's mask
+                const unsigned rowbase = (unsigned)((((long)m * H + h) * a.drop_tq + a.drop_q0 + q) * a.Tk);      // dense coordinates: packed rows draw the dense call's mask
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : 3) void attn_bwd_kernel(AttnArg
     const unsigned dth = DROP ? drop_threshold(a.drop_p) : 0u;
     const float dks = DROP ? 1.0f / (1.0f - a.drop_p) : 1.0f;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar loop control
-    const unsigned headbase = (unsigned)((((long)m * H + h) * a.Tq) * a.Tk);      // dense coordinates (see attn_fwd_kernel)
+    const unsigned headbase = (unsigned)((((long)m * H + h) * a.drop_tq + a.drop_q0) * a.Tk);      // dense coordinates (see attn_fwd_kernel)
     const unsigned short* qbase = a.q + qr0 * a.q_ld + h * ATT_D;
     const unsigned short* kbase = a.k + kr0 * a.kv_ld + h * ATT_D;
     const unsigned short* vbase = a.v + kr0 * a.kv_ld + h * ATT_D;
@@ -644,6 +644,28 @@ extern "C" int uniir_attention_one_fwd(const void* q, const void* k, const void*
     if (tk < 1 || tk > ATT_LONG_SEQ_MAX) return UNIIR_ESHAPE;
     if (att_ld_not8(kv_ld)) return UNIIR_EALIGN;          // (the pooled form below would answer UNIIR_ESHAPE)
     return attention_pooled_fwd_impl(q, k, v, kv_ld, out, lse, nullptr, 0, nullptr, batch, tk, heads, f16 != 0, stream);
+}
+
+// One query row per item that STANDS FOR row drop_q of a call with drop_tq query rows (include/uniir_hip.h): key counts (key_len) or
+// packed keys (kv_row_off), and dropout drawn at that call's coordinates.  The kernel bodies of the full call at Tq = 1: up to
+// ATT_SEQ_MAX keys attn_fwd_kernel (what uniir_attention_fwd_ex / _fwd_rows launch), above it attn_xlong_fwd_kernel (what
+// uniir_attention_fwd_long launches) -- so out and lse are that row of the full call, bit for bit.  The backward (uniir_onequery_bwd)
+// is the one-pass kernel of attention_one.hip.  The checks follow the _long entry points: drop_p (a NaN included) before batch == 0.
+extern "C" int uniir_onequery_fwd(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, void* out, int64_t out_ld,
+                                  float* lse, const int32_t* key_len, const int32_t* kv_row_off, int32_t batch, int32_t tk,
+                                  int32_t heads, float drop_p, uint32_t drop_seed, int32_t drop_tq, int32_t drop_q, void* stream) {
+    if (att_null(q, k, v, out, lse) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (att_bad_drop_nan(drop_p) || drop_tq < 1 || drop_q < 0 || drop_q >= drop_tq || (key_len && kv_row_off)) return UNIIR_EINVAL;
+    if (batch == 0) return UNIIR_OK;
+    if (tk < 1 || tk > ATT_LONG_SEQ_MAX) return UNIIR_ESHAPE;
+    if (att_ld_not8(q_ld, kv_ld, out_ld)) return UNIIR_EALIGN;
+    if (att_misaligned16(q, k, v, out)) return UNIIR_EALIGN;
+    AttnArgs a = att_args_qkv(q, q_ld, k, v, kv_ld, out, out_ld, lse, 1, tk, heads, key_len);
+    att_args_kv_rows(a, kv_row_off, 0);
+    att_args_drop(a, drop_p, drop_seed);
+    att_args_drop_at(a, drop_tq, drop_q);
+    if (tk > ATT_SEQ_MAX) return launch_attn_xlong_fwd(a, batch, (hipStream_t)stream);
+    return launch_attn_fwd(a, batch, (hipStream_t)stream);
 }
 
 // ---------------- separate Q and K | V, up to ATT_SEQ_MAX x ATT_SEQ_MAX (attention_long.hip has the _long forms) ----------------

@@ -114,10 +114,15 @@ DEVINL void al_fwd_body(const AttnArgs& a, int nqb) {
     int Tq, Tk;          // Tk: the keys of the sweep (XL: the item's valid keys; the masked ones are never staged)
     al_item<XL>(a, m, qr0, Tq, Tk);
     if (XL && qb * AL_ROWS >= Tq) return;      // a packed item shorter than the call's tq (the whole workgroup leaves)
+    long kr0 = (long)m * a.Tk;
+    if (XL && a.kv_row_off) {      // the forward alone (uniir_onequery_fwd): the item's keys are its own packed rows, its length the key count
+        kr0 = a.kv_row_off[m];
+        Tk = min(Tk, a.kv_row_off[m + 1] - a.kv_row_off[m]);
+    }
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned short* qbase = a.q + qr0 * a.q_ld + h * ATT_D;
-    const unsigned short* kbase = a.k + (long)m * a.Tk * a.kv_ld + h * ATT_D;
-    const unsigned short* vbase = a.v + (long)m * a.Tk * a.kv_ld + h * ATT_D;
+    const unsigned short* kbase = a.k + kr0 * a.kv_ld + h * ATT_D;
+    const unsigned short* vbase = a.v + kr0 * a.kv_ld + h * ATT_D;
     const unsigned dth = DROP ? drop_threshold(a.drop_p) : 0u;
     const float dks = DROP ? 1.0f / (1.0f - a.drop_p) : 1.0f;
     const int qi = lane & 15, g = lane >> 4;
@@ -203,7 +208,7 @@ DEVINL void al_fwd_body(const AttnArgs& a, int nqb) {
                     l4 = l4 + st[kt];
                 }
                 if (DROP) {      // acc[r] = S[key = 4g + r][q = qi]; dense coordinates: packed rows draw the dense call's mask
-                    const unsigned rowbase = (unsigned)((((long)m * H + h) * a.Tq + q) * a.Tk);
+                    const unsigned rowbase = (unsigned)((((long)m * H + h) * a.drop_tq + a.drop_q0 + q) * a.Tk);
 #pragma unroll
                     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -304,7 +309,7 @@ DEVINL void al_dkdv_body(const AttnArgs& a, int nkblk) {
     const float* lsebase = a.lse + ((long)m * H + h) * a.Tq;
     const unsigned dth = DROP ? drop_threshold(a.drop_p) : 0u;
     const float dks = DROP ? 1.0f / (1.0f - a.drop_p) : 1.0f;
-    const unsigned headbase = (unsigned)((((long)m * H + h) * a.Tq) * a.Tk);      // dense coordinates (see the forward)
+    const unsigned headbase = (unsigned)((((long)m * H + h) * a.drop_tq + a.drop_q0) * a.Tk);      // dense coordinates (see the forward)
     const int li = lane & 15, g = lane >> 4;
     const int k0 = kblk * AL_ROWS + w * 16, key = k0 + li;
     const float sl2 = REL ? a.scale * LOG2EF : SCALE_LOG2E;
@@ -566,7 +571,7 @@ DEVINL void al_dq_body(const AttnArgs& a, int nqb) {
                             if (k0 + kb * 32 + kt * 16 + 4 * g + r >= Tk) dst[kt][r] = 0.f;
                     }
                     if (DROP) {
-                        const unsigned rowbase = (unsigned)((((long)m * H + h) * a.Tq + q) * a.Tk);
+                        const unsigned rowbase = (unsigned)((((long)m * H + h) * a.drop_tq + a.drop_q0 + q) * a.Tk);
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
                             dp[r] *= drop_scale(rowbase + (unsigned)(k0 + kb * 32 + kt * 16 + 4 * g + r), a.drop_seed, dth, dks);
@@ -676,6 +681,14 @@ int launch_attn_long_fwd(const AttnArgs& a, int batch, hipStream_t st, bool f16)
 }
 int launch_attn_long_bwd(const AttnArgs& a, int batch, hipStream_t st) {
     return attn_long_plain(a) ? al_launch_bwd(AL_PLAIN, a, batch, st) : UNIIR_ESHAPE;
+}
+// the general form's forward for another file (uniir_onequery_fwd, attention.hip): what uniir_attention_fwd_long launches, and
+// the one caller that may pass kv_row_off
+int launch_attn_xlong_fwd(const AttnArgs& a, int batch, hipStream_t st) {
+    if (a.causal || a.rel_emb || a.scale != ATT_SCALE || a.Tq < 1 || a.Tk < 1 || a.Tq > ATT_LONG_SEQ_MAX || a.Tk > ATT_LONG_SEQ_MAX ||
+        (a.kv_row_off && (a.row_off || a.klen)))
+        return UNIIR_ESHAPE;
+    return al_launch_fwd(AL_XL, a, batch, st);
 }
 
 // ---------------- the general form (uniir_attention_fwd_long / _bwd_long) ----------------

@@ -288,6 +288,27 @@ def attention_one_bwd(q, k, v, kv_ld, out, dout, lse, dq, dq_ld, dk, dv, dkv_ld,
                                               dkv_ld, batch, tk, heads, _stream()), "attention_one_bwd")
 
 
+def onequery_fwd(q, q_ld, k, v, kv_ld, batch, tk, heads, *, key_len=None, kv_row_off=None, drop_p=0.0, drop_seed=0, drop_tq=1, drop_q=0):
+    """ONE query row per item (row m of q at m * q_ld, bf16) that stands for row drop_q of attention_fwd_ex with tq = drop_tq: dense
+    keys [batch*tk] with an optional key_len, or packed keys (kv_row_off int32 [batch + 1]); dropout at the full call's coordinates
+    (uniir_onequery_fwd).  Returns out [batch, heads*64] and lse [batch, heads]: bitwise that row of the full call."""
+    out = torch.empty(batch, heads * 64, device=q.device, dtype=torch.bfloat16)
+    lse = torch.empty(batch, heads, device=q.device, dtype=torch.float32)
+    check(_lib.load().uniir_onequery_fwd(_p(q), q_ld, _p(k), _p(v), kv_ld, _p(out), heads * 64, _p(lse), _p(key_len), _p(kv_row_off),
+                                         batch, tk, heads, float(drop_p), int(drop_seed), int(drop_tq), int(drop_q), _stream()),
+          "onequery_fwd")
+    return out, lse
+
+
+def onequery_bwd(q, q_ld, k, v, kv_ld, out, dout, lse, dq, dq_ld, dk, dv, dkv_ld, batch, tk, heads, *, key_len=None, kv_row_off=None,
+                 drop_p=0.0, drop_seed=0, drop_tq=1, drop_q=0):
+    """d loss / d q, k, v of onequery_fwd (out / dout dense [batch, heads*64]) into dq ([batch] rows, dq_ld) and dk / dv (the key rows,
+    dkv_ld; dense keys behind key_len get exact zeros): the one-pass kernel, bitwise reproducible (uniir_onequery_bwd)."""
+    check(_lib.load().uniir_onequery_bwd(_p(q), q_ld, _p(k), _p(v), kv_ld, _p(out), _p(dout), heads * 64, _p(lse), _p(key_len),
+                                         _p(kv_row_off), _p(dq), dq_ld, _p(dk), _p(dv), dkv_ld, batch, tk, heads, float(drop_p),
+                                         int(drop_seed), int(drop_tq), int(drop_q), _stream()), "onequery_bwd")
+
+
 # The most tokens whose keys the resident kernels hold in LDS: csrc/attention.h ATT_SEQ_MAX.  Above it the streaming entry points
 # (`_long`, csrc/attention_long.hip) run, up to ATT_LONG_SEQ_MAX = 1024; the library refuses what neither takes.
 ATT_RESIDENT_MAX = 512
