@@ -85,3 +85,13 @@ def clip_preprocess(img_u8, n_px, mean, std):
     lib().oracle_crop_normalize(r.ctypes.data_as(C.c_void_p), oh, ow, top, left, n_px, m.ctypes.data_as(C.c_void_p),
                                 s.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
     return out
+
+
+def inv_norms(x_f16):
+    """fp16 [n][dim] (float16, or its uint16 bit patterns) -> fp32 [n]: 1 / ||row|| in the pinned order, 0 for an all-zero row"""
+    x = np.ascontiguousarray(x_f16)
+    x = x.view(np.uint16) if x.dtype == np.float16 else np.ascontiguousarray(x, dtype=np.uint16)
+    n, dim = x.shape
+    out = np.empty(n, dtype=np.float32)
+    lib().oracle_inv_norms(x.ctypes.data_as(C.c_void_p), C.c_int64(n), dim, out.ctypes.data_as(C.c_void_p))
+    return out

@@ -173,7 +173,7 @@ DEVINL float act_fwd(float x, int act) {
         float E;
         return x * gelu_cdf(x, E);
     }
-    return fmaxf(x, 0.0f);
+    return x != x ? x : fmaxf(x, 0.0f);          // fmaxf alone returns its other operand for a NaN: the NaN has to reach the output
 }
 DEVINL float act_bwd(float x, int act) {
 #pragma clang fp contract(off)
