@@ -773,6 +773,72 @@ int uniir_image_preprocess_batch(const void* packed_u8, const uniir_image_desc* 
                                  const uniir_image_batch_info* info, const float* mean3, const float* std3, float* out,
                                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Train-time augmentation on the device: the ten ops of BLIP's RandomAugment(2, 5) (upstream backbone/transform/randaugment.py,
+ * blip_transform.py:11-40) on RGB uint8 images [n][n][3], between the flip and ToTensor.  The DRAW stays on the host
+ * (uniir_amd/randaugment.py: the reference's np.random calls); the device gets one uniir_image_aug record per image: up to
+ * UNIIR_AUG_MAX_SLOTS ops applied in order, each an op code and the parameters the host prepared for it.
+ *   table ops, per channel, a 256-entry table from the channel's histogram (lo / hi = smallest / largest value present):
+ *     AUTOCONTRAST      fp64, no fused multiply-add: scale = 255 / (hi - lo), off = ((256 - lo) % 256) * scale (the reference negates
+ *                       a uint8: only lo == 0 stretches as intended), t[i] = trunc(clip(i * scale + off, 0, 255)); hi <= lo: unchanged
+ *     AUTOCONTRAST_PIL  the same with off = -lo * scale (PIL.ImageOps.autocontrast); never drawn unless the caller asks
+ *     EQUALIZE          integers: step = (pixels outside the last nonzero bin) / 255; t[i] = min((step / 2 + sum of the bins
+ *                       below i) / step, 255); step == 0: unchanged
+ *     BRIGHTNESS        t[i] = trunc(clip(float(i) * float(factor), 0, 255)), no histogram
+ *   SHARPNESS           factor 1: the input.  Else d = the 3x3 filter (1 1 1 / 1 5 1 / 1 1 1) / 13 in fp32 (taps added in row-major
+ *                       order, reflect-101 border, half-even, saturated); factor 0: d; else the interior [1, n-1) becomes
+ *                       int32(trunc(d + float(factor) * (x - d))) & 255, the border rows and columns keep the input
+ *   SHEAR_X / SHEAR_Y / TRANSLATE_X / TRANSLATE_Y / ROTATE: the forward matrix ([[1, f, 0], [0, 1, 0]], [[1, 0, 0], [f, 1, 0]],
+ *                       [[1, 0, -o], [0, 1, 0]], [[1, 0, 0], [0, 1, -o]] with f, o rounded to fp32; rotation by the angle in degrees
+ *                       about (n / 2, n / 2): [[a, b, (1 - a) cx - b cy], [-b, a, b cx + (1 - a) cy]], a = cos, b = sin) is inverted
+ *                       in fp64 by uniir_image_aug_plan; for destination (x, y):
+ *                         X = (rint((m01 * y + m02) * 1024) + 16 + rint(m00 * x * 1024)) >> 5, Y likewise with m11, m12, m10;
+ *                       source cell (X >> 5, Y >> 5), fractions (X & 31, Y & 31) / 32, four weights (32 - fy)(32 - fx) * 32 ... of sum
+ *                       32768, result (sum p * w + 16384) >> 15; a source pixel outside the image counts as 128.
+ * (DESIGN.md section 3 has the definition in full; tests/randaugment_ref.py restates it in numpy.)
+ *
+ * uniir_image_aug_plan is HOST-ONLY (no HIP call): ops / args are [count][slots] (arg = the enhance factor, the shear factor, the
+ * translate offset in pixels, the angle in degrees; ignored by the other ops); it fills table[count] and the summary.  Errors:
+ * null pointer, count < 0, n <= 0, slots outside [0, UNIIR_AUG_MAX_SLOTS], an unknown op code, a non-finite argument ->
+ * UNIIR_EINVAL; n above 2048 or an argument above 1e6 in magnitude -> UNIIR_EUNSUPPORTED.  info->launches is 2 * slots for any
+ * count >= 1 (per slot: one statistics launch -- histograms in LDS, one workgroup per image whose op needs them -- and one
+ * apply launch over all pixels), info->launches_preprocess = 3 + 2 * slots + 1.
+ *
+ * uniir_image_augment_batch: the op kernels alone.  in_u8 / out_u8 are DEVICE uint8 [count][n][n][3] (different buffers), table the
+ * DEVICE copy, info the HOST summary; workspace >= info->workspace_bytes, 256-byte aligned.  Allocates nothing, never
+ * synchronises.  slots == 0 copies.
+ *
+ * uniir_image_preprocess_batch_aug: uniir_image_preprocess_batch with the table between the flip and ToTensor: resize to uint8, the
+ * slots, then x / 255 -> (v - mean) / std -> out[out_index].  aug[i] belongs to descs[i].  workspace >= info->workspace_bytes +
+ * aug_info->workspace_bytes.  With an all-Identity table the output equals uniir_image_preprocess_batch's bit for bit. */
+#define UNIIR_AUG_MAX_SLOTS 4
+enum {
+    UNIIR_AUG_IDENTITY = 0, UNIIR_AUG_AUTOCONTRAST = 1, UNIIR_AUG_EQUALIZE = 2, UNIIR_AUG_BRIGHTNESS = 3, UNIIR_AUG_SHARPNESS = 4,
+    UNIIR_AUG_SHEAR_X = 5, UNIIR_AUG_SHEAR_Y = 6, UNIIR_AUG_TRANSLATE_X = 7, UNIIR_AUG_TRANSLATE_Y = 8, UNIIR_AUG_ROTATE = 9,
+    UNIIR_AUG_AUTOCONTRAST_PIL = 10, UNIIR_AUG_OPS = 11
+};
+typedef struct uniir_image_aug_slot {
+    int32_t op, reserved;
+    double p[6];                /* warps: the inverse matrix m00 m01 m02 m10 m11 m12; enhance ops: p[0] = factor */
+} uniir_image_aug_slot;
+typedef struct uniir_image_aug {
+    uniir_image_aug_slot slot[UNIIR_AUG_MAX_SLOTS];
+} uniir_image_aug;
+typedef struct uniir_image_aug_info {
+    int64_t workspace_bytes;    /* two uint8 [count][n][n][3] buffers + the tables, 256-byte aligned */
+    int32_t count, n, slots;
+    int32_t launches;           /* of uniir_image_augment_batch: the same for every count >= 1 */
+    int32_t launches_preprocess;    /* of uniir_image_preprocess_batch_aug */
+    int32_t reserved;
+} uniir_image_aug_info;
+int uniir_image_aug_plan(const int32_t* ops, const double* args, int32_t count, int32_t slots, int32_t n, uniir_image_aug* table,
+                         uniir_image_aug_info* info);
+int uniir_image_augment_batch(const void* in_u8, const uniir_image_aug* table, const uniir_image_aug_info* info, void* out_u8,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int uniir_image_preprocess_batch_aug(const void* packed_u8, const uniir_image_desc* descs, const uniir_image_plan* plans,
+                                     const uniir_image_batch_info* info, const uniir_image_aug* aug,
+                                     const uniir_image_aug_info* aug_info, const float* mean3, const float* std3, float* out,
+                                     void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

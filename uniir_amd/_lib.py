@@ -70,6 +70,22 @@ class ImageBatchInfo(C.Structure):
                 ("launches", c_int), ("reserved", c_int)]
 
 
+class ImageAugSlot(C.Structure):
+    """uniir_image_aug_slot: one op of one image -- its code and the parameters the plan prepared (warps: the fp64 inverse matrix)"""
+    _fields_ = [("op", c_int), ("reserved", c_int), ("p", C.c_double * 6)]
+
+
+class ImageAug(C.Structure):
+    """uniir_image_aug: the ops of one image, applied in order"""
+    _fields_ = [("slot", ImageAugSlot * 4)]
+
+
+class ImageAugInfo(C.Structure):
+    """uniir_image_aug_info: uniir_image_aug_plan's summary of one batch (host side)"""
+    _fields_ = [("workspace_bytes", c_i64), ("count", c_int), ("n", c_int), ("slots", c_int), ("launches", c_int),
+                ("launches_preprocess", c_int), ("reserved", c_int)]
+
+
 # name -> (restype, argtypes); P = device pointer, S = stream
 P, S = c_void_p, c_void_p
 SIGNATURES = {
@@ -167,6 +183,11 @@ SIGNATURES = {
     "uniir_image_batch_plan": (c_int, [C.POINTER(ImageDesc), c_int, c_int, c_int, c_i64, C.POINTER(ImagePlan),
                                        C.POINTER(ImageBatchInfo)]),
     "uniir_image_preprocess_batch": (c_int, [P, P, P, C.POINTER(ImageBatchInfo), P, P, P, P, c_i64, S]),
+    "uniir_image_aug_plan": (c_int, [C.POINTER(c_int), C.POINTER(C.c_double), c_int, c_int, c_int, C.POINTER(ImageAug),
+                                     C.POINTER(ImageAugInfo)]),
+    "uniir_image_augment_batch": (c_int, [P, P, C.POINTER(ImageAugInfo), P, P, c_i64, S]),
+    "uniir_image_preprocess_batch_aug": (c_int, [P, P, P, C.POINTER(ImageBatchInfo), P, C.POINTER(ImageAugInfo), P, P, P, P, c_i64,
+                                                 S]),
     "uniir_topk_coarse": (c_int, [P, P, c_i64, c_int, P, c_int, c_int, P, P, P, c_i64, S]),
     "uniir_topk_rescore": (c_int, [P, P, P, c_i64, c_int, P, P, c_int, P, c_int, c_int, P, P, P, S]),
     "uniir_topk_merge": (c_int, [P, P, c_int, c_int, c_int, P, P, S]),

@@ -7,9 +7,8 @@ backbone/transform/blip_transform.py:9-49 that blip_ff.py imports).
     local_files_only, pointing at $UNIIR_BERT_VOCAB_DIR when set; without the files it raises (tokenizer parity is
     unpinned offline; feed token ids + attention masks);
   * get_blip_transform(): PIL + torch restatement of the eval transform (bicubic resize to a square, CLIP mean/std) and
-    of the train transform's geometric part (RandomResizedCrop scale (min_scale, 1), bicubic; horizontal flip).
-    RandomAugment (backbone/transform/randaugment.py) is a CPU data-augmentation policy outside the hot path and is not
-    carried; plug the reference's transform into the collator to get it;
+    of the train transform (RandomResizedCrop scale (min_scale, 1), bicubic; horizontal flip; with randaugment=(N, M) the
+    reference's RandomAugment(N, M) between the flip and ToTensor: uniir_amd/randaugment.py -- off unless asked for);
   * interpolate_pos_embed() / load_checkpoint(): checkpoint loading with the bicubic position-embedding resize.
 """
 import math
@@ -18,6 +17,8 @@ import random
 
 import numpy as np
 import torch
+
+from .randaugment import RandAugmentDraw, apply_ops  # noqa: F401  (RandAugmentDraw is part of this module's surface)
 
 _MEAN = (0.48145466, 0.4578275, 0.40821073)
 _STD = (0.26862954, 0.26130258, 0.27577711)
@@ -42,8 +43,17 @@ def _to_tensor_normalized(image):
     return (a - torch.tensor(_MEAN).view(3, 1, 1)) / torch.tensor(_STD).view(3, 1, 1)
 
 
-def get_blip_transform(image_size, min_scale=0.5, is_train=True):
+def _randaugment_draw(randaugment):
+    """None | (N, M) | a RandAugmentDraw -> None | RandAugmentDraw"""
+    if randaugment is None or isinstance(randaugment, RandAugmentDraw):
+        return randaugment
+    N, M = randaugment
+    return RandAugmentDraw(N, M)
+
+
+def get_blip_transform(image_size, min_scale=0.5, is_train=True, randaugment=None):
     from PIL import Image
+    aug = _randaugment_draw(randaugment)
 
     def eval_fn(image):
         return _to_tensor_normalized(image.resize((image_size, image_size), Image.BICUBIC))
@@ -68,6 +78,8 @@ def get_blip_transform(image_size, min_scale=0.5, is_train=True):
         image = image.crop(box).resize((image_size, image_size), Image.BICUBIC)
         if random.random() < 0.5:
             image = image.transpose(Image.FLIP_LEFT_RIGHT)
+        if aug is not None:     # RandomAugment(N, M, isPIL=True): drawn from np.random, applied to the uint8 array
+            image = Image.fromarray(apply_ops(np.array(image.convert("RGB")), aug.draw()), "RGB")
         return _to_tensor_normalized(image)
 
     return train_fn if is_train else eval_fn
@@ -78,13 +90,15 @@ class RawBlipTransform:
     uniir_image_preprocess_batch): the worker only decodes to uint8 and, in train mode, draws the RandomResizedCrop box and
     the flip from `random` with exactly the calls, order and count of train_fn above (the fallback box after ten failed tries
     included), so the same `random` state going in gives the same tensor, bit for bit, and the same state afterwards.  Eval
-    mode draws nothing and uses the whole image."""
+    mode draws nothing and uses the whole image.  With randaugment=(N, M) the train-mode worker also draws the RandomAugment ops
+    (np.random, after the box and the flip) and carries them on the RawImage; the device applies them."""
     center_crop = False          # Resize((n, n)) of the box, no crop window
     mean, std = _MEAN, _STD
 
-    def __init__(self, image_size, min_scale=0.5, is_train=True):
+    def __init__(self, image_size, min_scale=0.5, is_train=True, randaugment=None):
         self.n_px = self.image_size = image_size
         self.min_scale, self.is_train = min_scale, is_train
+        self.randaugment = _randaugment_draw(randaugment)
 
     def draw(self, w, h):
         """-> (left, top, box_w, box_h, flip) for a w x h image"""
@@ -108,7 +122,10 @@ class RawBlipTransform:
         from .clip_front import RawImage
         data = torch.from_numpy(np.array(image.convert("RGB"), dtype=np.uint8))
         w, h = image.size
-        return RawImage(data, self.draw(w, h) if self.is_train else None)
+        if not self.is_train:
+            return RawImage(data)
+        geom = self.draw(w, h)
+        return RawImage(data, geom, self.randaugment.draw() if self.randaugment is not None else None)
 
 
 def interpolate_pos_embed(pos_embed_checkpoint, num_patches, num_extra_tokens=1):

@@ -801,13 +801,14 @@ class BLIPFeatureFusion(nn.Module):
         return k
 
     # ---- reference surface ---------------------------------------------------------------------------------
-    def get_img_preprocess_fn(self, raw=False):
+    def get_img_preprocess_fn(self, raw=False, randaugment=None):
         """raw=True: the deferred form of the same transform (blip_front.RawBlipTransform) -- the workers decode and draw the
-        crop box / flip, the batched device transform does the rest; also set it as the collator's `raw_transform`"""
+        crop box / flip, the batched device transform does the rest; also set it as the collator's `raw_transform`.
+        randaugment=(N, M): the reference's RandomAugment(N, M) in train mode (upstream trains with (2, 5)); either form"""
         from .blip_front import RawBlipTransform, get_blip_transform
         if raw:
-            return RawBlipTransform(self.image_size, min_scale=0.5, is_train=self.training)
-        return get_blip_transform(self.image_size, min_scale=0.5, is_train=self.training)
+            return RawBlipTransform(self.image_size, min_scale=0.5, is_train=self.training, randaugment=randaugment)
+        return get_blip_transform(self.image_size, min_scale=0.5, is_train=self.training, randaugment=randaugment)
 
     def get_tokenizer(self):
         from .blip_front import init_tokenizer

@@ -84,9 +84,11 @@ class PackedImages:
     uint8 host buffer holding [descriptor table | plan table | pixels, every image 16-byte aligned] (include/uniir_hip.h
     [IMAGE]).  `geoms[i]` = (box_left, box_top, box_w, box_h, oh, ow, top, left, flip) of image i, or None for the CLIP
     chain on the whole image; `out_index[i]` = the output slot it lands in (default i).  The plan call validates the table
-    on the host: a malformed descriptor raises here, before anything reaches the device."""
+    on the host: a malformed descriptor raises here, before anything reaches the device.  `augs[i]` = the augmentation ops of
+    image i as (name | op code, arg) pairs (uniir_amd/randaugment.py) or None; with `augs` the aug table of
+    uniir_image_aug_plan joins the same buffer, after the plan table, and run() calls the _aug entry point."""
 
-    def __init__(self, images, geoms, n_px, out_index=None, out_items=None, pin=False):
+    def __init__(self, images, geoms, n_px, out_index=None, out_items=None, pin=False, augs=None):
         import ctypes
 
         from . import _lib
@@ -127,12 +129,26 @@ class PackedImages:
         nd, npl = count * ctypes.sizeof(_lib.ImageDesc), count * ctypes.sizeof(_lib.ImagePlan)
         self.plan0 = (nd + 255) & ~255
         self.pix0 = self.plan0 + ((npl + 255) & ~255)
+        self.aug_info, aug_table = None, None
+        if augs is not None and count:
+            from . import randaugment
+            if len(augs) != count:
+                raise ValueError("augs must have one entry per image")
+            codes, args, slots = randaugment.op_arrays(augs)
+            aug_table, self.aug_info = (_lib.ImageAug * count)(), _lib.ImageAugInfo()
+            _lib.check(lib.uniir_image_aug_plan(codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                args.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), count, slots, self.n_px,
+                                                aug_table, ctypes.byref(self.aug_info)), "image_aug_plan")
+            self.aug0, na = self.pix0, count * ctypes.sizeof(_lib.ImageAug)
+            self.pix0 = self.aug0 + ((na + 255) & ~255)
         self.blob = torch.empty(self.pix0 + off, dtype=torch.uint8, pin_memory=bool(pin))
         self.pinned = bool(pin)
         view = self.blob.numpy()
         if count:
             view[:nd] = np.frombuffer(descs, dtype=np.uint8, count=nd)
             view[self.plan0:self.plan0 + npl] = np.frombuffer(plans, dtype=np.uint8, count=npl)
+        if aug_table is not None:
+            view[self.aug0:self.aug0 + na] = np.frombuffer(aug_table, dtype=np.uint8, count=na)
         for i, a in enumerate(arrays):
             view[self.pix0 + descs[i].offset:self.pix0 + descs[i].offset + a.size] = a.reshape(-1)
         self.descs, self.plans = descs, plans
@@ -153,9 +169,16 @@ class PackedImages:
         if self.count == 0:
             return out
         dev = self.blob.to(device, non_blocking=True) if blob is None else blob
-        ws = torch.empty(max(int(self.info.workspace_bytes), 256), device=device, dtype=torch.uint8)
+        need = int(self.info.workspace_bytes) + (int(self.aug_info.workspace_bytes) if self.aug_info is not None else 0)
+        ws = torch.empty(max(need, 256), device=device, dtype=torch.uint8)
         mean_c, std_c = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
         base = dev.data_ptr()
+        if self.aug_info is not None:
+            _lib.check(lib.uniir_image_preprocess_batch_aug(
+                base + self.pix0, base, base + self.plan0, ctypes.byref(self.info), base + self.aug0, ctypes.byref(self.aug_info),
+                mean_c, std_c, out.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(device).cuda_stream),
+                "image_preprocess_batch_aug")
+            return out
         _lib.check(lib.uniir_image_preprocess_batch(base + self.pix0, base, base + self.plan0, ctypes.byref(self.info), mean_c,
                                                     std_c, out.data_ptr(), ws.data_ptr(), ws.numel(),
                                                     torch.cuda.current_stream(device).cuda_stream), "image_preprocess_batch")
@@ -173,13 +196,46 @@ def preprocess_batch_on_device(images, geoms, n_px, device, mean=_MEAN, std=_STD
     return packed.run(device, mean, std, out=out)
 
 
+def augment_batch_on_device(images, ops_per_image, out=None):
+    """the augmentation op kernels alone (uniir_image_augment_batch): device uint8 [count, n, n, 3] + one list of (name | op code,
+    arg) pairs per image (uniir_amd/randaugment.py; None = none) -> a new uint8 [count, n, n, 3]; two launches per op slot
+    whatever the batch size.  -> (out, the plan's summary)"""
+    import ctypes
+
+    from . import _lib, randaugment
+    lib = _lib.load()
+    if (not images.is_cuda or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3
+            or images.shape[1] != images.shape[2] or not images.is_contiguous()):
+        raise ValueError("images must be a contiguous device uint8 [count, n, n, 3] tensor")
+    count, n = int(images.shape[0]), int(images.shape[1])
+    if len(ops_per_image) != count:
+        raise ValueError("one op list per image")
+    codes, args, slots = randaugment.op_arrays(ops_per_image)
+    table, info = (_lib.ImageAug * max(count, 1))(), _lib.ImageAugInfo()
+    _lib.check(lib.uniir_image_aug_plan(codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                        args.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), count, slots, n, table,
+                                        ctypes.byref(info)), "image_aug_plan")
+    if out is None:
+        out = torch.empty_like(images)
+    if count == 0:
+        return out, info
+    nbytes = count * ctypes.sizeof(_lib.ImageAug)
+    dev_table = torch.from_numpy(np.frombuffer(table, dtype=np.uint8, count=nbytes).copy()).to(images.device)
+    ws = torch.empty(max(int(info.workspace_bytes), 256), device=images.device, dtype=torch.uint8)
+    _lib.check(lib.uniir_image_augment_batch(images.data_ptr(), dev_table.data_ptr(), ctypes.byref(info), out.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), torch.cuda.current_stream(images.device).cuda_stream),
+               "image_augment_batch")
+    return out, info
+
+
 class RawImage:
     """a decoded RGB image waiting for the device transform (uint8 [h, w, 3], shareable between loader workers); `geom` =
-    (box_left, box_top, box_w, box_h, flip) drawn by the worker (blip_front.RawBlipTransform), None = the whole image"""
-    __slots__ = ("data", "geom")
+    (box_left, box_top, box_w, box_h, flip) drawn by the worker (blip_front.RawBlipTransform), None = the whole image; `ops` =
+    the augmentation ops it drew as (name, arg) pairs (uniir_amd/randaugment.py), None = none"""
+    __slots__ = ("data", "geom", "ops")
 
-    def __init__(self, data, geom=None):
-        self.data, self.geom = data, geom
+    def __init__(self, data, geom=None, ops=None):
+        self.data, self.geom, self.ops = data, geom, ops
 
 
 class RawImageTransform:
@@ -208,14 +264,16 @@ class RawImageBatch:
     def _pack(self, pin):
         t = self.transform
         have = [i for i, im in enumerate(self.images) if im is not None]
-        datas, geoms = [], []
+        datas, geoms, augs = [], [], []
         for i in have:
             im = self.images[i]
             data, g = (im.data, im.geom) if isinstance(im, RawImage) else (im, None)
+            augs.append(im.ops if isinstance(im, RawImage) else None)     # a batch of Identity alone takes the plain entry: same bits
             left, top, bw, bh, flip = g if g is not None else (0, 0, int(data.shape[1]), int(data.shape[0]), 0)
             datas.append(data)      # the transform's own Resize (+ CenterCrop) applied to the box
             geoms.append((left, top, bw, bh) + resize_geometry(bh, bw, t.n_px, t.center_crop) + (flip,))
-        return PackedImages(datas, geoms, t.n_px, out_index=have, out_items=len(self.images), pin=pin)
+        return PackedImages(datas, geoms, t.n_px, out_index=have, out_items=len(self.images), pin=pin,
+                            augs=augs if any(name not in ("Identity", 0) for a in augs if a for name, _ in a) else None)
 
     def pin_memory(self):
         if self._packed is None or not self._packed.pinned:

@@ -6,6 +6,8 @@
 // (22-bit fixed-point weights, horizontal pass into a uint8 intermediate, then vertical), float stage the same two IEEE
 // divisions.  HBM-bound byte work: three small launches per image, only the rows / columns the crop keeps are computed.
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <vector>
 #include "common.h"
 #include "../../include/uniir_hip.h"
@@ -261,10 +263,13 @@ __global__ __launch_bounds__(256) void img_batch_horizontal_kernel(const unsigne
 }
 // all vertical passes + ToTensor + Normalize: grid (image, 256 output pixels), x fastest, so the fp32 stores are coalesced; the
 // flip mirrors the column that is READ
+// U8: the same pixels as bytes, u8out[image][ty][tx][3] by position in the table (the augmentation ops run on them before ToTensor)
+template <bool U8>
 __global__ __launch_bounds__(256) void img_batch_vertical_kernel(const uniir_image_desc* __restrict__ descs,
                                                                  const uniir_image_plan* __restrict__ plans, int n,
                                                                  const unsigned char* __restrict__ ws, float m0, float m1, float m2,
-                                                                 float s0, float s1, float s2, float* __restrict__ out) {
+                                                                 float s0, float s1, float s2, float* __restrict__ out,
+                                                                 unsigned char* __restrict__ u8out) {
     const int idx = blockIdx.y * 256 + threadIdx.x;
     if (idx >= n * n) return;
     const uniir_image_desc d = descs[blockIdx.x];
@@ -291,6 +296,11 @@ __global__ __launch_bounds__(256) void img_batch_vertical_kernel(const uniir_ima
         p0 = img_clip8(a0); p1 = img_clip8(a1); p2 = img_clip8(a2);
     }
     const long plane = (long)n * n;
+    if (U8) {
+        unsigned char* b = u8out + ((long)blockIdx.x * plane + idx) * 3;
+        b[0] = p0; b[1] = p1; b[2] = p2;
+        return;
+    }
     float* o = out + (long)d.out_index * 3 * plane;
     o[idx] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)p0, 255.0f), m0), s0);
     o[plane + idx] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)p1, 255.0f), m1), s1);
@@ -371,8 +381,334 @@ extern "C" int uniir_image_preprocess_batch(const void* packed_u8, const uniir_i
     hipLaunchKernelGGL(img_batch_coeffs_kernel, dim3(count, 2, (n + 63) / 64), dim3(64), 0, st, descs, plans, n, ws);
     hipLaunchKernelGGL(img_batch_horizontal_kernel, dim3(count, (info->max_rows + IMGB_ROWS - 1) / IMGB_ROWS), dim3(256), 0, st,
                        (const unsigned char*)packed_u8, descs, plans, n, ws);
-    hipLaunchKernelGGL(img_batch_vertical_kernel, dim3(count, (n * n + 255) / 256), dim3(256), 0, st, descs, plans, n,
-                       (const unsigned char*)ws, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], out);
+    hipLaunchKernelGGL(img_batch_vertical_kernel<false>, dim3(count, (n * n + 255) / 256), dim3(256), 0, st, descs, plans, n,
+                       (const unsigned char*)ws, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], out, (unsigned char*)nullptr);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Train-time augmentation (include/uniir_hip.h [IMAGE]): one uniir_image_aug record per image, up to four op
+// slots applied in order on uint8 [count][n][n][3].  Per slot two launches whatever the batch: statistics (per-channel histograms
+// in LDS -> the 256-entry tables of the ops that need them) and apply (table lookup, fixed-point bilinear gather, 3x3 filter or
+// copy, by op code), ping-ponging between two buffers.  Every formula below is restated in numpy by tests/randaugment_ref.py and
+// compared byte for byte: fp64 / fp32 products are rounded before they are summed (the __d*_rn / __f*_rn forms say so).
+// ------------------------------------------------------------------------------------------------------------------------------
+#define AUG_STAT_THREADS 1024
+#define AUG_STAT_WAVES (AUG_STAT_THREADS / 64)
+#define AUG_FILL 128
+#define AUG_MAX_ARG 1e6
+
+DEVINL bool aug_needs_stats(int op) {
+    return op == UNIIR_AUG_AUTOCONTRAST || op == UNIIR_AUG_EQUALIZE || op == UNIIR_AUG_AUTOCONTRAST_PIL;
+}
+// one workgroup per image; images whose op of this slot needs no histogram leave at once.  lut[image][3][256]
+__global__ __launch_bounds__(AUG_STAT_THREADS) void img_aug_stats_kernel(const unsigned char* __restrict__ src,
+                                                                         const uniir_image_aug* __restrict__ table, int slot, int n,
+                                                                         unsigned char* __restrict__ lut) {
+    __shared__ unsigned int sub[AUG_STAT_WAVES][3][256];        // one histogram per wave: integer LDS atomics, order-independent
+    __shared__ unsigned int hist[3][256];
+    __shared__ unsigned int scan[256];
+    __shared__ int lohi[2];
+    const int op = table[blockIdx.x].slot[slot].op;
+    if (!aug_needs_stats(op)) return;
+    const int t = threadIdx.x;
+    for (int i = t; i < AUG_STAT_WAVES * 3 * 256; i += AUG_STAT_THREADS) (&sub[0][0][0])[i] = 0;
+    __syncthreads();
+    const long pixels = (long)n * n;
+    const unsigned char* img = src + (long)blockIdx.x * pixels * 3;
+    unsigned int(*mine)[256] = sub[t >> 6];
+    if ((pixels & 3) == 0 && ((uintptr_t)img & 3) == 0) {      // even n, image on a dword boundary: 4 pixels = 3 dwords
+        const uint32_t* words = (const uint32_t*)img;
+#pragma unroll 2
+        for (long g = t; g < pixels / 4; g += AUG_STAT_THREADS) {
+            const uint32_t w0 = words[3 * g], w1 = words[3 * g + 1], w2 = words[3 * g + 2];     // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+            atomicAdd(&mine[0][w0 & 255], 1u);
+            atomicAdd(&mine[1][(w0 >> 8) & 255], 1u);
+            atomicAdd(&mine[2][(w0 >> 16) & 255], 1u);
+            atomicAdd(&mine[0][w0 >> 24], 1u);
+            atomicAdd(&mine[1][w1 & 255], 1u);
+            atomicAdd(&mine[2][(w1 >> 8) & 255], 1u);
+            atomicAdd(&mine[0][(w1 >> 16) & 255], 1u);
+            atomicAdd(&mine[1][w1 >> 24], 1u);
+            atomicAdd(&mine[2][w2 & 255], 1u);
+            atomicAdd(&mine[0][(w2 >> 8) & 255], 1u);
+            atomicAdd(&mine[1][(w2 >> 16) & 255], 1u);
+            atomicAdd(&mine[2][w2 >> 24], 1u);
+        }
+    } else {
+        for (long p = t; p < pixels; p += AUG_STAT_THREADS) {
+            atomicAdd(&mine[0][img[3 * p]], 1u);
+            atomicAdd(&mine[1][img[3 * p + 1]], 1u);
+            atomicAdd(&mine[2][img[3 * p + 2]], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = t; i < 3 * 256; i += AUG_STAT_THREADS) {
+        unsigned int s = 0;
+        for (int w = 0; w < AUG_STAT_WAVES; ++w) s += (&sub[w][0][0])[i];
+        (&hist[0][0])[i] = s;
+    }
+    __syncthreads();
+    for (int c = 0; c < 3; ++c) {
+        if (t == 0) { lohi[0] = 256; lohi[1] = -1; }
+        if (t < 256) scan[t] = hist[c][t];
+        __syncthreads();
+        if (t < 256 && hist[c][t]) {
+            atomicMin(&lohi[0], t);
+            atomicMax(&lohi[1], t);
+        }
+        for (int off = 1; off < 256; off <<= 1) {               // inclusive prefix sums of the 256 bins
+            const unsigned int a = (t < 256 && t >= off) ? scan[t - off] : 0;
+            __syncthreads();
+            if (t < 256) scan[t] += a;
+            __syncthreads();
+        }
+        if (t < 256) {
+            const int lo = lohi[0], hi = lohi[1];
+            int v = t;                                          // an unchanged channel: the identity table
+            if (op == UNIIR_AUG_EQUALIZE) {
+                const unsigned int step = (scan[255] - hist[c][hi]) / 255u;
+                if (step) {
+                    const unsigned int q = (step / 2 + scan[t] - hist[c][t]) / step;
+                    v = q > 255u ? 255 : (int)q;
+                }
+            } else if (hi > lo) {
+                const double scale = __ddiv_rn(255.0, (double)(hi - lo));
+                const double off = op == UNIIR_AUG_AUTOCONTRAST_PIL ? __dmul_rn(-(double)lo, scale)
+                                                                    : __dmul_rn((double)((256 - lo) % 256), scale);
+                double f = __dadd_rn(__dmul_rn((double)t, scale), off);
+                f = f < 0.0 ? 0.0 : (f > 255.0 ? 255.0 : f);
+                v = (int)f;
+            }
+            lut[((long)blockIdx.x * 3 + c) * 256 + t] = (unsigned char)v;
+        }
+        __syncthreads();                                        // scan and lohi are reused by the next channel
+    }
+}
+
+DEVINL long aug_fix(double v) {                                  // rint (half to even), saturated to int32
+    v = rint(v);
+    v = v < -2147483648.0 ? -2147483648.0 : (v > 2147483647.0 ? 2147483647.0 : v);
+    return (long)v;
+}
+DEVINL int aug_tap(const unsigned char* __restrict__ img, int n, long yy, long xx, int c) {
+    return (yy >= 0 && yy < n && xx >= 0 && xx < n) ? img[(yy * n + xx) * 3 + c] : AUG_FILL;
+}
+DEVINL int aug_reflect(int i, int n) { return i < 0 ? (n > 1 ? 1 : 0) : (i >= n ? (n > 1 ? n - 2 : 0) : i); }
+// grid (image, 256 pixels): dst[image][y][x][:] = op(src[image]) for the op of this slot
+__global__ __launch_bounds__(256) void img_aug_apply_kernel(const unsigned char* __restrict__ src,
+                                                            const uniir_image_aug* __restrict__ table, int slot, int n,
+                                                            const unsigned char* __restrict__ lut, unsigned char* __restrict__ dst) {
+    const int idx = blockIdx.y * 256 + threadIdx.x;
+    if (idx >= n * n) return;
+    const uniir_image_aug_slot s = table[blockIdx.x].slot[slot];
+    const long base = (long)blockIdx.x * n * n * 3;
+    const unsigned char* img = src + base;
+    const unsigned char* px = img + (long)idx * 3;
+    unsigned char* o = dst + base + (long)idx * 3;
+    const int y = idx / n, x = idx - y * n;
+    int r0 = px[0], r1 = px[1], r2 = px[2];
+    switch (s.op) {
+    case UNIIR_AUG_AUTOCONTRAST:
+    case UNIIR_AUG_AUTOCONTRAST_PIL:
+    case UNIIR_AUG_EQUALIZE: {
+        const unsigned char* l = lut + (long)blockIdx.x * 768;
+        r0 = l[r0]; r1 = l[256 + r1]; r2 = l[512 + r2];
+        break;
+    }
+    case UNIIR_AUG_BRIGHTNESS: {
+        const float f = (float)s.p[0];
+        float v0 = __fmul_rn((float)r0, f), v1 = __fmul_rn((float)r1, f), v2 = __fmul_rn((float)r2, f);
+        r0 = (int)(v0 < 0.f ? 0.f : (v0 > 255.f ? 255.f : v0));
+        r1 = (int)(v1 < 0.f ? 0.f : (v1 > 255.f ? 255.f : v1));
+        r2 = (int)(v2 < 0.f ? 0.f : (v2 > 255.f ? 255.f : v2));
+        break;
+    }
+    case UNIIR_AUG_SHARPNESS: {
+        if (s.p[0] == 1.0) break;
+        const float k = __fdiv_rn(1.0f, 13.0f), kc = __fdiv_rn(5.0f, 13.0f), f = (float)s.p[0];
+        const bool blend = s.p[0] != 0.0;
+        if (blend && (x == 0 || y == 0 || x == n - 1 || y == n - 1)) break;     // the border keeps the input
+        int in3[3] = {r0, r1, r2}, out3[3];
+        for (int c = 0; c < 3; ++c) {
+            float acc = 0.f;
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const float p = (float)img[((long)aug_reflect(y + dy, n) * n + aug_reflect(x + dx, n)) * 3 + c];
+                    acc = __fadd_rn(acc, __fmul_rn(p, (dy == 0 && dx == 0) ? kc : k));
+                }
+            float d = rintf(acc);
+            d = d < 0.f ? 0.f : (d > 255.f ? 255.f : d);
+            if (blend) {
+                float v = truncf(__fadd_rn(d, __fmul_rn(f, __fsub_rn((float)in3[c], d))));
+                v = v < -2147483648.f ? -2147483648.f : (v > 2147483520.f ? 2147483520.f : v);
+                out3[c] = (int)((long)v & 255);
+            } else {
+                out3[c] = (int)d;
+            }
+        }
+        r0 = out3[0]; r1 = out3[1]; r2 = out3[2];
+        break;
+    }
+    case UNIIR_AUG_SHEAR_X:
+    case UNIIR_AUG_SHEAR_Y:
+    case UNIIR_AUG_TRANSLATE_X:
+    case UNIIR_AUG_TRANSLATE_Y:
+    case UNIIR_AUG_ROTATE: {
+        const double xd = (double)x, yd = (double)y;
+        const long X = (aug_fix(__dmul_rn(__dadd_rn(__dmul_rn(s.p[1], yd), s.p[2]), 1024.0)) + 16 +
+                        aug_fix(__dmul_rn(__dmul_rn(s.p[0], xd), 1024.0))) >> 5;
+        const long Y = (aug_fix(__dmul_rn(__dadd_rn(__dmul_rn(s.p[4], yd), s.p[5]), 1024.0)) + 16 +
+                        aug_fix(__dmul_rn(__dmul_rn(s.p[3], xd), 1024.0))) >> 5;
+        const long sx = X >> 5, sy = Y >> 5;
+        const int fx = (int)(X & 31), fy = (int)(Y & 31);
+        // rint(wy * wx * 32768) of the 1/32 fractions: exact integers that sum to 32768, the correction never applies
+        const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
+        int out3[3];
+        for (int c = 0; c < 3; ++c) {
+            const int acc = aug_tap(img, n, sy, sx, c) * w00 + aug_tap(img, n, sy, sx + 1, c) * w01 +
+                            aug_tap(img, n, sy + 1, sx, c) * w10 + aug_tap(img, n, sy + 1, sx + 1, c) * w11;
+            out3[c] = (acc + 16384) >> 15;
+        }
+        r0 = out3[0]; r1 = out3[1]; r2 = out3[2];
+        break;
+    }
+    default: break;                                             // Identity: a copy
+    }
+    o[0] = (unsigned char)r0; o[1] = (unsigned char)r1; o[2] = (unsigned char)r2;
+}
+// ToTensor + Normalize of the augmented bytes: the expression and the x-fastest store order of img_batch_vertical_kernel
+__global__ __launch_bounds__(256) void img_aug_normalize_kernel(const unsigned char* __restrict__ src,
+                                                                const uniir_image_desc* __restrict__ descs, int n, float m0, float m1,
+                                                                float m2, float s0, float s1, float s2, float* __restrict__ out) {
+    const int idx = blockIdx.y * 256 + threadIdx.x;
+    if (idx >= n * n) return;
+    const long plane = (long)n * n;
+    const unsigned char* px = src + ((long)blockIdx.x * plane + idx) * 3;
+    const unsigned char p0 = px[0], p1 = px[1], p2 = px[2];
+    float* o = out + (long)descs[blockIdx.x].out_index * 3 * plane;
+    o[idx] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)p0, 255.0f), m0), s0);
+    o[plane + idx] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)p1, 255.0f), m1), s1);
+    o[2 * plane + idx] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)p2, 255.0f), m2), s2);
+}
+
+// forward matrix of a warp op -> its fp64 inverse (every product rounded before it is summed: no contraction in this file)
+static void aug_inverse(int op, double arg, int n, double* p) {
+    double a00 = 1, a01 = 0, a02 = 0, a10 = 0, a11 = 1, a12 = 0;
+    if (op == UNIIR_AUG_SHEAR_X) a01 = (double)(float)arg;
+    else if (op == UNIIR_AUG_SHEAR_Y) a10 = (double)(float)arg;
+    else if (op == UNIIR_AUG_TRANSLATE_X) a02 = (double)(float)-arg;
+    else if (op == UNIIR_AUG_TRANSLATE_Y) a12 = (double)(float)-arg;
+    else {
+        const double cx = n / 2.0, cy = n / 2.0, rad = arg * (3.141592653589793 / 180.0);
+        const double a = cos(rad), b = sin(rad);
+        a00 = a; a01 = b; a02 = (1 - a) * cx - b * cy;
+        a10 = -b; a11 = a; a12 = b * cx + (1 - a) * cy;
+    }
+    double d = a00 * a11 - a01 * a10;
+    d = d != 0 ? 1.0 / d : 0.0;
+    const double i00 = a11 * d, i11 = a00 * d, i01 = a01 * -d, i10 = a10 * -d;
+    p[0] = i00; p[1] = i01; p[2] = -i00 * a02 - i01 * a12;
+    p[3] = i10; p[4] = i11; p[5] = -i10 * a02 - i11 * a12;
+}
+
+extern "C" int uniir_image_aug_plan(const int32_t* ops, const double* args, int32_t count, int32_t slots, int32_t n,
+                                    uniir_image_aug* table, uniir_image_aug_info* info) {
+    if (!info || count < 0 || n <= 0 || slots < 0 || slots > UNIIR_AUG_MAX_SLOTS) return UNIIR_EINVAL;
+    if (count > 0 && (!table || (slots > 0 && (!ops || !args)))) return UNIIR_EINVAL;
+    if (n > IMGB_MAX_N) return UNIIR_EUNSUPPORTED;
+    for (long i = 0; i < (long)count * slots; ++i) {
+        if (ops[i] < 0 || ops[i] >= UNIIR_AUG_OPS || !std::isfinite(args[i])) return UNIIR_EINVAL;
+    }
+    for (long i = 0; i < (long)count * slots; ++i)
+        if (fabs(args[i]) > AUG_MAX_ARG) return UNIIR_EUNSUPPORTED;
+    for (int i = 0; i < count; ++i) {
+        uniir_image_aug& rec = table[i];
+        memset(&rec, 0, sizeof(rec));                           // unused slots: Identity
+        for (int k = 0; k < slots; ++k) {
+            const int op = ops[(long)i * slots + k];
+            const double arg = args[(long)i * slots + k];
+            rec.slot[k].op = op;
+            if (op == UNIIR_AUG_BRIGHTNESS || op == UNIIR_AUG_SHARPNESS) rec.slot[k].p[0] = arg;
+            else if (op >= UNIIR_AUG_SHEAR_X && op <= UNIIR_AUG_ROTATE) aug_inverse(op, arg, n, rec.slot[k].p);
+        }
+    }
+    info->workspace_bytes = count > 0 ? 2 * img_align(3L * count * n * n) + img_align(768L * count) : 0;
+    info->count = count; info->n = n; info->slots = slots;
+    info->launches = count > 0 ? 2 * slots : 0;
+    info->launches_preprocess = count > 0 ? 3 + 2 * slots + 1 : 0;
+    info->reserved = 0;
+    return UNIIR_OK;
+}
+
+// slot k reads what slot k - 1 wrote (`first` for k = 0, never written) and writes `even` / `odd` by its parity -> the buffer the
+// last slot wrote
+static const unsigned char* aug_run_slots(hipStream_t st, const unsigned char* first, unsigned char* even, unsigned char* odd,
+                                          const uniir_image_aug* table, unsigned char* lut, int count, int n, int slots) {
+    const dim3 grid((unsigned)count, (unsigned)((n * n + 255) / 256));
+    const unsigned char* cur = first;
+    for (int k = 0; k < slots; ++k) {
+        unsigned char* nxt = (k & 1) ? odd : even;
+        hipLaunchKernelGGL(img_aug_stats_kernel, dim3((unsigned)count), dim3(AUG_STAT_THREADS), 0, st, cur, table, k, n, lut);
+        hipLaunchKernelGGL(img_aug_apply_kernel, grid, dim3(256), 0, st, cur, table, k, n, (const unsigned char*)lut, nxt);
+        cur = nxt;
+    }
+    return cur;
+}
+
+extern "C" int uniir_image_augment_batch(const void* in_u8, const uniir_image_aug* table, const uniir_image_aug_info* info,
+                                         void* out_u8, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!info || info->count < 0) return UNIIR_EINVAL;
+    if (info->count == 0) return UNIIR_OK;
+    if (!in_u8 || !table || !out_u8 || !workspace || in_u8 == out_u8) return UNIIR_EINVAL;
+    if (info->n <= 0 || info->n > IMGB_MAX_N || info->slots < 0 || info->slots > UNIIR_AUG_MAX_SLOTS) return UNIIR_EINVAL;
+    if (((uintptr_t)workspace & 255) || workspace_bytes < info->workspace_bytes) return UNIIR_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int n = info->n, count = info->count;
+    const int64_t buf = img_align(3L * count * n * n);
+    unsigned char* ws = (unsigned char*)workspace;
+    if (info->slots == 0) {
+        if (hipMemcpyAsync(out_u8, in_u8, 3L * count * n * n, hipMemcpyDeviceToDevice, st) != hipSuccess) return UNIIR_ELAUNCH;
+        return UNIIR_OK;
+    }
+    unsigned char* o = (unsigned char*)out_u8;                  // the last slot writes out_u8: it is `even` for an odd slot count
+    aug_run_slots(st, (const unsigned char*)in_u8, (info->slots & 1) ? o : ws, (info->slots & 1) ? ws : o, table, ws + 2 * buf, count,
+                  n, info->slots);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+extern "C" int uniir_image_preprocess_batch_aug(const void* packed_u8, const uniir_image_desc* descs, const uniir_image_plan* plans,
+                                                const uniir_image_batch_info* info, const uniir_image_aug* aug,
+                                                const uniir_image_aug_info* aug_info, const float* mean3, const float* std3,
+                                                float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!info || !aug_info || info->count < 0 || aug_info->count != info->count) return UNIIR_EINVAL;
+    if (info->count == 0) return UNIIR_OK;
+    if (!packed_u8 || !descs || !plans || !aug || !mean3 || !std3 || !out || !workspace) return UNIIR_EINVAL;
+    if (info->n <= 0 || info->n > IMGB_MAX_N || info->out_items <= 0 || info->max_rows <= 0 || aug_info->n != info->n)
+        return UNIIR_EINVAL;
+    if (aug_info->slots < 0 || aug_info->slots > UNIIR_AUG_MAX_SLOTS) return UNIIR_EINVAL;
+    if (((uintptr_t)packed_u8 & 15) || ((uintptr_t)workspace & 255) ||
+        workspace_bytes < info->workspace_bytes + aug_info->workspace_bytes)
+        return UNIIR_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int n = info->n;
+    const unsigned count = (unsigned)info->count;
+    unsigned char* ws = (unsigned char*)workspace;
+    const int64_t buf = img_align(3L * count * n * n);
+    unsigned char* u0 = ws + info->workspace_bytes;              // info->workspace_bytes is a multiple of 256
+    unsigned char* u1 = u0 + buf;
+    unsigned char* lut = u1 + buf;
+    const dim3 grid(count, (n * n + 255) / 256);
+    hipLaunchKernelGGL(img_batch_coeffs_kernel, dim3(count, 2, (n + 63) / 64), dim3(64), 0, st, descs, plans, n, ws);
+    hipLaunchKernelGGL(img_batch_horizontal_kernel, dim3(count, (info->max_rows + IMGB_ROWS - 1) / IMGB_ROWS), dim3(256), 0, st,
+                       (const unsigned char*)packed_u8, descs, plans, n, ws);
+    hipLaunchKernelGGL(img_batch_vertical_kernel<true>, grid, dim3(256), 0, st, descs, plans, n, (const unsigned char*)ws, 0.f, 0.f,
+                       0.f, 1.f, 1.f, 1.f, (float*)nullptr, u0);
+    const unsigned char* fin = aug_run_slots(st, u0, u1, u0, aug, lut, (int)count, n, aug_info->slots);
+    hipLaunchKernelGGL(img_aug_normalize_kernel, grid, dim3(256), 0, st, fin, descs, n, mean3[0], mean3[1],
+                       mean3[2], std3[0], std3[1], std3[2], out);
     HIP_LAUNCH_CHECK();
     return UNIIR_OK;
 }

@@ -87,7 +87,9 @@ def main(config):
         from uniir_amd import comm
         comm.sync_replicas(model)
     optimizer = NativeAdamW(model, lr=tc.init_lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=tc.weight_decay)
-    train_ds, collate = build_dataset(config, model.get_tokenizer(), model.get_img_preprocess_fn(), train=True)
+    # UNIIR_BLIP_RANDAUGMENT=1: the reference's RandomAugment(2, 5) in the train transform (blip_transform.py:11-40); off by default
+    randaugment = (2, 5) if os.environ.get("UNIIR_BLIP_RANDAUGMENT") == "1" else None
+    train_ds, collate = build_dataset(config, model.get_tokenizer(), model.get_img_preprocess_fn(randaugment=randaugment), train=True)
     sampler = DistributedSampler(train_ds, num_replicas=utils.get_world_size(), rank=utils.get_rank(), shuffle=True)
     loader = DataLoader(train_ds, batch_size=config.dataloader_config.train_batch_size,
                         num_workers=config.dataloader_config.num_workers, pin_memory=True, sampler=sampler, shuffle=False,
