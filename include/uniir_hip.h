@@ -36,7 +36,8 @@ extern "C" {
 const char* uniir_strerror(int code);
 /* ABI version; bumped on any signature or struct-layout change (3: uniir_clip_tower.recompute; 4: uniir_reduce_stats;
  * 5: uniir_image_*; 6: uniir_attention_fwd_long / _bwd_long; still 6, new entry points only: uniir_attention_rel_fwd_long /
- * _rel_bwd_long; uniir_attention_one_fwd / _one_bwd, and the value 2 of uniir_clip_tower.pool_last_block: no layout changes). */
+ * _rel_bwd_long; uniir_attention_one_fwd / _one_bwd, and the value 2 of uniir_clip_tower.pool_last_block; uniir_layernorm_fwd_f16,
+ * uniir_patchify_f16, uniir_vit_assemble_f16: no layout changes). */
 int uniir_abi_version(void);
 /* Reproducible reductions (round 6).  Bias, LayerNorm-weight and token-embedding gradients are sums over every row of a batch taken by
  * many workgroups; added with fp32 atomics they depend on the arrival order, and two runs of one training step differ in their last
@@ -143,6 +144,10 @@ int uniir_gemm_timing_filter(const float* windows, int32_t nwin, const float* sa
  * ---------------------------------------------------------------------------------------------- */
 int uniir_layernorm_fwd(const float* x, int64_t x_stride, const float* gamma, const float* beta,
                         void* y_bf16, float* y_f32, int32_t rows, int32_t width, float eps, void* stream);
+/* the forward with an fp16 16-bit output (the fp16 forward of an embedding tower, forward only): the same checks; y_f32 has the
+ * bits of uniir_layernorm_fwd's y_f32, y_f16 is that value rounded to fp16.  Either output may be NULL, not both. */
+int uniir_layernorm_fwd_f16(const float* x, int64_t x_stride, const float* gamma, const float* beta,
+                            void* y_f16, float* y_f32, int32_t rows, int32_t width, float eps, void* stream);
 int uniir_layernorm_bwd(const float* x, int64_t x_stride, const float* gamma, const void* dy,
                         int32_t dy_is_f32, const float* dres, float* dx_f32, int64_t dx_stride,
                         void* dx_bf16, float* dgamma, float* dbeta, float* dx_colsum, int32_t rows,
@@ -172,6 +177,9 @@ int uniir_layernorm_bwd_ex(const float* x, int64_t x_stride, const float* gamma,
  *   uniir_onequery_fwd / _bwd                  : ONE query row per item against tk <= 1024 keys with key_len or packed keys and dropout
  *                                                at the coordinates of the full call (the class row of BLIP's last BERT layer)
  *   Still 512 at most: the causal mask, fully packed rows (_packed, _rows with kv_packed).
+ *   On fp16 tensors (forward only): uniir_attention_fwd_f16 with the limits of uniir_attention_fwd / _fwd_packed (causal = 0 and
+ *   dense rows: seq <= 1024, the BLIP ViT at 384 pixels; else 512) and uniir_attention_one_fwd with f16 = 1.  The general form
+ *   (_ex, _rows, _long) has no fp16 entry point.
  * qkv bf16 [batch*seq][3*heads*64] as produced by nn.MultiheadAttention.in_proj ([q | k | v] per row);
  * out bf16 [batch*seq][heads*64]; lse f32 [batch][heads][seq] (natural log-sum-exp of scaled scores).
  * causal = 1 applies CLIP's build_attention_mask (key <= query).
@@ -308,7 +316,13 @@ int uniir_patchify(const float* images, void* patches, int32_t n, int32_t res, i
 /* x[n][1+g][w] (f32) = concat(class_emb, patch_out[n][g][w] (bf16)) + pos_emb[1+g][w] */
 int uniir_vit_assemble(const void* patch_out, const float* class_emb, const float* pos_emb, float* x,
                        int32_t n, int32_t tokens, int32_t width, void* stream);
-/* backward of the above: dpatch bf16 [n*g][w] = dx[:,1:,:]; dclass += sum_n dx[:,0,:]; dpos += sum_n dx */
+/* the two with fp16 in place of bf16 (the fp16 forward of a vision tower: fp16 patch rows for a UNIIR_DT_F16 patch-embedding GEMM,
+ * whose fp16 patch_out is read back here); the same checks, no backward */
+int uniir_patchify_f16(const float* images, void* patches, int32_t n, int32_t res, int32_t patch,
+                       int32_t kpad, void* stream);
+int uniir_vit_assemble_f16(const void* patch_out, const float* class_emb, const float* pos_emb, float* x,
+                           int32_t n, int32_t tokens, int32_t width, void* stream);
+/* backward of uniir_vit_assemble: dpatch bf16 [n*g][w] = dx[:,1:,:]; dclass += sum_n dx[:,0,:]; dpos += sum_n dx */
 int uniir_vit_assemble_bwd(const float* dx, void* dpatch_out, float* dclass, float* dpos, int32_t n,
                            int32_t tokens, int32_t width, void* stream);
 /* x[n][ctx][w] (f32) = token_emb[text[n][t]] + pos_emb[t]; also eot[n] = argmax_t text[n][t] (first max) */

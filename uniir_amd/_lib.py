@@ -103,6 +103,7 @@ SIGNATURES = {
     "uniir_gemm_timing_filter": (c_int, [C.POINTER(c_float), c_int, C.POINTER(c_float), c_int, c_float, C.POINTER(C.c_uint8),
                                          C.POINTER(c_int)]),
     "uniir_layernorm_fwd": (c_int, [P, c_i64, P, P, P, P, c_int, c_int, c_float, S]),
+    "uniir_layernorm_fwd_f16": (c_int, [P, c_i64, P, P, P, P, c_int, c_int, c_float, S]),
     "uniir_layernorm_bwd": (c_int, [P, c_i64, P, P, c_int, P, P, c_i64, P, P, P, P, c_int, c_int, c_float, S]),
     "uniir_layernorm_bwd_ex": (c_int, [P, c_i64, P, P, c_int, P, P, c_i64, P, P, P, P, P, c_int, c_int, c_float, S]),
     "uniir_attention_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, S]),
@@ -129,6 +130,8 @@ SIGNATURES = {
                                    C.c_uint32, c_int, c_int, S]),
     "uniir_patchify": (c_int, [P, P, c_int, c_int, c_int, c_int, S]),
     "uniir_vit_assemble": (c_int, [P, P, P, P, c_int, c_int, c_int, S]),
+    "uniir_patchify_f16": (c_int, [P, P, c_int, c_int, c_int, c_int, S]),
+    "uniir_vit_assemble_f16": (c_int, [P, P, P, P, c_int, c_int, c_int, S]),
     "uniir_vit_assemble_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, S]),
     "uniir_text_embed": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, S]),
     "uniir_text_embed_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, S]),

@@ -112,8 +112,11 @@ def vit_recompute_from(depth, vit_grad_ckpt, vit_ckpt_layer):
     return depth - min(max(int(vit_ckpt_layer), 0), depth)
 
 
-def vit_forward(st, conv16, prefix, cfg, img_size, images, save, drop=None, recompute_from=None):
+def vit_forward(st, conv16, prefix, cfg, img_size, images, save, drop=None, recompute_from=None, dtype16=torch.bfloat16):
     """src/models/uniir_blip/backbone/vit.py:196-221 -> bf16 tokens [M*T, D] (after the final norm) + stash.
+    dtype16 = torch.float16 (forward only: save False, conv16 the fp16 copy of the patch-embedding weight): patches, activations and
+    the returned tokens are fp16, the weights come from st's fp16 shadow (FlatStore.w16h); the residual stream, the LayerNorm
+    statistics and every accumulation stay fp32.  Three more mantissa bits in every operand, the same MFMA rate.
     drop (ops.DropSeeds, train mode): DropPath with rates linspace(0, drop_path_rate, depth) (vit.py:167), one Bernoulli
     draw per item and residual branch from torch's CPU generator.
     recompute_from: blocks from this one on keep only their input and are rebuilt in vit_backward (vit_recompute_from); the
@@ -124,19 +127,24 @@ def vit_forward(st, conv16, prefix, cfg, img_size, images, save, drop=None, reco
     T = G + 1
     heads = cfg["num_heads"]
     kpad = conv16.shape[1]
-    patches = torch.empty(M * G, kpad, device=dev, dtype=torch.bfloat16)
-    ops.call("uniir_patchify", images.float().contiguous(), patches, M, img_size, P, kpad)
+    half = dtype16 == torch.float16
+    if conv16.dtype != dtype16:
+        raise ValueError(f"vit_forward: a {conv16.dtype} patch-embedding weight with dtype16 = {dtype16}")
+    patches = torch.empty(M * G, kpad, device=dev, dtype=dtype16)
+    ops.call("uniir_patchify_f16" if half else "uniir_patchify", images.float().contiguous(), patches, M, img_size, P, kpad)
     po = ops.linear_fwd(patches, conv16, st.p(prefix + "patch_embed.proj.bias"))
     x0 = torch.empty(M * T, D, device=dev, dtype=torch.float32)
-    ops.call("uniir_vit_assemble", po, st.p(prefix + "cls_token"), st.p(prefix + "pos_embed"), x0, M, T, D)
+    ops.call("uniir_vit_assemble_f16" if half else "uniir_vit_assemble", po, st.p(prefix + "cls_token"), st.p(prefix + "pos_embed"),
+             x0, M, T, D)
     del po
     rowscale = None
     if drop is not None and cfg.get("drop_path_rate", 0.0) > 0 and depth > 1:
         keep = 1.0 - torch.linspace(0, cfg["drop_path_rate"], depth).view(depth, 1, 1)
         rowscale = (torch.floor(keep + torch.rand(depth, 2, M)) / keep).to(dev)
     x, saved = tower_fwd(st, lambda i: _vit_blk_names(prefix, i), depth, x0, M, T, D, heads, False, save, eps=VIT_EPS,
-                         act=ops.ACT_GELU_ERF, rowscale=rowscale, recompute_from=recompute_from)
-    tok = ops.layernorm_fwd(x, st.p(prefix + "norm.weight"), st.p(prefix + "norm.bias"), VIT_EPS, rows=M * T, width=D)
+                         act=ops.ACT_GELU_ERF, rowscale=rowscale, recompute_from=recompute_from, dtype16=dtype16)
+    tok = ops.layernorm_fwd(x, st.p(prefix + "norm.weight"), st.p(prefix + "norm.bias"), VIT_EPS, rows=M * T, width=D,
+                            dtype16=dtype16)
     stash = dict(patches=patches, x=x, saved=saved, M=M, T=T, rowscale=rowscale, recompute_from=recompute_from) if save else None
     return tok, T, stash
 
@@ -846,6 +854,7 @@ class BLIPFeatureFusion(nn.Module):
         self._conv16 = torch.zeros(D, kpad, device=dev, dtype=torch.bfloat16)
         self._conv16_m = torch.zeros(D, kpad, device=dev, dtype=torch.bfloat16)
         self._dconv = torch.zeros(D, kpad, device=dev, dtype=torch.float32)
+        self._conv16h = None              # fp16 twin of _conv16 (_vit_tokens(precision="fp16")): built on first use
         self._version = -1
         self.refresh_shadow()
         return self._online
@@ -865,6 +874,23 @@ class BLIPFeatureFusion(nn.Module):
         pairs = [(self._online, self._conv16)] + ([(self._mom, self._conv16_m)] if momentum_too else [])
         for st, dst in pairs:
             ops.call("uniir_cast_pad_rows", st.p("visual_encoder.patch_embed.proj.weight"), dst, D, 3 * P * P, dst.shape[1])
+            # every event that moves the master weights ends here -- refresh_shadow(), the fused AdamW (trainer.NativeAdamW.step) and
+            # the EMA of _momentum_update, which write p32 and the bf16 shadow themselves -- so the fp16 copies go stale here
+            st.mark_half_stale()
+
+    def _sync_half(self):
+        """_sync() plus the fp16 copies of the online encoder's weights (its store's fp16 shadow and the fp16 twin of _conv16): built
+        on first use, rebuilt whenever the bf16 ones were refreshed or the parameters moved since.  -> the online store"""
+        self._sync()
+        st = self._online
+        if self._conv16h is None or st.h16_buf is None or st.half_stale:
+            D, P = self.vit_cfg["embed_dim"], self.vit_cfg["patch_size"]
+            if self._conv16h is None:
+                self._conv16h = torch.zeros_like(self._conv16, dtype=torch.float16)
+            ops.call("uniir_cast_pad_rows_f16", st.p("visual_encoder.patch_embed.proj.weight"), self._conv16h, D, 3 * P * P,
+                     self._conv16h.shape[1])
+        st.half_shadow()
+        return st
 
     def refresh_shadow(self):
         self._online.refresh_shadow()
@@ -931,6 +957,29 @@ class BLIPFeatureFusion(nn.Module):
         if ver is not None:
             mask._uniir_pack = (ver, L, pack)
         return pack
+
+    @torch.no_grad()
+    def _vit_tokens(self, image_batched, precision="bf16"):
+        """Internal (the ViT leg of an fp16 embedding forward, and what the tests and tools/blip_vit_rate.py drive; not part of the
+        model's surface).  The online vision encoder on its own, forward only (no stash, no graph): the normed tokens [n, T, D] in
+        the 16-bit type of `precision`.  "bf16": the kernels of the training forward.  "fp16": the same launch sequence on fp16 operands and
+        activations from fp16 copies of the weights (vit_forward's dtype16) -- the reference embedder's arithmetic
+        (mbeir_embedder.py:52-56: autocast(fp16)), 577 tokens at 384 pixels included.  fp16 is an eval-mode path: in training mode
+        it raises (DropPath belongs to the bf16 training forward)."""
+        if precision not in ("bf16", "fp16"):
+            raise RuntimeError(f"unknown precision {precision!r}")
+        if precision == "fp16":
+            if self.training:
+                raise RuntimeError("precision='fp16' is a forward-only embedding path; call model.eval() first or use "
+                                   "precision='bf16'")
+            st = self._sync_half()
+            conv, dt, drop = self._conv16h, torch.float16, None
+        else:
+            self._sync()
+            st, conv, dt, drop = self._online, self._conv16, torch.bfloat16, self._drop_seeds()
+        tok, T, _ = vit_forward(st, conv, "visual_encoder.", self.vit_cfg, self.image_size, image_batched, False, drop=drop,
+                                dtype16=dt)
+        return tok.view(image_batched.shape[0], T, -1)
 
     def encode_multimodal_input(self, txt_dict_batched, image_batched, txt_mask=None, img_mask=None, use_momentum=False):
         """blip_ff.py:82-116: BERT(text) cross-attending to ViT(image) tokens -> pooler_output [n, embed_dim]"""

@@ -182,6 +182,10 @@ extern "C" int uniir_patchify(const float* images, void* patches, int32_t n, int
                               int32_t kpad, void* stream) {
     return patchify_impl(images, patches, n, res, patch, kpad, 0, stream);
 }
+extern "C" int uniir_patchify_f16(const float* images, void* patches, int32_t n, int32_t res, int32_t patch,
+                                  int32_t kpad, void* stream) {
+    return patchify_impl(images, patches, n, res, patch, kpad, 1, stream);
+}
 int patchify_impl(const float* images, void* patches, int32_t n, int32_t res, int32_t patch, int32_t kpad, int f16, void* stream) {
     if (!images || !patches || n < 0) return UNIIR_EINVAL;
     if (n == 0) return UNIIR_OK;
@@ -226,6 +230,10 @@ int vit_assemble_impl(const void* patch_out, const float* class_emb, const float
 extern "C" int uniir_vit_assemble(const void* patch_out, const float* class_emb, const float* pos_emb,
                                   float* x, int32_t n, int32_t tokens, int32_t width, void* stream) {
     return vit_assemble_impl(patch_out, class_emb, pos_emb, x, n, tokens, width, 0, stream);
+}
+extern "C" int uniir_vit_assemble_f16(const void* patch_out, const float* class_emb, const float* pos_emb,
+                                      float* x, int32_t n, int32_t tokens, int32_t width, void* stream) {
+    return vit_assemble_impl(patch_out, class_emb, pos_emb, x, n, tokens, width, 1, stream);
 }
 int vit_assemble_impl(const void* patch_out, const float* class_emb, const float* pos_emb, float* x, int32_t n, int32_t tokens,
                       int32_t width, int f16, void* stream) {

@@ -261,6 +261,13 @@ extern "C" int uniir_layernorm_fwd(const float* x, int64_t x_stride, const float
                                    void* stream) {
     return layernorm_fwd_impl(x, x_stride, gamma, beta, y_bf16, y_f32, rows, width, eps, 0, stream);
 }
+// the same with an fp16 16-bit output (what tower.hip's fp16 forward calls): y_f32 has the bits of uniir_layernorm_fwd's, y_f16 is
+// that value rounded to fp16
+extern "C" int uniir_layernorm_fwd_f16(const float* x, int64_t x_stride, const float* gamma, const float* beta,
+                                       void* y_f16, float* y_f32, int32_t rows, int32_t width, float eps,
+                                       void* stream) {
+    return layernorm_fwd_impl(x, x_stride, gamma, beta, y_f16, y_f32, rows, width, eps, 1, stream);
+}
 
 static int layernorm_bwd_impl(const float* x, int64_t x_stride, const float* gamma, const void* dy, int32_t dy_is_f32,
                               const float* dres, float* dx_f32, int64_t dx_stride, void* dx_bf16, float* dgamma, float* dbeta,

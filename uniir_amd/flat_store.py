@@ -17,7 +17,8 @@ def padded(numel):
 class FlatStore:
     """p32 fp32 [total] (master weights), g32 fp32 [total] (gradients; None without), w16_buf bf16 [total] (shadow of
     p32, refresh_shadow()); tensor `name` occupies [off[name], off[name] + numel) of each, in the order it was given.
-    The named views are p(name) (fp32), w16(name) and grad_view(name)."""
+    The named views are p(name) (fp32), w16(name) and grad_view(name); w16h(name) is w16's twin in the optional fp16 shadow
+    (h16_buf: the forward-only fp16 path, built on first use)."""
 
     def __init__(self, named_shapes, device, with_grad=True):
         self.off, self.shapes, cur = {}, {}, 0
@@ -29,6 +30,11 @@ class FlatStore:
         self.g32 = torch.zeros(cur, device=device, dtype=torch.float32) if with_grad else None
         self.w16_buf = torch.empty(cur, device=device, dtype=torch.bfloat16)
         self.dev = self.p32.device
+        # the optional fp16 shadow (w16h()): `total` halves in the same layout, allocated and filled on first use, filled again on
+        # the next use once marked stale -- by refresh_shadow(), and by mark_half_stale() for writers that go past this class (the
+        # fused AdamW and EMA kernels write p32 and w16_buf themselves).  A store that never asks for it allocates nothing.
+        self.h16_buf = None
+        self.half_stale = True
 
     @classmethod
     def adopt(cls, named, device, with_grad=True, frozen=()):
@@ -65,6 +71,10 @@ class FlatStore:
     def w16(self, name, shape=None):
         return self._view(self.w16_buf, name, shape)
 
+    def w16h(self, name, shape=None):
+        """fp16 view of `name` (same offsets and spans as w16) in the fp16 shadow, which is built or rebuilt here when it is stale"""
+        return self._view(self.half_shadow(), name, shape)
+
     def grad_view(self, name, shape=None):
         return self._view(self.g32, name, shape)
 
@@ -98,6 +108,21 @@ class FlatStore:
     # ---- device work ---------------------------------------------------------------------------------------------
     def refresh_shadow(self):
         ops.call("uniir_cast_f32_to_bf16", self.p32, self.w16_buf, self.total)
+        self.half_stale = True
+
+    def mark_half_stale(self):
+        """the master weights moved without refresh_shadow() (a kernel that writes p32 and the bf16 shadow itself)"""
+        self.half_stale = True
+
+    def half_shadow(self):
+        """the fp16 shadow of p32, up to date: one cast of the whole buffer on first use and after every event that marked it stale"""
+        if self.h16_buf is None:
+            self.h16_buf = torch.empty(self.total, device=self.dev, dtype=torch.float16)
+            self.half_stale = True
+        if self.half_stale:
+            ops.call("uniir_cast_f32_to_f16", self.p32, self.h16_buf, self.total)
+            self.half_stale = False
+        return self.h16_buf
 
     def zero_grad(self, named, frozen=()):
         """one memset of the gradient buffer; a parameter whose .grad was replaced gets its view back"""

@@ -171,15 +171,28 @@ def gemm(A, B, C_out, M, N, K, lda, ldb, ldc, *, a_tmaj=False, b_tmaj=False, epi
     return C_out
 
 
+def _dtype16(first, *rest):
+    """DT_BF16 / DT_F16 of a call from its 16-bit operands (None entries skipped): they all have the type of `first`.  fp16 is the
+    forward-only path of the embedding towers; mixing it with bf16 is a ValueError, raised before anything is launched"""
+    half = first.dtype == torch.float16
+    for t in rest:
+        if t is not None and (t.dtype == torch.float16) != half:
+            raise ValueError(f"mixed 16-bit operands: {first.dtype} with {t.dtype} (an fp16 call takes fp16 tensors only)")
+    return DT_F16 if half else DT_BF16
+
+
 def linear_fwd(x, w, bias=None, *, out=None, epilogue=EPI_BF16, resid=None, C2=None, act=ACT_QUICKGELU, row_scale=None):
     """y[M,N] = x[M,K] @ w[N,K]^T (+bias ...).  x, w bf16 contiguous.  row_scale (fp32 [M], EPI_RESID_F32): the branch output is
-    multiplied by it before the residual is added (DropPath)."""
+    multiplied by it before the residual is added (DropPath).
+    The 16-bit type follows x: an fp16 x needs an fp16 w (ValueError otherwise), the product runs as UNIIR_DT_F16 and the 16-bit
+    outputs are fp16 (the forward-only fp16 path; the library refuses the epilogues that have no fp16 form)."""
     M, K = x.shape
     N = w.shape[0]
+    dt16 = _dtype16(x, w, *(() if epilogue in (EPI_RESID_F32, EPI_F32) else (out,)), C2)
     if out is None:
-        out = torch.empty(M, N, device=x.device,
-                          dtype=torch.float32 if epilogue in (EPI_RESID_F32, EPI_F32) else torch.bfloat16)
-    return gemm(x, w, out, M, N, K, K, K, N, epilogue=epilogue, bias=bias, resid=resid, C2=C2, act=act, row_scale=row_scale)
+        out = torch.empty(M, N, device=x.device, dtype=torch.float32 if epilogue in (EPI_RESID_F32, EPI_F32) else x.dtype)
+    return gemm(x, w, out, M, N, K, K, K, N, epilogue=epilogue, bias=bias, resid=resid, C2=C2, act=act, row_scale=row_scale,
+                dtype=dt16)
 
 
 def linear_dgrad(dy, w, *, out=None, aux=None, act=ACT_QUICKGELU, act_out=None, colsum=None):
@@ -216,12 +229,19 @@ def linear_wgrad(dy, x, dw, *, dbias=None):
                 k_splits=wgrad_splits(M, tiles), a_rowsum=dbias)
 
 
-def layernorm_fwd(x, gamma, beta, eps=1e-5, *, out_bf16=None, out_f32=None, rows=None, width=None, x_stride=None):
+def layernorm_fwd(x, gamma, beta, eps=1e-5, *, out_bf16=None, out_f32=None, rows=None, width=None, x_stride=None,
+                  dtype16=torch.bfloat16):
+    """out_bf16: the 16-bit output; an fp16 tensor there (or dtype16 = torch.float16 when this function allocates it) takes
+    uniir_layernorm_fwd_f16 -- the same fp32 result, rounded to fp16 (the forward-only fp16 path)"""
     width = width or x.shape[-1]
     rows = rows if rows is not None else x.numel() // width
     x_stride = x_stride or width
     if out_bf16 is None and out_f32 is None:
-        out_bf16 = torch.empty(rows, width, device=x.device, dtype=torch.bfloat16)
+        out_bf16 = torch.empty(rows, width, device=x.device, dtype=dtype16)
+    if out_bf16 is not None and out_bf16.dtype == torch.float16:
+        check(_lib.load().uniir_layernorm_fwd_f16(_p(x), x_stride, _p(gamma), _p(beta), _p(out_bf16), _p(out_f32), rows,
+                                                  width, eps, _stream()), "layernorm_fwd_f16")
+        return out_bf16
     check(_lib.load().uniir_layernorm_fwd(_p(x), x_stride, _p(gamma), _p(beta), _p(out_bf16), _p(out_f32), rows,
                                           width, eps, _stream()), "layernorm_fwd")
     return out_bf16 if out_bf16 is not None else out_f32
@@ -251,11 +271,20 @@ def layernorm_bwd(x, gamma, dy, dgamma, dbeta, eps=1e-5, *, dres=None, dx=None, 
 def attention_fwd(qkv, batch, seq, heads, causal, *, out=None, lse=None):
     """softmax(q k^T / 8 [+ causal mask]) v on the packed in_proj layout qkv [batch*seq, 3*heads*64] (bf16) -> out [batch*seq, heads*64],
     lse [batch, heads, seq] (fp32, natural log).  seq <= 512 with or without the causal mask; 513 .. 1024 tokens without it (the
-    streaming kernels of csrc/attention_long.hip); anything longer, or causal above 512, is UNIIR_ESHAPE."""
+    streaming kernels of csrc/attention_long.hip); anything longer, or causal above 512, is UNIIR_ESHAPE.
+    An fp16 qkv (forward only, the embedding towers) runs uniir_attention_fwd_f16 with the same limits and gives an fp16 out; with
+    the causal mask it is a ValueError (no per-op fp16 forward is causal; the causal fp16 text tower runs from C, csrc/tower.hip)."""
+    half = _dtype16(qkv, out) == DT_F16
+    if half and causal:
+        raise ValueError("fp16 attention is the embedding forward of the per-op towers: no causal mask")
     if out is None:
-        out = torch.empty(batch * seq, heads * 64, device=qkv.device, dtype=torch.bfloat16)
+        out = torch.empty(batch * seq, heads * 64, device=qkv.device, dtype=qkv.dtype)
     if lse is None:
         lse = torch.empty(batch, heads, seq, device=qkv.device, dtype=torch.float32)
+    if half:
+        check(_lib.load().uniir_attention_fwd_f16(_p(qkv), _p(out), _p(lse), None, batch, seq, heads, int(causal), _stream()),
+              "attention_fwd_f16")
+        return out, lse
     check(_lib.load().uniir_attention_fwd(_p(qkv), _p(out), _p(lse), batch, seq, heads, int(causal), _stream()),
           "attention_fwd")
     return out, lse
@@ -327,7 +356,15 @@ def attention_fwd_ex(q, q_ld, k, v, kv_ld, batch, tq, tk, heads, *, key_len=None
     uniir_attention_fwd_rows); kv_packed: K / V are rows of the same numbering (self-attention), else dense [batch][tk].
     tq, tk <= 512; without the causal mask and with dense K / V (kv_packed false) up to 1024 each: max(tq, tk) > 512 runs
     uniir_attention_fwd_long (the streaming kernels of csrc/attention_long.hip), everything at 512 and below the calls it always
-    ran.  Causal or kv_packed above 512 is UNIIR_ESHAPE."""
+    ran.  Causal or kv_packed above 512 is UNIIR_ESHAPE.
+    bf16 only: the general form has no fp16 entry point in the library, so fp16 operands are refused here, before any launch --
+    ValueError for what an fp16 forward never takes (the causal mask, dropout, operands of mixed types), NotImplementedError for
+    the rest."""
+    if torch.float16 in (q.dtype, k.dtype, v.dtype):
+        _dtype16(q, k, v)
+        if causal or drop_p > 0:
+            raise ValueError("fp16 attention is the embedding forward: no causal mask and no dropout in the general form")
+        raise NotImplementedError("the general attention form (uniir_attention_fwd_ex / _rows / _long) has no fp16 entry point")
     nrow = batch * tq if row_off is None else int(rows)
     out = torch.empty(nrow, heads * 64, device=q.device, dtype=torch.bfloat16)
     lse = torch.empty(batch, heads, tq, device=q.device, dtype=torch.float32)

@@ -18,11 +18,12 @@ def clip_block_names(prefix, i):
 class _Blk:
     """one residual block's tensors inside a FlatStore"""
 
-    def __init__(self, store, names):
+    def __init__(self, store, names, dtype16=torch.bfloat16):
         self.st, self.names = store, names
+        self.half = dtype16 == torch.float16          # the 16-bit weights come from the store's fp16 shadow
 
     def w16(self, k):
-        return self.st.w16(self.names[k])
+        return self.st.w16h(self.names[k]) if self.half else self.st.w16(self.names[k])
 
     def p(self, k):
         return self.st.p(self.names[k])
@@ -53,7 +54,9 @@ def block_sublayers(b, x, bufs, g, M, T, W, heads, causal, eps, act, row_scale):
     block_fwd_sublayers in csrc/tower.hip: the stored forward, the recompute forward and the rebuild in tower_bwd call THIS function
     with the same arguments -- same kernels, same shapes, same operand values, deterministic kernels -> the same bits.  The block's
     c_proj GEMM is not part of it: no backward reads a block's output.
-    f None (forward-only pass): the pre-activation is not needed, only act(f) is written (EPI_ACT_ONLY)."""
+    f None (forward-only pass): the pre-activation is not needed, only act(f) is written (EPI_ACT_ONLY).
+    The 16-bit type is that of the buffers and of b's weights (_Blk's dtype16): every op follows its operands (ops.linear_fwd,
+    ops.layernorm_fwd, ops.attention_fwd), so fp16 buffers with an fp16 _Blk run the fp16 forward."""
     qkv, ao, lse, x2, f, h1, h2 = bufs
     R = M * T
     ops.layernorm_fwd(x, b.p("ln1w"), b.p("ln1b"), eps, out_bf16=h1, rows=R, width=W)
@@ -68,26 +71,32 @@ def block_sublayers(b, x, bufs, g, M, T, W, heads, causal, eps, act, row_scale):
 
 
 def tower_fwd(st, names, layers, x, M, T, W, heads, causal, save, eps=1e-5, act=ops.ACT_QUICKGELU, rowscale=None,
-              recompute_from=None):
+              recompute_from=None, dtype16=torch.bfloat16):
     """pre-LN residual blocks (CLIP resblocks; with eps / act / names overridden also the BLIP ViT blocks).
     rowscale fp32 [layers, 2, M]: DropPath factors (0 or 1/keep per item) of the two residual branches of each block
     (BLIP ViT-large in train mode, backbone/vit.py:79-80); None = no DropPath (the residual add stays in the GEMM).
     recompute_from (with save): blocks i >= recompute_from keep only their fp32 input -- their stash entry is (x,) -- and run their
     sublayers into one set of buffers they all share; tower_bwd rebuilds the set from x right before such a block's backward.
-    Blocks below the boundary are stored whole.  None, or any value >= layers: every block is stored."""
+    Blocks below the boundary are stored whole.  None, or any value >= layers: every block is stored.
+    dtype16 = torch.float16 (forward only, save False): 16-bit activations in fp16, weights from the store's fp16 shadow; the residual
+    stream, LayerNorm statistics and accumulation stay fp32.  There is no fp16 backward: with save it raises."""
+    if dtype16 not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"dtype16 is torch.bfloat16 or torch.float16, not {dtype16!r}")
+    if save and dtype16 == torch.float16:
+        raise RuntimeError("the fp16 tower forward keeps nothing for a backward (save=True needs dtype16=torch.bfloat16)")
     R = M * T
     dev = x.device
-    h = torch.empty(R, W, device=dev, dtype=torch.bfloat16)
-    g = torch.empty(R, 4 * W, device=dev, dtype=torch.bfloat16)
+    h = torch.empty(R, W, device=dev, dtype=dtype16)
+    g = torch.empty(R, 4 * W, device=dev, dtype=dtype16)
     saved = []
     # DropPath factors per ROW (item factor repeated over its T tokens): applied inside the residual GEMM's epilogue
     rs_rows = None if rowscale is None else rowscale.repeat_interleave(T, dim=2).contiguous()
     first_rc = layers if (recompute_from is None or not save) else max(int(recompute_from), 0)
     shared = None        # the one set of the recomputed blocks
     for i in range(layers):
-        b = _Blk(st, names(i))
+        b = _Blk(st, names(i), dtype16)
         if not save:      # forward only: both LayerNorm outputs pass through h, no pre-activation f
-            bufs = (torch.empty(R, 3 * W, device=dev, dtype=torch.bfloat16), None, None,
+            bufs = (torch.empty(R, 3 * W, device=dev, dtype=dtype16), None, None,
                     torch.empty(R, W, device=dev, dtype=torch.float32), None, h, h)
         elif i >= first_rc:
             if shared is None:
