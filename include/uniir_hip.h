@@ -178,8 +178,9 @@ int uniir_layernorm_bwd_ex(const float* x, int64_t x_stride, const float* gamma,
  *                                                at the coordinates of the full call (the class row of BLIP's last BERT layer)
  *   Still 512 at most: the causal mask, fully packed rows (_packed, _rows with kv_packed).
  *   On fp16 tensors (forward only): uniir_attention_fwd_f16 with the limits of uniir_attention_fwd / _fwd_packed (causal = 0 and
- *   dense rows: seq <= 1024, the BLIP ViT at 384 pixels; else 512) and uniir_attention_one_fwd with f16 = 1.  The general form
- *   (_ex, _rows, _long) has no fp16 entry point.
+ *   dense rows: seq <= 1024, the BLIP ViT at 384 pixels; else 512), uniir_attention_one_fwd with f16 = 1, and the general form
+ *   (_ex, _rows, _long without the causal mask and dropout) as uniir_attn_general_fwd_f16 with its one-query form
+ *   uniir_onequery_fwd_f16: the BLIP MED BERT's eval-mode forward.  There is no fp16 backward.
  * qkv bf16 [batch*seq][3*heads*64] as produced by nn.MultiheadAttention.in_proj ([q | k | v] per row);
  * out bf16 [batch*seq][heads*64]; lse f32 [batch][heads][seq] (natural log-sum-exp of scaled scores).
  * causal = 1 applies CLIP's build_attention_mask (key <= query).
@@ -305,6 +306,28 @@ int uniir_onequery_bwd(const void* q, int64_t q_ld, const void* k, const void* v
                        int64_t out_ld, const float* lse, const int32_t* key_len, const int32_t* kv_row_off, void* dq, int64_t dq_ld,
                        void* dk, void* dv, int64_t dkv_ld, int32_t batch, int32_t tk, int32_t heads, float drop_p, uint32_t drop_seed,
                        int32_t drop_tq, int32_t drop_q, void* stream);
+/* The general form ON FP16 TENSORS, forward only (q / k / v / out fp16, lse f32 [batch][heads][tq]; head_dim 64, scale 1/8, no causal
+ * mask, no dropout): the eval-mode embedding forward of the BLIP MED BERT under use_fp16.  One call for what uniir_attention_fwd_ex,
+ * _fwd_rows and _fwd_long are in bf16: q_row_off == NULL: dense [batch][tq] query rows; q_row_off != NULL: packed query rows, with
+ * kv_packed != 0 K / V in the same packed numbering (self-attention: key_len NULL, tq == tk), with kv_packed == 0 K / V dense
+ * [batch][tk] and key_len optional.  q_row_off, kv_packed and key_len mean what they mean there: every item has at least one row,
+ * key_len[m] >= 1, lse entries of rows an item does not have are not written, a packed call's live rows are bitwise the dense call's.
+ * Kernels: max(tq, tk) <= 512 the resident kernel of uniir_attention_fwd_f16 (with tq == tk, no key_len and the thirds of one packed
+ * [q | k | v] buffer the two give the same bits); above it, with kv_packed == 0, the streaming kernel of uniir_attention_fwd_long on
+ * fp16 operands (128 query rows per workgroup, K / V in 128-key chunks).
+ * The checks, in this order: (1) UNIIR_EINVAL: a NULL q, k, v, out or lse, heads <= 0, batch < 0; (2) UNIIR_EINVAL: kv_packed != 0 with
+ * a NULL q_row_off, a non-NULL key_len or tq != tk; (3) batch == 0 is UNIIR_OK; (4) UNIIR_ESHAPE: tq or tk outside 1 .. 1024, or
+ * kv_packed != 0 with tq > 512; (5) UNIIR_EALIGN: a leading dimension that is no multiple of 8, then a pointer among q, k, v, out
+ * that is not 16-byte aligned.  A refused call writes nothing. */
+int uniir_attn_general_fwd_f16(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, void* out, int64_t out_ld,
+                               float* lse, const int32_t* q_row_off, int32_t kv_packed, const int32_t* key_len, int32_t batch,
+                               int32_t tq, int32_t tk, int32_t heads, void* stream);
+/* uniir_onequery_fwd on fp16 tensors, without its four dropout arguments and with its check order otherwise (both key forms:
+ * UNIIR_EINVAL, before batch == 0 and the sizes).  The two kernels of uniir_attn_general_fwd_f16 at one query row -- packed keys above
+ * 512 take the streaming kernel, as in the bf16 twin -- so out and lse are bitwise row 0 of that call on the same operands. */
+int uniir_onequery_fwd_f16(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, void* out, int64_t out_ld,
+                           float* lse, const int32_t* key_len, const int32_t* kv_row_off, int32_t batch, int32_t tk, int32_t heads,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * [ENC] small fused pieces of the towers.

@@ -128,6 +128,8 @@ SIGNATURES = {
     "uniir_onequery_fwd": (c_int, [P, c_i64, P, P, c_i64, P, c_i64, P, P, P, c_int, c_int, c_int, c_float, C.c_uint32, c_int, c_int, S]),
     "uniir_onequery_bwd": (c_int, [P, c_i64, P, P, c_i64, P, P, c_i64, P, P, P, P, c_i64, P, P, c_i64, c_int, c_int, c_int, c_float,
                                    C.c_uint32, c_int, c_int, S]),
+    "uniir_attn_general_fwd_f16": (c_int, [P, c_i64, P, P, c_i64, P, c_i64, P, P, c_int, P, c_int, c_int, c_int, c_int, S]),
+    "uniir_onequery_fwd_f16": (c_int, [P, c_i64, P, P, c_i64, P, c_i64, P, P, P, c_int, c_int, c_int, S]),
     "uniir_patchify": (c_int, [P, P, c_int, c_int, c_int, c_int, S]),
     "uniir_vit_assemble": (c_int, [P, P, P, P, c_int, c_int, c_int, S]),
     "uniir_patchify_f16": (c_int, [P, P, c_int, c_int, c_int, c_int, S]),

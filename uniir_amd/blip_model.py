@@ -7,7 +7,8 @@ idx_queue / new_ptr_queue`, forward(batch, alpha, encode_mbeir_batch)).
 All arithmetic is in libuniir_hip.so; this file is the launch sequence, the flat parameter stores and the activation
 stash.  Differences from the reference, stated once:
   * bf16 MFMA GEMMs with fp32 accumulation / fp32 LayerNorm, softmax statistics, residual stream, loss (the reference
-    runs fp16 autocast); no GradScaler is needed;
+    runs fp16 autocast); no GradScaler is needed; the eval-mode embedding forward alone also runs on fp16 operands
+    (BLIPFeatureFusion.precision = "fp16", the reference embedder's autocast);
   * train mode applies the reference's dropout sites -- BERT hidden / attention-probability dropout 0.1 (med.py:84,
     175,198,212,341; online and momentum encoders alike, both are in train mode) and DropPath of ViT-large (vit.py:79-80,
     blip.py:249-254) -- with counter-based masks regenerated in backward (ops.DropSeeds); the masks are a different random
@@ -169,10 +170,11 @@ def vit_backward(st, dconv, prefix, cfg, dtok, stash):
     ops.call("uniir_unpad_add", dconv, st.grad_view(prefix + "patch_embed.proj.weight"), D, 3 * P * P, dconv.shape[1])
 
 
-def _ln2(st, x, wname, eps, R, W):
-    """post-LN sublayer output in both precisions: fp32 for the next residual, bf16 for the next GEMM"""
+def _ln2(st, x, wname, eps, R, W, dtype16=torch.bfloat16):
+    """post-LN sublayer output in both precisions: fp32 for the next residual, bf16 (fp16 with dtype16 = torch.float16, through
+    uniir_layernorm_fwd_f16) for the next GEMM"""
     o32 = torch.empty(R, W, device=x.device, dtype=torch.float32)
-    o16 = torch.empty(R, W, device=x.device, dtype=torch.bfloat16)
+    o16 = torch.empty(R, W, device=x.device, dtype=dtype16)
     ops.layernorm_fwd(x, st.p(wname + "weight"), st.p(wname + "bias"), eps, out_bf16=o16, out_f32=o32, rows=R, width=W)
     return o32, o16
 
@@ -210,7 +212,7 @@ class TextPack:
 
 
 def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, pool=True, drop=None, pack=None, pool_last=False,
-                 log=None):
+                 log=None, dtype16=torch.bfloat16):
     """src/models/uniir_blip/backbone/med.py BertModel.forward(mode="multimodal") -> pooler_output fp32 [M,W] + stash.
     ids int32 [M,L]; key_len int32 [M]; img16 bf16 [M*Ti, enc_width] (image attention mask all ones, blip_ff.py:98,108).
     cross=False: mode "text" (the cross-attention sublayer is skipped, BLIP_SF); pool=False: add_pooling_layer=False, the
@@ -221,10 +223,24 @@ def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, poo
     parameter gradients equal up to the order of the fp32 additions in the weight-gradient reductions.
     pool_last (BLIPFeatureFusion.pool_last_layer): only the class row of every item leaves the encoder, so the LAST layer runs on
     those M rows (_bert_last_layer_pooled): the same class row bit for bit, train mode included.  log: a list that gets a line
-    when it does."""
+    when it does.
+    dtype16 = torch.float16 (forward only and eval only: save False, drop None; img16 fp16, or None for mode "text"): every weight
+    comes from st's fp16 shadow (FlatStore.w16h, the spanning q | k | v and cross k | v shapes included), the 16-bit activations are
+    fp16 and both attentions run the fp16 general form (ops.attention_fwd_ex_f16 / ops.onequery_fwd_f16); the residual stream, the
+    LayerNorm statistics, tanh and the gathered class rows stay fp32, as in vit_forward.  pack and pool_last are honoured, each bit for
+    bit the unpacked / full-layer result.  A bf16 caller makes exactly the calls it made before this argument existed."""
     W, I, eps = cfg["hidden_size"], cfg["intermediate_size"], cfg["layer_norm_eps"]
     heads, layers = cfg["num_attention_heads"], cfg["num_hidden_layers"]
     M, L = ids.shape
+    if dtype16 not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"dtype16 is torch.bfloat16 or torch.float16, not {dtype16!r}")
+    half = dtype16 == torch.float16
+    if half and (save or drop is not None):
+        raise RuntimeError("the fp16 BERT forward is the eval-mode embedding forward: it keeps nothing for a backward and takes no "
+                           "dropout (save=True and drop need dtype16=torch.bfloat16)")
+    if half and img16 is not None and img16.dtype != torch.float16:
+        raise ValueError(f"bert_forward: {img16.dtype} image tokens with dtype16 = {dtype16}")
+    w16 = st.w16h if half else st.w16
     R, dev = (pack.R if pack is not None else M * L), ids.device
     roff = pack.row_off if pack is not None else None
     rmap = pack.row_map if pack is not None else None
@@ -236,7 +252,7 @@ def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, poo
     else:
         ops.call("uniir_text_embed_packed", ids, st.p(prefix + "embeddings.word_embeddings.weight"),
                  st.p(prefix + "embeddings.position_embeddings.weight"), roff, e32, None, M, L, W, cfg["vocab_size"])
-    h32, h16 = _ln2(st, e32, prefix + "embeddings.LayerNorm.", eps, R, W)
+    h32, h16 = _ln2(st, e32, prefix + "embeddings.LayerNorm.", eps, R, W, dtype16)
     ph = cfg.get("hidden_dropout_prob", 0.0) if drop is not None else 0.0
     pa = cfg.get("attention_probs_dropout_prob", 0.0) if drop is not None else 0.0
     s_emb = drop.next() if ph else 0
@@ -251,44 +267,51 @@ def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, poo
     def out_dense(x16, name, resid, row_map=rmap):
         """dense -> dropout -> + residual (BertSelfOutput / BertOutput, med.py:196-200,339-343), pre-LayerNorm sum"""
         if not ph:
-            return ops.linear_fwd(x16, st.w16(name + "weight"), st.p(name + "bias"), epilogue=ops.EPI_RESID_F32,
+            return ops.linear_fwd(x16, w16(name + "weight"), st.p(name + "bias"), epilogue=ops.EPI_RESID_F32,
                                   resid=resid), 0
-        t = ops.linear_fwd(x16, st.w16(name + "weight"), st.p(name + "bias"), epilogue=ops.EPI_RESID_F32)
+        t = ops.linear_fwd(x16, w16(name + "weight"), st.p(name + "bias"), epilogue=ops.EPI_RESID_F32)
         sd = drop.next()
         ops.dropout_f32(t, ph, sd, resid=resid, out_f32=t, row_map=row_map)
         return t, sd
 
-    g = torch.empty(R, I, device=dev, dtype=torch.bfloat16) if not (pool_last and layers == 1) else None
+    g = torch.empty(R, I, device=dev, dtype=dtype16) if not (pool_last and layers == 1) else None
     for i in range(layers - 1 if pool_last else layers):
         b = f"{prefix}encoder.layer.{i}."
         s, c = b + "attention.self.", b + "crossattention.self."
-        qkv = ops.linear_fwd(h16, st.w16(s + "query.weight", (3 * W, W)), st.p(s + "query.bias", (3 * W,)))
+        qkv = ops.linear_fwd(h16, w16(s + "query.weight", (3 * W, W)), st.p(s + "query.bias", (3 * W,)))
         sa1 = drop.next() if pa else 0
-        ao, lse1 = ops.attention_fwd_ex(qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, M, L, L, heads, drop_p=pa, drop_seed=sa1,
-                                        **self_kw)
+        if half:
+            ao, lse1 = ops.attention_fwd_ex_f16(qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, M, L, L, heads, **self_kw)
+        else:
+            ao, lse1 = ops.attention_fwd_ex(qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, M, L, L, heads, drop_p=pa, drop_seed=sa1,
+                                            **self_kw)
         t1, so1 = out_dense(ao, b + "attention.output.dense.", h32)
-        a32, a16 = _ln2(st, t1, b + "attention.output.LayerNorm.", eps, R, W)
+        a32, a16 = _ln2(st, t1, b + "attention.output.LayerNorm.", eps, R, W, dtype16)
         cq = ckv = co = lse2 = t2 = None
         sa2 = so2 = 0
         if cross:
-            cq = ops.linear_fwd(a16, st.w16(c + "query.weight"), st.p(c + "query.bias"))
-            ckv = ops.linear_fwd(img16, st.w16(c + "key.weight", (2 * W, img16.shape[1])), st.p(c + "key.bias", (2 * W,)))
+            cq = ops.linear_fwd(a16, w16(c + "query.weight"), st.p(c + "query.bias"))
+            ckv = ops.linear_fwd(img16, w16(c + "key.weight", (2 * W, img16.shape[1])), st.p(c + "key.bias", (2 * W,)))
             sa2 = drop.next() if pa else 0
-            co, lse2 = ops.attention_fwd_ex(cq, W, ckv, ckv[:, W:], 2 * W, M, L, Ti, heads, drop_p=pa, drop_seed=sa2, **cross_kw)
+            if half:
+                co, lse2 = ops.attention_fwd_ex_f16(cq, W, ckv, ckv[:, W:], 2 * W, M, L, Ti, heads, **cross_kw)
+            else:
+                co, lse2 = ops.attention_fwd_ex(cq, W, ckv, ckv[:, W:], 2 * W, M, L, Ti, heads, drop_p=pa, drop_seed=sa2, **cross_kw)
             t2, so2 = out_dense(co, b + "crossattention.output.dense.", a32)
-            c32, c16 = _ln2(st, t2, b + "crossattention.output.LayerNorm.", eps, R, W)
+            c32, c16 = _ln2(st, t2, b + "crossattention.output.LayerNorm.", eps, R, W, dtype16)
         else:
             c32, c16 = a32, a16
-        f = torch.empty(R, I, device=dev, dtype=torch.bfloat16)
-        ops.linear_fwd(c16, st.w16(b + "intermediate.dense.weight"), st.p(b + "intermediate.dense.bias"), out=f,
+        f = torch.empty(R, I, device=dev, dtype=dtype16)
+        ops.linear_fwd(c16, w16(b + "intermediate.dense.weight"), st.p(b + "intermediate.dense.bias"), out=f,
                        epilogue=ops.EPI_BIAS_ACT, C2=g, act=ops.ACT_GELU_ERF)
         t3, so3 = out_dense(g, b + "output.dense.", c32)
         if save:
             stash["layers"].append(dict(h16=h16, qkv=qkv, ao=ao, lse1=lse1, t1=t1, a16=a16, cq=cq, ckv=ckv, co=co,
                                         lse2=lse2, t2=t2, c16=c16, f=f, t3=t3, seeds=(sa1, so1, sa2, so2, so3)))
-        h32, h16 = _ln2(st, t3, b + "output.LayerNorm.", eps, R, W)
+        h32, h16 = _ln2(st, t3, b + "output.LayerNorm.", eps, R, W, dtype16)
     if pool_last:
-        rows, sv = _bert_last_layer_pooled(st, prefix, cfg, h32, h16, key_len, img16, Ti, M, L, R, cross, drop, ph, pa, pack, out_dense)
+        rows, sv = _bert_last_layer_pooled(st, prefix, cfg, h32, h16, key_len, img16, Ti, M, L, R, cross, drop, ph, pa, pack, out_dense,
+                                           dtype16)
         if save:
             stash["layers"].append(sv)
         if log is not None:
@@ -303,9 +326,9 @@ def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, poo
             ops.call("uniir_gather_rows", h32, roff, rows, M, 0, W)          # the class token = the first row of every item
     if not pool:
         return rows, stash
-    rows16 = torch.empty(M, W, device=dev, dtype=torch.bfloat16)
-    ops.call("uniir_cast_f32_to_bf16", rows, rows16, rows.numel())
-    pre = ops.linear_fwd(rows16, st.w16(prefix + "pooler.dense.weight"), st.p(prefix + "pooler.dense.bias"),
+    rows16 = torch.empty(M, W, device=dev, dtype=dtype16)
+    ops.call("uniir_cast_f32_to_f16" if half else "uniir_cast_f32_to_bf16", rows, rows16, rows.numel())
+    pre = ops.linear_fwd(rows16, w16(prefix + "pooler.dense.weight"), st.p(prefix + "pooler.dense.bias"),
                          epilogue=ops.EPI_RESID_F32)
     pooled = torch.empty_like(pre)
     ops.call("uniir_tanh_fwd", pre, pooled, pre.numel())
@@ -321,7 +344,8 @@ def _class_rows(pack, M, L, dev):
     return (cmap.long() if pack is None else pack.row_off[:M].long()), cmap
 
 
-def _bert_last_layer_pooled(st, prefix, cfg, h32, h16, key_len, img16, Ti, M, L, R, cross, drop, ph, pa, pack, out_dense):
+def _bert_last_layer_pooled(st, prefix, cfg, h32, h16, key_len, img16, Ti, M, L, R, cross, drop, ph, pa, pack, out_dense,
+                            dtype16=torch.bfloat16):
     """The last BERT layer when only the class row of every item leaves the encoder (blip_ff.py:82-116 reads pooler_output,
     blip_sf.py the class token): what that row needs from the other rows is their KEYS AND VALUES, so the q | k | v projection still
     runs on all R rows -- the same GEMM as in the full layer, so K | V have its bits, a dense BERT passes row m * L of that buffer as
@@ -329,41 +353,51 @@ def _bert_last_layer_pooled(st, prefix, cfg, h32, h16, key_len, img16, Ti, M, L,
     the M class rows: the one-query self-attention (ops.onequery_fwd with key_len or the packed rows), attention.output.dense +
     LayerNorm, the cross query, the one-query cross-attention over the Ti image tokens, its output dense + LayerNorm, the FFN and
     output.LayerNorm.  The dropout seeds are drawn in the full layer's order; attention dropout sits at the coordinates of query 0 of
-    L (drop_tq = L, drop_q = 0), hidden dropout at the dense rows m * L (row_map).  -> the class rows fp32 [M, W], the layer's stash."""
+    L (drop_tq = L, drop_q = 0), hidden dropout at the dense rows m * L (row_map).  -> the class rows fp32 [M, W], the layer's stash.
+    dtype16 = torch.float16: bert_forward's fp16 forward (no dropout; out_dense is its closure over the fp16 shadow): the one-query
+    attentions are ops.onequery_fwd_f16."""
     W, I, eps = cfg["hidden_size"], cfg["intermediate_size"], cfg["layer_norm_eps"]
     heads, i = cfg["num_attention_heads"], cfg["num_hidden_layers"] - 1
     dev = h32.device
+    half = dtype16 == torch.float16
+    w16 = st.w16h if half else st.w16
     b = f"{prefix}encoder.layer.{i}."
     s, c = b + "attention.self.", b + "crossattention.self."
     cls, cmap = _class_rows(pack, M, L, dev)
-    qkv = ops.linear_fwd(h16, st.w16(s + "query.weight", (3 * W, W)), st.p(s + "query.bias", (3 * W,)))
+    qkv = ops.linear_fwd(h16, w16(s + "query.weight", (3 * W, W)), st.p(s + "query.bias", (3 * W,)))
     sa1 = drop.next() if pa else 0
     if pack is None:
         q, q_ld, kw = qkv, L * 3 * W, dict(key_len=key_len)
     else:
         q, q_ld, kw = qkv[cls, :W], W, dict(kv_row_off=pack.row_off)          # a copy of M rows
-    ao, lse1 = ops.onequery_fwd(q, q_ld, qkv[:, W:], qkv[:, 2 * W:], 3 * W, M, L, heads, drop_p=pa, drop_seed=sa1, drop_tq=L, drop_q=0, **kw)
+    if half:
+        ao, lse1 = ops.onequery_fwd_f16(q, q_ld, qkv[:, W:], qkv[:, 2 * W:], 3 * W, M, L, heads, **kw)
+    else:
+        ao, lse1 = ops.onequery_fwd(q, q_ld, qkv[:, W:], qkv[:, 2 * W:], 3 * W, M, L, heads, drop_p=pa, drop_seed=sa1, drop_tq=L, drop_q=0, **kw)
     h32c = torch.empty(M, W, device=dev, dtype=torch.float32)
     ops.call("uniir_gather_rows", h32, None if pack is None else pack.row_off, h32c, M, L if pack is None else 0, W)
     t1, so1 = out_dense(ao, b + "attention.output.dense.", h32c, cmap)
-    a32, a16 = _ln2(st, t1, b + "attention.output.LayerNorm.", eps, M, W)
+    a32, a16 = _ln2(st, t1, b + "attention.output.LayerNorm.", eps, M, W, dtype16)
     cq = ckv = co = lse2 = t2 = None
     sa2 = so2 = 0
     if cross:
-        cq = ops.linear_fwd(a16, st.w16(c + "query.weight"), st.p(c + "query.bias"))
-        ckv = ops.linear_fwd(img16, st.w16(c + "key.weight", (2 * W, img16.shape[1])), st.p(c + "key.bias", (2 * W,)))
+        cq = ops.linear_fwd(a16, w16(c + "query.weight"), st.p(c + "query.bias"))
+        ckv = ops.linear_fwd(img16, w16(c + "key.weight", (2 * W, img16.shape[1])), st.p(c + "key.bias", (2 * W,)))
         sa2 = drop.next() if pa else 0
-        co, lse2 = ops.onequery_fwd(cq, W, ckv, ckv[:, W:], 2 * W, M, Ti, heads, drop_p=pa, drop_seed=sa2, drop_tq=L, drop_q=0)
+        if half:
+            co, lse2 = ops.onequery_fwd_f16(cq, W, ckv, ckv[:, W:], 2 * W, M, Ti, heads)
+        else:
+            co, lse2 = ops.onequery_fwd(cq, W, ckv, ckv[:, W:], 2 * W, M, Ti, heads, drop_p=pa, drop_seed=sa2, drop_tq=L, drop_q=0)
         t2, so2 = out_dense(co, b + "crossattention.output.dense.", a32, cmap)
-        c32, c16 = _ln2(st, t2, b + "crossattention.output.LayerNorm.", eps, M, W)
+        c32, c16 = _ln2(st, t2, b + "crossattention.output.LayerNorm.", eps, M, W, dtype16)
     else:
         c32, c16 = a32, a16
-    f = torch.empty(M, I, device=dev, dtype=torch.bfloat16)
-    g = torch.empty(M, I, device=dev, dtype=torch.bfloat16)
-    ops.linear_fwd(c16, st.w16(b + "intermediate.dense.weight"), st.p(b + "intermediate.dense.bias"), out=f,
+    f = torch.empty(M, I, device=dev, dtype=dtype16)
+    g = torch.empty(M, I, device=dev, dtype=dtype16)
+    ops.linear_fwd(c16, w16(b + "intermediate.dense.weight"), st.p(b + "intermediate.dense.bias"), out=f,
                    epilogue=ops.EPI_BIAS_ACT, C2=g, act=ops.ACT_GELU_ERF)
     t3, so3 = out_dense(g, b + "output.dense.", c32, cmap)
-    rows, _ = _ln2(st, t3, b + "output.LayerNorm.", eps, M, W)
+    rows, _ = _ln2(st, t3, b + "output.LayerNorm.", eps, M, W, dtype16)
     sv = dict(pooled=True, h16=h16, qkv=qkv, q=q, q_ld=q_ld, ao=ao, lse1=lse1, t1=t1, a16=a16, cq=cq, ckv=ckv, co=co, lse2=lse2, t2=t2,
               c16=c16, f=f, t3=t3, seeds=(sa1, so1, sa2, so2, so3))
     return rows, sv
@@ -790,6 +824,14 @@ class BLIPFeatureFusion(nn.Module):
         # fewer rows.  Off by default (profiles/blip_pooled_last_layer.txt has the measurement): UNIIR_BLIP_POOL_LAST_LAYER=1
         # switches it on at construction.  A plain attribute: may be changed between steps; must be the same on every rank.
         self.pool_last_layer = os.environ.get("UNIIR_BLIP_POOL_LAST_LAYER", "0") not in ("", "0")
+        # The 16-bit type of the embedding forward: "bf16" (the training kernels), or "fp16": encode_multimodal_input -- and with it
+        # encode_mbeir_batch and forward(encode_mbeir_batch=True) -- runs ViT and BERT (and BLIP_SF's projections) on fp16 activations
+        # from the online store's fp16 shadow, under no_grad, and returns fp32 embeddings as always: the reference embedder's
+        # autocast(fp16), 1e-3 from the fp32 oracle instead of bf16's 6e-3.  Eval mode and the online encoder only.  A plain attribute.
+        self.precision = "bf16"
+        # Whether the embedder's use_fp16 switches precision to "fp16" for an extraction (src/common/mbeir_embedder.py
+        # _tower_precision).  Off by default, so that no existing run changes: UNIIR_BLIP_EMBED_FP16=1 switches it on at construction.
+        self.embed_fp16 = os.environ.get("UNIIR_BLIP_EMBED_FP16", "0") not in ("", "0")
         self.path_log = []                # one line per BERT pass whose last layer ran on the class rows (the newest 64)
 
     def _path_log(self):
@@ -981,12 +1023,36 @@ class BLIPFeatureFusion(nn.Module):
                                 dtype16=dt)
         return tok.view(image_batched.shape[0], T, -1)
 
+    def _embed_half(self, use_momentum):
+        """whether this encode call is the fp16 embedding forward (precision == "fp16"); what that path cannot serve raises"""
+        if self.precision not in ("bf16", "fp16"):
+            raise RuntimeError(f"unknown precision {self.precision!r}")
+        if self.precision == "bf16":
+            return False
+        if self.training:
+            raise RuntimeError("precision='fp16' is a forward-only embedding path; call model.eval() first or use precision='bf16'")
+        if use_momentum:
+            raise RuntimeError("precision='fp16' is the online encoder's embedding path: the fp16 shadow exists for the online store "
+                               "only (use_momentum=True needs precision='bf16')")
+        return True
+
     def encode_multimodal_input(self, txt_dict_batched, image_batched, txt_mask=None, img_mask=None, use_momentum=False):
         """blip_ff.py:82-116: BERT(text) cross-attending to ViT(image) tokens -> pooler_output [n, embed_dim]"""
-        self._sync()
+        half = self._embed_half(use_momentum)
+        if half:
+            self._sync_half()          # _sync() plus the fp16 copies
+        else:
+            self._sync()
         ids, key_len = self._text_inputs(txt_dict_batched)
         pack = self._text_pack(txt_dict_batched, key_len, ids.shape[1])
         self.last_text_rows = (pack.R if pack is not None else ids.numel(), ids.numel())
+        if half:
+            with torch.no_grad():
+                st = self._online
+                tok, Ti, _ = vit_forward(st, self._conv16h, "visual_encoder.", self.vit_cfg, self.image_size, image_batched, False,
+                                         dtype16=torch.float16)
+                return bert_forward(st, "text_encoder.", self.med_cfg, ids, key_len, tok, Ti, False, pack=pack,
+                                    pool_last=self.pool_last_layer, log=self._path_log(), dtype16=torch.float16)[0]
         if use_momentum:
             with torch.no_grad():
                 drop = self._drop_seeds()
@@ -1112,27 +1178,35 @@ class BLIPScoreFusion(BLIPFeatureFusion):
     parameters exist but are frozen (:66-69) and unused (mode "text")."""
     SCORE_FUSION = True
 
-    def _encode_sf(self, st, conv16, ids, key_len, images, tmask, imask, save, pack=None):
+    def _encode_sf(self, st, conv16, ids, key_len, images, tmask, imask, save, pack=None, dtype16=torch.bfloat16):
+        """dtype16 = torch.float16 (the fp16 embedding forward: save False, eval mode, conv16 the fp16 patch weight): ViT, BERT and
+        the two projections on fp16 operands from st's fp16 shadow"""
         dev = ids.device
         M = ids.shape[0]
         E = self.embed_dim
-        drop = self._drop_seeds()
+        half = dtype16 == torch.float16
+        w16 = st.w16h if half else st.w16
+        drop = None if half else self._drop_seeds()
         tok, T, vst = vit_forward(st, conv16, "visual_encoder.", self.vit_cfg, self.image_size, images, save, drop=drop,
-                                  recompute_from=self._vit_boundary(save))
+                                  recompute_from=self._vit_boundary(save), dtype16=dtype16)
         ifeat16 = tok.view(M, T, -1)[:, 0].contiguous()                     # class-token rows (a copy)
         tfeat, bst = bert_forward(st, "text_encoder.", self.med_cfg, ids, key_len, None, 0, save, cross=False, pool=False,
-                                  drop=drop, pack=pack, pool_last=self.pool_last_layer, log=self._path_log())
-        tfeat16 = torch.empty(M, tfeat.shape[1], device=dev, dtype=torch.bfloat16)
-        ops.call("uniir_cast_f32_to_bf16", tfeat, tfeat16, tfeat.numel())
-        temb = ops.linear_fwd(tfeat16, st.w16("text_proj.weight"), st.p("text_proj.bias"), epilogue=ops.EPI_RESID_F32)
-        iemb = ops.linear_fwd(ifeat16, st.w16("vision_proj.weight"), st.p("vision_proj.bias"), epilogue=ops.EPI_RESID_F32)
+                                  drop=drop, pack=pack, pool_last=self.pool_last_layer, log=self._path_log(), dtype16=dtype16)
+        tfeat16 = torch.empty(M, tfeat.shape[1], device=dev, dtype=dtype16)
+        ops.call("uniir_cast_f32_to_f16" if half else "uniir_cast_f32_to_bf16", tfeat, tfeat16, tfeat.numel())
+        temb = ops.linear_fwd(tfeat16, w16("text_proj.weight"), st.p("text_proj.bias"), epilogue=ops.EPI_RESID_F32)
+        iemb = ops.linear_fwd(ifeat16, w16("vision_proj.weight"), st.p("vision_proj.bias"), epilogue=ops.EPI_RESID_F32)
         emb = torch.empty(M, E, device=dev, dtype=torch.float32)
         ops.call("uniir_fuse_embeddings", temb, iemb, tmask, imask, emb, M, E)
         stash = dict(vst=vst, bst=bst, T=T, tfeat16=tfeat16, ifeat16=ifeat16, tmask=tmask, imask=imask) if save else None
         return emb, stash
 
     def encode_multimodal_input(self, txt_dict_batched, image_batched, txt_mask=None, img_mask=None, use_momentum=False):
-        self._sync()
+        half = self._embed_half(use_momentum)
+        if half:
+            self._sync_half()          # _sync() plus the fp16 copies
+        else:
+            self._sync()
         ids, key_len = self._text_inputs(txt_dict_batched)
         pack = self._text_pack(txt_dict_batched, key_len, ids.shape[1])
         self.last_text_rows = (pack.R if pack is not None else ids.numel(), ids.numel())
@@ -1141,6 +1215,9 @@ class BLIPScoreFusion(BLIPFeatureFusion):
         ones = torch.ones(M, dtype=torch.int64, device=dev)
         tmask = ones if txt_mask is None else txt_mask.to(dev).to(torch.int64).contiguous()
         imask = ones if img_mask is None else img_mask.to(dev).to(torch.int64).contiguous()
+        if half:
+            with torch.no_grad():
+                return self._encode_sf(self._online, self._conv16h, ids, key_len, image_batched, tmask, imask, False, pack, torch.float16)[0]
         if use_momentum:
             with torch.no_grad():
                 return self._encode_sf(self._mom, self._conv16_m, ids, key_len, image_batched, tmask, imask, False, pack)[0]

@@ -242,7 +242,8 @@ int launch_attn_long_bwd(const AttnArgs& a, int batch, hipStream_t st);
 // attention_one.hip: the backward of ONE dense query row per (item, head) against 1 .. ATT_LONG_SEQ_MAX dense keys in one pass over K and V
 int launch_attn_one_bwd(const AttnArgs& a, int batch, hipStream_t st);
 // attention_long.hip: the streaming forward of the general form (attn_xlong_fwd_kernel) for uniir_onequery_fwd above ATT_SEQ_MAX keys
-int launch_attn_xlong_fwd(const AttnArgs& a, int batch, hipStream_t st);
+// and for the fp16 general form (f16: uniir_attn_general_fwd_f16 / uniir_onequery_fwd_f16, no dropout)
+int launch_attn_xlong_fwd(const AttnArgs& a, int batch, hipStream_t st, bool f16 = false);
 
 // what tower.hip calls (attention.hip).  The forward: row_off = nullptr for dense rows; f16 = the 16-bit tensors are fp16
 int attention_fwd_impl(const void* qkv, void* out, float* lse, const int32_t* row_off, int32_t batch, int32_t seq, int32_t heads,

@@ -744,6 +744,42 @@ extern "C" int uniir_attention_bwd_rows(const void* q, int64_t q_ld, const void*
     return launch_attn_bwd(a, batch, (hipStream_t)stream);
 }
 
+// ---------------- the general form on fp16 tensors, forward only ----------------
+// uniir_attention_fwd_ex (causal = 0), _fwd_rows and _fwd_long in one call, without dropout: the eval-mode forward of the BLIP MED BERT
+// under fp16.  Up to ATT_SEQ_MAX x ATT_SEQ_MAX the resident attn_fwd_kernel<false, false, true> (the kernel of uniir_attention_fwd_f16),
+// above it -- dense K / V only -- the streaming attn_xlong_fwd_kernel<false, true>.  The argument misuse of kv_packed is tested before
+// batch == 0, the sizes after it.
+extern "C" int uniir_attn_general_fwd_f16(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, void* out,
+                                          int64_t out_ld, float* lse, const int32_t* q_row_off, int32_t kv_packed,
+                                          const int32_t* key_len, int32_t batch, int32_t tq, int32_t tk, int32_t heads, void* stream) {
+    if (att_null(q, k, v, out, lse) || heads <= 0 || batch < 0) return UNIIR_EINVAL;
+    if (kv_packed && (!q_row_off || key_len || tq != tk)) return UNIIR_EINVAL;
+    if (batch == 0) return UNIIR_OK;
+    if (tq < 1 || tk < 1 || tq > ATT_LONG_SEQ_MAX || tk > ATT_LONG_SEQ_MAX || (kv_packed && tq > ATT_SEQ_MAX)) return UNIIR_ESHAPE;
+    if (att_ld_not8(q_ld, kv_ld, out_ld)) return UNIIR_EALIGN;
+    if (att_misaligned16(q, k, v, out)) return UNIIR_EALIGN;
+    AttnArgs a = att_args_qkv(q, q_ld, k, v, kv_ld, out, out_ld, lse, tq, tk, heads, key_len);
+    if (q_row_off) att_args_q_rows(a, q_row_off, kv_packed ? 0 : 1);
+    if (tq > ATT_SEQ_MAX || tk > ATT_SEQ_MAX) return launch_attn_xlong_fwd(a, batch, (hipStream_t)stream, true);
+    return launch_attn_fwd(a, batch, (hipStream_t)stream, true);
+}
+// ... and its one-query form: uniir_onequery_fwd without dropout.  The same two kernels at Tq = 1 (packed keys above ATT_SEQ_MAX take
+// the streaming kernel, as in the bf16 twin), so out and lse are row 0 of the call above, bit for bit.
+extern "C" int uniir_onequery_fwd_f16(const void* q, int64_t q_ld, const void* k, const void* v, int64_t kv_ld, void* out,
+                                      int64_t out_ld, float* lse, const int32_t* key_len, const int32_t* kv_row_off, int32_t batch,
+                                      int32_t tk, int32_t heads, void* stream) {
+    if (att_null(q, k, v, out, lse) || batch < 0 || heads <= 0) return UNIIR_EINVAL;
+    if (key_len && kv_row_off) return UNIIR_EINVAL;
+    if (batch == 0) return UNIIR_OK;
+    if (tk < 1 || tk > ATT_LONG_SEQ_MAX) return UNIIR_ESHAPE;
+    if (att_ld_not8(q_ld, kv_ld, out_ld)) return UNIIR_EALIGN;
+    if (att_misaligned16(q, k, v, out)) return UNIIR_EALIGN;
+    AttnArgs a = att_args_qkv(q, q_ld, k, v, kv_ld, out, out_ld, lse, 1, tk, heads, key_len);
+    att_args_kv_rows(a, kv_row_off, 0);
+    if (tk > ATT_SEQ_MAX) return launch_attn_xlong_fwd(a, batch, (hipStream_t)stream, true);
+    return launch_attn_fwd(a, batch, (hipStream_t)stream, true);
+}
+
 // ---------------- T5-style self-attention ----------------
 // For the CLIP_FF fusion stack: logits = scale * q.k + rel_emb[rel_bucket[key - query + seq - 1]][head]
 // (transformers T5Attention: scale 1, bucketed relative position bias shared by all layers), packed qkv like

@@ -247,9 +247,9 @@ template <bool F16>
 __global__ __launch_bounds__(AL_THREADS) void attn_long_fwd_kernel(AttnArgs a, int nqb) {
     al_fwd_body<F16, false, false>(a, nqb);
 }
-template <bool DROP>
+template <bool DROP, bool F16 = false>
 __global__ __launch_bounds__(AL_THREADS) void attn_xlong_fwd_kernel(AttnArgs a, int nqb) {
-    al_fwd_body<false, true, DROP>(a, nqb);
+    al_fwd_body<F16, true, DROP>(a, nqb);
 }
 template <bool DROP>
 __global__ __launch_bounds__(AL_THREADS, 4) void attn_rlong_fwd_kernel(AttnArgs a, int nqb) {
@@ -610,6 +610,7 @@ template __global__ void attn_long_fwd_kernel<false>(AttnArgs, int);
 template __global__ void attn_long_fwd_kernel<true>(AttnArgs, int);
 template __global__ void attn_xlong_fwd_kernel<false>(AttnArgs, int);
 template __global__ void attn_xlong_fwd_kernel<true>(AttnArgs, int);
+template __global__ void attn_xlong_fwd_kernel<false, true>(AttnArgs, int);
 template __global__ void attn_xlong_dkdv_kernel<false>(AttnArgs, int);
 template __global__ void attn_xlong_dkdv_kernel<true>(AttnArgs, int);
 template __global__ void attn_xlong_dq_kernel<false>(AttnArgs, int);
@@ -622,7 +623,7 @@ static const int AL_DQ_LDS = 2 * 2 * AL_KV * 128 + 2 * AL_ROWS * 4;
 static int al_rel_tab_bytes(int seq) { return (2 * seq + 32) * 4; }
 static int al_rel_dkdv_bytes(int seq) { return 64 * 8 + (seq + 164) * 12; }
 
-// f16: AL_PLAIN only (the fp16 forward of the towers)
+// f16: AL_PLAIN (the fp16 forward of the towers) and AL_XL without dropout (uniir_attn_general_fwd_f16 / uniir_onequery_fwd_f16)
 static int al_launch_fwd(AlFamily fam, const AttnArgs& a, int batch, hipStream_t st, bool f16 = false) {
     const int nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
     const long grid = (long)batch * a.H * nqb;
@@ -634,9 +635,14 @@ static int al_launch_fwd(AlFamily fam, const AttnArgs& a, int batch, hipStream_t
         return att_launch<attn_long_fwd_kernel<true>>(AL_FWD_LDS, g, b, AL_FWD_LDS, st, a, nqb);
     }
     if (fam == AL_XL) {
+        if (f16) {
+            if (drop) return UNIIR_EUNSUPPORTED;
+            return att_launch<attn_xlong_fwd_kernel<false, true>>(AL_FWD_LDS, g, b, AL_FWD_LDS, st, a, nqb);
+        }
         if (!drop) return att_launch<attn_xlong_fwd_kernel<false>>(AL_FWD_LDS, g, b, AL_FWD_LDS, st, a, nqb);
         return att_launch<attn_xlong_fwd_kernel<true>>(AL_FWD_LDS, g, b, AL_FWD_LDS, st, a, nqb);
     }
+    if (f16) return UNIIR_EUNSUPPORTED;
     const int sm = AL_FWD_LDS + al_rel_tab_bytes(a.Tq), mx = AL_FWD_LDS + al_rel_tab_bytes(ATT_LONG_SEQ_MAX);
     if (!drop) return att_launch<attn_rlong_fwd_kernel<false>>(mx, g, b, sm, st, a, nqb);
     return att_launch<attn_rlong_fwd_kernel<true>>(mx, g, b, sm, st, a, nqb);
@@ -682,13 +688,13 @@ int launch_attn_long_fwd(const AttnArgs& a, int batch, hipStream_t st, bool f16)
 int launch_attn_long_bwd(const AttnArgs& a, int batch, hipStream_t st) {
     return attn_long_plain(a) ? al_launch_bwd(AL_PLAIN, a, batch, st) : UNIIR_ESHAPE;
 }
-// the general form's forward for another file (uniir_onequery_fwd, attention.hip): what uniir_attention_fwd_long launches, and
-// the one caller that may pass kv_row_off
-int launch_attn_xlong_fwd(const AttnArgs& a, int batch, hipStream_t st) {
+// the general form's forward for another file (uniir_onequery_fwd, uniir_attn_general_fwd_f16 and uniir_onequery_fwd_f16 in
+// attention.hip): what uniir_attention_fwd_long launches; the one-query callers alone may pass kv_row_off.  f16: no dropout
+int launch_attn_xlong_fwd(const AttnArgs& a, int batch, hipStream_t st, bool f16) {
     if (a.causal || a.rel_emb || a.scale != ATT_SCALE || a.Tq < 1 || a.Tk < 1 || a.Tq > ATT_LONG_SEQ_MAX || a.Tk > ATT_LONG_SEQ_MAX ||
         (a.kv_row_off && (a.row_off || a.klen)))
         return UNIIR_ESHAPE;
-    return al_launch_fwd(AL_XL, a, batch, st);
+    return al_launch_fwd(AL_XL, a, batch, st, f16);
 }
 
 // ---------------- the general form (uniir_attention_fwd_long / _bwd_long) ----------------

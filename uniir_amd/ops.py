@@ -357,14 +357,14 @@ def attention_fwd_ex(q, q_ld, k, v, kv_ld, batch, tq, tk, heads, *, key_len=None
     tq, tk <= 512; without the causal mask and with dense K / V (kv_packed false) up to 1024 each: max(tq, tk) > 512 runs
     uniir_attention_fwd_long (the streaming kernels of csrc/attention_long.hip), everything at 512 and below the calls it always
     ran.  Causal or kv_packed above 512 is UNIIR_ESHAPE.
-    bf16 only: the general form has no fp16 entry point in the library, so fp16 operands are refused here, before any launch --
-    ValueError for what an fp16 forward never takes (the causal mask, dropout, operands of mixed types), NotImplementedError for
-    the rest."""
+    bf16 only: fp16 operands are refused here, before any launch -- ValueError for what an fp16 forward never takes (the causal
+    mask, dropout, operands of mixed types), NotImplementedError for the rest: the fp16 general form is a wrapper of its own,
+    attention_fwd_ex_f16 (uniir_attn_general_fwd_f16)."""
     if torch.float16 in (q.dtype, k.dtype, v.dtype):
         _dtype16(q, k, v)
         if causal or drop_p > 0:
             raise ValueError("fp16 attention is the embedding forward: no causal mask and no dropout in the general form")
-        raise NotImplementedError("the general attention form (uniir_attention_fwd_ex / _rows / _long) has no fp16 entry point")
+        raise NotImplementedError("uniir_attention_fwd_ex / _rows / _long take bf16; fp16 operands go through ops.attention_fwd_ex_f16")
     nrow = batch * tq if row_off is None else int(rows)
     out = torch.empty(nrow, heads * 64, device=q.device, dtype=torch.bfloat16)
     lse = torch.empty(batch, heads, tq, device=q.device, dtype=torch.float32)
@@ -382,6 +382,37 @@ def attention_fwd_ex(q, q_ld, k, v, kv_ld, batch, tq, tk, heads, *, key_len=None
         check(_lib.load().uniir_attention_fwd_rows(_p(q), q_ld, _p(k), _p(v), kv_ld, _p(out), heads * 64, _p(lse), _p(row_off),
                                                    int(bool(kv_packed)), _p(key_len), batch, tq, tk, heads, float(drop_p),
                                                    int(drop_seed), _stream()), "attention_fwd_rows")
+    return out, lse
+
+
+def _all_fp16(what, *tensors):
+    """the fp16 general form takes fp16 operands only: anything else is a ValueError, raised before anything is launched"""
+    if _dtype16(*tensors) != DT_F16:
+        raise ValueError(f"{what} takes fp16 operands, not {tensors[0].dtype} (bf16: the wrapper without _f16)")
+
+
+def attention_fwd_ex_f16(q, q_ld, k, v, kv_ld, batch, tq, tk, heads, *, key_len=None, row_off=None, kv_packed=False, rows=None):
+    """attention_fwd_ex on fp16 operands, forward only, without the causal mask and dropout (uniir_attn_general_fwd_f16): the same
+    views, row_off / kv_packed / rows and key_len; tq, tk <= 512, with dense K / V up to 1024 each.  Returns fp16 out
+    [batch*tq or rows, heads*64] and fp32 lse [batch, heads, tq]."""
+    _all_fp16("attention_fwd_ex_f16", q, k, v)
+    nrow = batch * tq if row_off is None else int(rows)
+    out = torch.empty(nrow, heads * 64, device=q.device, dtype=torch.float16)
+    lse = torch.empty(batch, heads, tq, device=q.device, dtype=torch.float32)
+    check(_lib.load().uniir_attn_general_fwd_f16(_p(q), q_ld, _p(k), _p(v), kv_ld, _p(out), heads * 64, _p(lse), _p(row_off),
+                                                 int(bool(kv_packed)), _p(key_len), batch, tq, tk, heads, _stream()),
+          "attn_general_fwd_f16")
+    return out, lse
+
+
+def onequery_fwd_f16(q, q_ld, k, v, kv_ld, batch, tk, heads, *, key_len=None, kv_row_off=None):
+    """onequery_fwd on fp16 operands, without dropout (uniir_onequery_fwd_f16): out fp16 [batch, heads*64] and lse [batch, heads] are
+    bitwise row 0 of attention_fwd_ex_f16 on the same operands."""
+    _all_fp16("onequery_fwd_f16", q, k, v)
+    out = torch.empty(batch, heads * 64, device=q.device, dtype=torch.float16)
+    lse = torch.empty(batch, heads, device=q.device, dtype=torch.float32)
+    check(_lib.load().uniir_onequery_fwd_f16(_p(q), q_ld, _p(k), _p(v), kv_ld, _p(out), heads * 64, _p(lse), _p(key_len),
+                                             _p(kv_row_off), batch, tk, heads, _stream()), "onequery_fwd_f16")
     return out, lse
 
 

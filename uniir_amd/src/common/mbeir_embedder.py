@@ -40,19 +40,32 @@ def _clip_towers(model):
     return clip if hasattr(clip, "precision") else None
 
 
+def _blip_module(model):
+    """the uniir_amd BLIP_FF / BLIP_SF module (DDP-wrapped or not), or None (CLIP): it carries its own precision and embed_fp16"""
+    inner = getattr(model, "module", model)
+    return inner if hasattr(inner, "embed_fp16") and hasattr(inner, "precision") else None
+
+
 @contextlib.contextmanager
 def _tower_precision(model, use_fp16):
     # the reference runs the towers under torch.cuda.amp.autocast(enabled=use_fp16) (:52-56) -- fp16 matmuls: the CLIP towers here take
-    # their fp16 forward for the extraction (clip_model.precision = "fp16") and go back to what they were set to afterwards
+    # their fp16 forward for the extraction (clip_model.precision = "fp16") and go back to what they were set to afterwards.  A BLIP
+    # model does the same when it opted in (BLIPFeatureFusion.embed_fp16, UNIIR_BLIP_EMBED_FP16=1); without that its extraction stays
+    # in bf16 whatever use_fp16 says, as it always was
     clip = _clip_towers(model)
-    restore = None
+    blip = _blip_module(model) if clip is None else None
+    restore = restore_blip = None
     if clip is not None and use_fp16 and clip.precision == "bf16":
         restore, clip.precision = clip.precision, "fp16"
+    if blip is not None and use_fp16 and blip.embed_fp16 and blip.precision == "bf16":
+        restore_blip, blip.precision = blip.precision, "fp16"
     try:
         yield
     finally:
         if restore is not None:
             clip.precision = restore
+        if restore_blip is not None:
+            blip.precision = restore_blip
 
 
 @torch.no_grad()
