@@ -17,6 +17,7 @@ stash.  Differences from the reference, stated once:
   * hard negatives (blip_ff.py:127-131,159-170,233-246) are supported; like the reference their momentum features are
     used un-normalised and a host coin flip decides what is enqueued.
 """
+import functools
 import json
 import logging
 import os
@@ -170,15 +171,6 @@ def vit_backward(st, dconv, prefix, cfg, dtok, stash):
     ops.call("uniir_unpad_add", dconv, st.grad_view(prefix + "patch_embed.proj.weight"), D, 3 * P * P, dconv.shape[1])
 
 
-def _ln2(st, x, wname, eps, R, W, dtype16=torch.bfloat16):
-    """post-LN sublayer output in both precisions: fp32 for the next residual, bf16 (fp16 with dtype16 = torch.float16, through
-    uniir_layernorm_fwd_f16) for the next GEMM"""
-    o32 = torch.empty(R, W, device=x.device, dtype=torch.float32)
-    o16 = torch.empty(R, W, device=x.device, dtype=dtype16)
-    ops.layernorm_fwd(x, st.p(wname + "weight"), st.p(wname + "bias"), eps, out_bf16=o16, out_f32=o32, rows=R, width=W)
-    return o32, o16
-
-
 class TextPack:
     """The rows of a padded [M, L] token batch up to each caption's valid length, packed back to back.  The
     reference runs BERT on all L positions and masks the padded KEYS with (1 - m) * -10000 (med.py:687-688: exp underflows to an
@@ -211,6 +203,271 @@ class TextPack:
         return TextPack(lens, L, dev)
 
 
+class _BertCall:
+    """What one bert_forward / bert_backward call knows about itself: the sizes, the rows (dense or packed), the dropout rates and the
+    weight shadow of its 16-bit type.  Built once in the forward and again from the stash in the backward."""
+
+    def __init__(self, st, prefix, cfg, M, L, Ti, key_len, img16, pack, ph, pa, cross, drop=None, dtype16=torch.bfloat16):
+        self.st, self.prefix, self.cross, self.drop, self.dtype16 = st, prefix, cross, drop, dtype16
+        self.W, self.I, self.eps = cfg["hidden_size"], cfg["intermediate_size"], cfg["layer_norm_eps"]
+        self.heads, self.layers, self.vocab = cfg["num_attention_heads"], cfg["num_hidden_layers"], cfg["vocab_size"]
+        self.M, self.L, self.Ti, self.key_len, self.img16, self.pack, self.ph, self.pa = M, L, Ti, key_len, img16, pack, ph, pa
+        self.half, self.dev = dtype16 == torch.float16, key_len.device
+        self.w16 = st.w16h if self.half else st.w16
+        self.R = pack.R if pack is not None else M * L
+        self.roff = pack.row_off if pack is not None else None
+        self.rmap = pack.row_map if pack is not None else None
+        # attention on dense rows (padding mask key_len) or on the packed rows (the item's own length is its key count)
+        self.self_kw = dict(key_len=key_len) if pack is None else dict(row_off=self.roff, kv_packed=True)
+        self.cross_kw = {} if pack is None else dict(row_off=self.roff, kv_packed=False)
+        self.out_rows = {} if pack is None else dict(rows=self.R)          # the forward allocates its packed output by this
+
+    @classmethod
+    def of_stash(cls, st, prefix, cfg, stash, cross):
+        return cls(st, prefix, cfg, stash["M"], stash["L"], stash["Ti"], stash["key_len"], stash["img16"], stash.get("pack"),
+                   stash["ph"], stash["pa"], cross)
+
+    def f32(self, *shape, zero=False):
+        return (torch.zeros if zero else torch.empty)(*shape, device=self.dev, dtype=torch.float32)
+
+    def b16(self, *shape, zero=False):
+        """a 16-bit activation: bf16, or fp16 in the fp16 forward"""
+        return (torch.zeros if zero else torch.empty)(*shape, device=self.dev, dtype=self.dtype16)
+
+    def seed(self, p):
+        """the next dropout seed of the pass for a site with rate p (0: the site launches nothing and draws nothing)"""
+        return self.drop.next() if p else 0
+
+    def attention(self, name, *args, seed, at=None, **kw):
+        """the forward attention `name` (ops.attention_fwd_ex / ops.onequery_fwd) in this call's 16-bit type: the fp16 wrappers take no
+        dropout arguments, the bf16 ones get the rate, the seed and `at` (the coordinates of a one-query call's dropout)"""
+        if self.half:
+            return getattr(ops, name + "_f16")(*args, **kw)
+        return getattr(ops, name)(*args, drop_p=self.pa, drop_seed=seed, **(at or {}), **kw)
+
+    def ln2(self, x, wname, n):
+        """post-LN sublayer output in both precisions: fp32 for the next residual, bf16 (fp16 in the fp16 forward, through
+        uniir_layernorm_fwd_f16) for the next GEMM"""
+        o32, o16 = self.f32(n, self.W), self.b16(n, self.W)
+        ops.layernorm_fwd(x, self.st.p(wname + "weight"), self.st.p(wname + "bias"), self.eps, out_bf16=o16, out_f32=o32, rows=n,
+                          width=self.W)
+        return o32, o16
+
+    def out_dense(self, x16, name, resid, row_map):
+        """dense -> dropout -> + residual (BertSelfOutput / BertOutput, med.py:196-200,339-343), pre-LayerNorm sum"""
+        w, bias = self.w16(name + "weight"), self.st.p(name + "bias")
+        if not self.ph:
+            return ops.linear_fwd(x16, w, bias, epilogue=ops.EPI_RESID_F32, resid=resid), 0
+        t = ops.linear_fwd(x16, w, bias, epilogue=ops.EPI_RESID_F32)
+        sd = self.drop.next()
+        ops.dropout_f32(t, self.ph, sd, resid=resid, out_f32=t, row_map=row_map)
+        return t, sd
+
+
+class _AllRows:
+    """A layer on all R rows of the batch, dense [M * L] or packed: the general attention, the residual stream as it is."""
+
+    def __init__(self, cx, full_layers):
+        self.cx, self.n, self.row_map = cx, cx.R, cx.rmap
+        # gelu's output [R, I]: one buffer serves every full layer of the call (nothing keeps it after output.dense has read it)
+        self.g = cx.b16(cx.R, cx.I) if full_layers else None
+
+    def g_buffer(self):
+        return self.g
+
+    def take(self, h32):
+        return h32
+
+    def spread(self, d):
+        return d
+
+    def self_fwd(self, qkv, seed):
+        cx, W = self.cx, self.cx.W
+        return cx.attention("attention_fwd_ex", qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, cx.M, cx.L, cx.L, cx.heads, seed=seed,
+                            **cx.self_kw, **cx.out_rows) + ({},)
+
+    def cross_fwd(self, cq, ckv, seed):
+        cx, W = self.cx, self.cx.W
+        return cx.attention("attention_fwd_ex", cq, W, ckv, ckv[:, W:], 2 * W, cx.M, cx.L, cx.Ti, cx.heads, seed=seed, **cx.cross_kw,
+                            **cx.out_rows)
+
+    def self_bwd(self, sv, dao, seed):
+        cx, W, qkv = self.cx, self.cx.W, sv["qkv"]
+        dqkv = cx.b16(self.n, 3 * W)
+        ops.attention_bwd_ex(qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, sv["ao"], dao, sv["lse1"], dqkv, 3 * W, dqkv[:, W:],
+                             dqkv[:, 2 * W:], 3 * W, cx.M, cx.L, cx.L, cx.heads, drop_p=cx.pa, drop_seed=seed, **cx.self_kw)
+        return dqkv
+
+    def cross_bwd(self, sv, dco, dcq, dckv, seed):
+        cx, W, ckv = self.cx, self.cx.W, sv["ckv"]
+        ops.attention_bwd_ex(sv["cq"], W, ckv, ckv[:, W:], 2 * W, sv["co"], dco, sv["lse2"], dcq, W, dckv, dckv[:, W:], 2 * W, cx.M,
+                             cx.L, cx.Ti, cx.heads, drop_p=cx.pa, drop_seed=seed, **cx.cross_kw)
+
+
+class _ClassRows:
+    """The last BERT layer when only the class row of every item leaves the encoder (blip_ff.py:82-116 reads pooler_output,
+    blip_sf.py the class token): what that row needs from the other rows is their KEYS AND VALUES, so the q | k | v projection still
+    runs on all R rows -- the same GEMM as in the full layer, so K | V have its bits, a dense BERT passes row m * L of that buffer as
+    the query without a copy, and the backward's weight-gradient and d h32 products keep their shape -- and everything behind it on
+    the M class rows: the one-query self-attention (ops.onequery_fwd with key_len or the packed rows), attention.output.dense +
+    LayerNorm, the cross query, the one-query cross-attention over the Ti image tokens, its output dense + LayerNorm, the FFN and
+    output.LayerNorm.  The dropout seeds are drawn in the full layer's order; attention dropout sits at the coordinates of query 0 of
+    L (drop_tq = L, drop_q = 0), hidden dropout at the dense rows m * L (row_map).
+    Backward: everything up to the self-attention runs on M rows; the one-query backward writes dk | dv of EVERY key row (exact zeros
+    behind a dense item's key_len) and dq of the class rows into a zeroed [R, 3W] buffer -- the rows whose query gradient the full
+    layer finds to be zero -- so the q | k | v weight gradient and d h32 = dqkv @ Wqkv + dt1 are the full layer's products; dt1 is
+    scattered into zeroed R rows.
+    take / spread are also how a full last layer's class rows leave the encoder and how their gradient comes back."""
+
+    def __init__(self, cx):
+        self.cx, self.n = cx, cx.M
+        self.at = dict(drop_tq=cx.L, drop_q=0)
+
+    @functools.cached_property
+    def row_map(self):
+        """int32: the DENSE row m * L of each of the M rows (the coordinates of hidden dropout)"""
+        return torch.arange(self.n, device=self.cx.dev, dtype=torch.int32) * self.cx.L
+
+    @functools.cached_property
+    def cls(self):
+        """the class token's row among the packed rows = the first row of every item, as an index tensor"""
+        return self.cx.roff[:self.n].long()
+
+    def g_buffer(self):
+        return self.cx.b16(self.n, self.cx.I)
+
+    def take(self, h32):
+        cx = self.cx
+        rows = cx.f32(self.n, cx.W)
+        ops.call("uniir_gather_rows", h32, cx.roff, rows, cx.M, cx.L if cx.pack is None else 0, cx.W)
+        return rows
+
+    def spread(self, d):
+        cx = self.cx
+        out = cx.f32(cx.R, cx.W, zero=True)
+        ops.call("uniir_scatter_rows", d, cx.roff, out, cx.M, cx.L if cx.pack is None else 0, cx.W)
+        return out
+
+    def self_fwd(self, qkv, seed):
+        cx, W = self.cx, self.cx.W
+        if cx.pack is None:
+            q, q_ld, kw = qkv, cx.L * 3 * W, dict(key_len=cx.key_len)
+        else:
+            q, q_ld, kw = qkv[self.cls, :W], W, dict(kv_row_off=cx.roff)          # a copy of M rows
+        return cx.attention("onequery_fwd", q, q_ld, qkv[:, W:], qkv[:, 2 * W:], 3 * W, cx.M, cx.L, cx.heads, seed=seed, at=self.at,
+                            **kw) + (dict(pooled=True, q=q, q_ld=q_ld),)
+
+    def cross_fwd(self, cq, ckv, seed):
+        cx, W = self.cx, self.cx.W
+        return cx.attention("onequery_fwd", cq, W, ckv, ckv[:, W:], 2 * W, cx.M, cx.Ti, cx.heads, seed=seed, at=self.at)
+
+    def self_bwd(self, sv, dao, seed):
+        cx, W, qkv = self.cx, self.cx.W, sv["qkv"]
+        dqkv = cx.b16(cx.R, 3 * W, zero=True)
+        if cx.pack is None:
+            dq, kw = dqkv, dict(key_len=cx.key_len)
+        else:
+            dq, kw = cx.b16(self.n, W), dict(kv_row_off=cx.roff)
+        ops.onequery_bwd(sv["q"], sv["q_ld"], qkv[:, W:], qkv[:, 2 * W:], 3 * W, sv["ao"], dao, sv["lse1"], dq, sv["q_ld"], dqkv[:, W:],
+                         dqkv[:, 2 * W:], 3 * W, cx.M, cx.L, cx.heads, drop_p=cx.pa, drop_seed=seed, **self.at, **kw)
+        if cx.pack is not None:
+            dqkv[self.cls, :W] = dq          # a copy of M rows
+        return dqkv
+
+    def cross_bwd(self, sv, dco, dcq, dckv, seed):
+        cx, W, ckv = self.cx, self.cx.W, sv["ckv"]
+        ops.onequery_bwd(sv["cq"], W, ckv, ckv[:, W:], 2 * W, sv["co"], dco, sv["lse2"], dcq, W, dckv, dckv[:, W:], 2 * W, cx.M, cx.Ti,
+                         cx.heads, drop_p=cx.pa, drop_seed=seed, **self.at)
+
+
+def _layer_forward(cx, rows, i, h32, h16, save):
+    """BertLayer i of med.py on `rows` (an _AllRows or a _ClassRows of cx): self-attention, cross-attention over the image tokens
+    (mode "multimodal"), feed-forward, each closed by dense -> dropout -> + residual -> LayerNorm.  h32 / h16: the layer's input on
+    all R rows.  -> the output on rows.n rows in fp32 and 16 bits, and what the backward needs (None without save)"""
+    st, w16, W, n = cx.st, cx.w16, cx.W, rows.n
+    b = f"{cx.prefix}encoder.layer.{i}."
+    s, c = b + "attention.self.", b + "crossattention.self."
+    qkv = ops.linear_fwd(h16, w16(s + "query.weight", (3 * W, W)), st.p(s + "query.bias", (3 * W,)))
+    sa1 = cx.seed(cx.pa)
+    ao, lse1, kept = rows.self_fwd(qkv, sa1)          # kept: what the backward of these rows needs beyond the tensors below
+    t1, so1 = cx.out_dense(ao, b + "attention.output.dense.", rows.take(h32), rows.row_map)
+    a32, a16 = cx.ln2(t1, b + "attention.output.LayerNorm.", n)
+    cq = ckv = co = lse2 = t2 = None
+    sa2 = so2 = 0
+    if cx.cross:
+        cq = ops.linear_fwd(a16, w16(c + "query.weight"), st.p(c + "query.bias"))
+        ckv = ops.linear_fwd(cx.img16, w16(c + "key.weight", (2 * W, cx.img16.shape[1])), st.p(c + "key.bias", (2 * W,)))
+        sa2 = cx.seed(cx.pa)
+        co, lse2 = rows.cross_fwd(cq, ckv, sa2)
+        t2, so2 = cx.out_dense(co, b + "crossattention.output.dense.", a32, rows.row_map)
+        c32, c16 = cx.ln2(t2, b + "crossattention.output.LayerNorm.", n)
+    else:
+        c32, c16 = a32, a16
+    f, g = cx.b16(n, cx.I), rows.g_buffer()
+    ops.linear_fwd(c16, w16(b + "intermediate.dense.weight"), st.p(b + "intermediate.dense.bias"), out=f,
+                   epilogue=ops.EPI_BIAS_ACT, C2=g, act=ops.ACT_GELU_ERF)
+    t3, so3 = cx.out_dense(g, b + "output.dense.", c32, rows.row_map)
+    sv = dict(h16=h16, qkv=qkv, ao=ao, lse1=lse1, t1=t1, a16=a16, cq=cq, ckv=ckv, co=co, lse2=lse2, t2=t2, c16=c16, f=f, t3=t3,
+              seeds=(sa1, so1, sa2, so2, so3), **kept) if save else None
+    return cx.ln2(t3, b + "output.LayerNorm.", n) + (sv,)
+
+
+def _layer_backward(cx, rows, i, sv, do, dimg):
+    """backward of _layer_forward on the same `rows`.  do fp32 [rows.n, W]: the gradient of the layer's output; dimg (cross-attention)
+    accumulates the gradient of the image tokens.  -> d h32 fp32 [R, W], the gradient of the layer's input on all R rows"""
+    st, G, W, I, n, eps, ph = cx.st, cx.st.grad_view, cx.W, cx.I, rows.n, cx.eps, cx.ph
+    b = f"{cx.prefix}encoder.layer.{i}."
+    s, c = b + "attention.self.", b + "crossattention.self."
+    sa1, so1, sa2, so2, so3 = sv["seeds"]
+    # ---- feed-forward sublayer: o = LN(g @ Wout^T + bout + c32), g = gelu(c16 @ Wi^T + bi)
+    d16 = cx.b16(n, W)
+    dt3 = ops.layernorm_bwd(sv["t3"], st.p(b + "output.LayerNorm.weight"), do, G(b + "output.LayerNorm.weight"),
+                            G(b + "output.LayerNorm.bias"), eps, dx_bf16=d16, rows=n, width=W)
+    if ph:      # the dense branch sees the masked gradient, the residual branch (dt3, fp32) the full one
+        ops.dropout_bf16_(d16, ph, so3, row_map=rows.row_map)
+    df, g = cx.b16(n, I), rows.g_buffer()
+    ops.linear_dgrad(d16, st.w16(b + "output.dense.weight"), out=df, aux=sv["f"], act_out=g,
+                     colsum=G(b + "intermediate.dense.bias"), act=ops.ACT_GELU_ERF)
+    ops.linear_wgrad(d16, g, G(b + "output.dense.weight"), dbias=G(b + "output.dense.bias"))
+    ops.linear_wgrad(df, sv["c16"], G(b + "intermediate.dense.weight"))
+    dc = cx.f32(n, W)       # d c32 = df @ Wi + dt3 (the residual branch)
+    ops.gemm(df, st.w16(b + "intermediate.dense.weight"), dc, n, W, I, I, W, W, b_tmaj=True, epilogue=ops.EPI_RESID_F32, resid=dt3)
+    if not cx.cross:
+        da = dc                      # mode "text": c32 is a32
+    else:
+        # ---- cross-attention sublayer: c = LN(co @ Wco^T + bco + a32)
+        dt2 = ops.layernorm_bwd(sv["t2"], st.p(b + "crossattention.output.LayerNorm.weight"), dc,
+                                G(b + "crossattention.output.LayerNorm.weight"), G(b + "crossattention.output.LayerNorm.bias"), eps,
+                                dx_bf16=d16, rows=n, width=W)
+        if ph:
+            ops.dropout_bf16_(d16, ph, so2, row_map=rows.row_map)
+        ops.linear_wgrad(d16, sv["co"], G(b + "crossattention.output.dense.weight"), dbias=G(b + "crossattention.output.dense.bias"))
+        dco = ops.linear_dgrad(d16, st.w16(b + "crossattention.output.dense.weight"))
+        dcq, dckv = cx.b16(n, W), cx.b16(cx.M * cx.Ti, 2 * W)
+        rows.cross_bwd(sv, dco, dcq, dckv, sa2)
+        img16 = cx.img16
+        Ew = img16.shape[1]
+        ops.linear_wgrad(dckv, img16, G(c + "key.weight", (2 * W, Ew)), dbias=G(c + "key.bias", (2 * W,)))
+        ops.gemm(dckv, st.w16(c + "key.weight", (2 * W, Ew)), dimg, cx.M * cx.Ti, Ew, 2 * W, 2 * W, Ew, Ew, b_tmaj=True,
+                 epilogue=ops.EPI_RESID_F32, resid=dimg)          # dimg += dckv @ Wkv (in place: same element r/w)
+        ops.linear_wgrad(dcq, sv["a16"], G(c + "query.weight"), dbias=G(c + "query.bias"))
+        da = cx.f32(n, W)       # d a32 = dcq @ Wcq + dt2
+        ops.gemm(dcq, st.w16(c + "query.weight"), da, n, W, W, W, W, W, b_tmaj=True, epilogue=ops.EPI_RESID_F32, resid=dt2)
+    # ---- self-attention sublayer: a = LN(ao @ Wo^T + bo + h32)
+    dt1 = ops.layernorm_bwd(sv["t1"], st.p(b + "attention.output.LayerNorm.weight"), da, G(b + "attention.output.LayerNorm.weight"),
+                            G(b + "attention.output.LayerNorm.bias"), eps, dx_bf16=d16, rows=n, width=W)
+    if ph:
+        ops.dropout_bf16_(d16, ph, so1, row_map=rows.row_map)
+    ops.linear_wgrad(d16, sv["ao"], G(b + "attention.output.dense.weight"), dbias=G(b + "attention.output.dense.bias"))
+    dao = ops.linear_dgrad(d16, st.w16(b + "attention.output.dense.weight"))
+    dqkv = rows.self_bwd(sv, dao, sa1)          # on all R rows, whichever rows the layer ran on
+    ops.linear_wgrad(dqkv, sv["h16"], G(s + "query.weight", (3 * W, W)), dbias=G(s + "query.bias", (3 * W,)))
+    dh = cx.f32(cx.R, W)       # d h32 = dqkv @ Wqkv + dt1
+    ops.gemm(dqkv, st.w16(s + "query.weight", (3 * W, W)), dh, cx.R, W, 3 * W, 3 * W, W, W, b_tmaj=True, epilogue=ops.EPI_RESID_F32,
+             resid=rows.spread(dt1))
+    return dh
+
+
 def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, pool=True, drop=None, pack=None, pool_last=False,
                  log=None, dtype16=torch.bfloat16):
     """src/models/uniir_blip/backbone/med.py BertModel.forward(mode="multimodal") -> pooler_output fp32 [M,W] + stash.
@@ -222,15 +479,12 @@ def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, poo
     pack (TextPack): run on the rows up to each caption's valid length only -- same pooled output bit for bit (train mode included),
     parameter gradients equal up to the order of the fp32 additions in the weight-gradient reductions.
     pool_last (BLIPFeatureFusion.pool_last_layer): only the class row of every item leaves the encoder, so the LAST layer runs on
-    those M rows (_bert_last_layer_pooled): the same class row bit for bit, train mode included.  log: a list that gets a line
-    when it does.
+    those M rows (_ClassRows): the same class row bit for bit, train mode included.  log: a list that gets a line when it does.
     dtype16 = torch.float16 (forward only and eval only: save False, drop None; img16 fp16, or None for mode "text"): every weight
     comes from st's fp16 shadow (FlatStore.w16h, the spanning q | k | v and cross k | v shapes included), the 16-bit activations are
     fp16 and both attentions run the fp16 general form (ops.attention_fwd_ex_f16 / ops.onequery_fwd_f16); the residual stream, the
     LayerNorm statistics, tanh and the gathered class rows stay fp32, as in vit_forward.  pack and pool_last are honoured, each bit for
     bit the unpacked / full-layer result.  A bf16 caller makes exactly the calls it made before this argument existed."""
-    W, I, eps = cfg["hidden_size"], cfg["intermediate_size"], cfg["layer_norm_eps"]
-    heads, layers = cfg["num_attention_heads"], cfg["num_hidden_layers"]
     M, L = ids.shape
     if dtype16 not in (torch.bfloat16, torch.float16):
         raise ValueError(f"dtype16 is torch.bfloat16 or torch.float16, not {dtype16!r}")
@@ -240,95 +494,42 @@ def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, poo
                            "dropout (save=True and drop need dtype16=torch.bfloat16)")
     if half and img16 is not None and img16.dtype != torch.float16:
         raise ValueError(f"bert_forward: {img16.dtype} image tokens with dtype16 = {dtype16}")
-    w16 = st.w16h if half else st.w16
-    R, dev = (pack.R if pack is not None else M * L), ids.device
-    roff = pack.row_off if pack is not None else None
-    rmap = pack.row_map if pack is not None else None
-    e32 = torch.empty(R, W, device=dev, dtype=torch.float32)
-    if pack is None:
-        scratch = torch.empty(M, device=dev, dtype=torch.int32)
-        ops.call("uniir_text_embed", ids, st.p(prefix + "embeddings.word_embeddings.weight"),
-                 st.p(prefix + "embeddings.position_embeddings.weight"), e32, scratch, M, L, W, cfg["vocab_size"])
-    else:
-        ops.call("uniir_text_embed_packed", ids, st.p(prefix + "embeddings.word_embeddings.weight"),
-                 st.p(prefix + "embeddings.position_embeddings.weight"), roff, e32, None, M, L, W, cfg["vocab_size"])
-    h32, h16 = _ln2(st, e32, prefix + "embeddings.LayerNorm.", eps, R, W, dtype16)
     ph = cfg.get("hidden_dropout_prob", 0.0) if drop is not None else 0.0
     pa = cfg.get("attention_probs_dropout_prob", 0.0) if drop is not None else 0.0
-    s_emb = drop.next() if ph else 0
+    cx = _BertCall(st, prefix, cfg, M, L, Ti, key_len, img16, pack, ph, pa, cross, drop, dtype16)
+    W, R, layers = cx.W, cx.R, cx.layers
+    e32 = cx.f32(R, W)
+    word, pos = st.p(prefix + "embeddings.word_embeddings.weight"), st.p(prefix + "embeddings.position_embeddings.weight")
+    if pack is None:
+        scratch = torch.empty(M, device=ids.device, dtype=torch.int32)
+        ops.call("uniir_text_embed", ids, word, pos, e32, scratch, M, L, W, cx.vocab)
+    else:
+        ops.call("uniir_text_embed_packed", ids, word, pos, cx.roff, e32, None, M, L, W, cx.vocab)
+    h32, h16 = cx.ln2(e32, prefix + "embeddings.LayerNorm.", R)
+    s_emb = cx.seed(ph)
     if ph:
-        ops.dropout_f32(h32, ph, s_emb, out_f32=h32, out_bf16=h16, row_map=rmap)
+        ops.dropout_f32(h32, ph, s_emb, out_f32=h32, out_bf16=h16, row_map=cx.rmap)
     stash = dict(ids=ids, e32=e32, layers=[], M=M, L=L, Ti=Ti, key_len=key_len, img16=img16, ph=ph, pa=pa,
                  s_emb=s_emb, pack=pack) if save else None
-    # attention on dense rows (padding mask key_len) or on the packed rows (the item's own length is its key count)
-    self_kw = dict(key_len=key_len) if pack is None else dict(row_off=roff, kv_packed=True, rows=R)
-    cross_kw = {} if pack is None else dict(row_off=roff, kv_packed=False, rows=R)
-
-    def out_dense(x16, name, resid, row_map=rmap):
-        """dense -> dropout -> + residual (BertSelfOutput / BertOutput, med.py:196-200,339-343), pre-LayerNorm sum"""
-        if not ph:
-            return ops.linear_fwd(x16, w16(name + "weight"), st.p(name + "bias"), epilogue=ops.EPI_RESID_F32,
-                                  resid=resid), 0
-        t = ops.linear_fwd(x16, w16(name + "weight"), st.p(name + "bias"), epilogue=ops.EPI_RESID_F32)
-        sd = drop.next()
-        ops.dropout_f32(t, ph, sd, resid=resid, out_f32=t, row_map=row_map)
-        return t, sd
-
-    g = torch.empty(R, I, device=dev, dtype=dtype16) if not (pool_last and layers == 1) else None
-    for i in range(layers - 1 if pool_last else layers):
-        b = f"{prefix}encoder.layer.{i}."
-        s, c = b + "attention.self.", b + "crossattention.self."
-        qkv = ops.linear_fwd(h16, w16(s + "query.weight", (3 * W, W)), st.p(s + "query.bias", (3 * W,)))
-        sa1 = drop.next() if pa else 0
-        if half:
-            ao, lse1 = ops.attention_fwd_ex_f16(qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, M, L, L, heads, **self_kw)
-        else:
-            ao, lse1 = ops.attention_fwd_ex(qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, M, L, L, heads, drop_p=pa, drop_seed=sa1,
-                                            **self_kw)
-        t1, so1 = out_dense(ao, b + "attention.output.dense.", h32)
-        a32, a16 = _ln2(st, t1, b + "attention.output.LayerNorm.", eps, R, W, dtype16)
-        cq = ckv = co = lse2 = t2 = None
-        sa2 = so2 = 0
-        if cross:
-            cq = ops.linear_fwd(a16, w16(c + "query.weight"), st.p(c + "query.bias"))
-            ckv = ops.linear_fwd(img16, w16(c + "key.weight", (2 * W, img16.shape[1])), st.p(c + "key.bias", (2 * W,)))
-            sa2 = drop.next() if pa else 0
-            if half:
-                co, lse2 = ops.attention_fwd_ex_f16(cq, W, ckv, ckv[:, W:], 2 * W, M, L, Ti, heads, **cross_kw)
-            else:
-                co, lse2 = ops.attention_fwd_ex(cq, W, ckv, ckv[:, W:], 2 * W, M, L, Ti, heads, drop_p=pa, drop_seed=sa2, **cross_kw)
-            t2, so2 = out_dense(co, b + "crossattention.output.dense.", a32)
-            c32, c16 = _ln2(st, t2, b + "crossattention.output.LayerNorm.", eps, R, W, dtype16)
-        else:
-            c32, c16 = a32, a16
-        f = torch.empty(R, I, device=dev, dtype=dtype16)
-        ops.linear_fwd(c16, w16(b + "intermediate.dense.weight"), st.p(b + "intermediate.dense.bias"), out=f,
-                       epilogue=ops.EPI_BIAS_ACT, C2=g, act=ops.ACT_GELU_ERF)
-        t3, so3 = out_dense(g, b + "output.dense.", c32)
-        if save:
-            stash["layers"].append(dict(h16=h16, qkv=qkv, ao=ao, lse1=lse1, t1=t1, a16=a16, cq=cq, ckv=ckv, co=co,
-                                        lse2=lse2, t2=t2, c16=c16, f=f, t3=t3, seeds=(sa1, so1, sa2, so2, so3)))
-        h32, h16 = _ln2(st, t3, b + "output.LayerNorm.", eps, R, W, dtype16)
-    if pool_last:
-        rows, sv = _bert_last_layer_pooled(st, prefix, cfg, h32, h16, key_len, img16, Ti, M, L, R, cross, drop, ph, pa, pack, out_dense,
-                                           dtype16)
+    all_rows, class_rows = _AllRows(cx, layers - bool(pool_last)), _ClassRows(cx)
+    for i in range(layers):
+        rows = class_rows if pool_last and i == layers - 1 else all_rows
+        h32, h16, sv = _layer_forward(cx, rows, i, h32, h16, save)
         if save:
             stash["layers"].append(sv)
+    if pool_last:
+        rows = h32
         if log is not None:
             log.append(f"BERT last layer {layers - 1} on the {M} class rows (pool_last_layer): K | V from {R} "
                        f"{'packed' if pack is not None else 'dense'} rows, {'self- and cross-' if cross else 'self-'}attention in the "
                        f"one-query form, {'stash of M-row tensors' if save else 'no stash'}")
     else:
-        rows = torch.empty(M, W, device=dev, dtype=torch.float32)
-        if pack is None:
-            ops.call("uniir_gather_rows", h32, None, rows, M, L, W)
-        else:
-            ops.call("uniir_gather_rows", h32, roff, rows, M, 0, W)          # the class token = the first row of every item
+        rows = class_rows.take(h32)          # the class token = the first row of every item
     if not pool:
         return rows, stash
-    rows16 = torch.empty(M, W, device=dev, dtype=dtype16)
+    rows16 = cx.b16(M, W)
     ops.call("uniir_cast_f32_to_f16" if half else "uniir_cast_f32_to_bf16", rows, rows16, rows.numel())
-    pre = ops.linear_fwd(rows16, w16(prefix + "pooler.dense.weight"), st.p(prefix + "pooler.dense.bias"),
+    pre = ops.linear_fwd(rows16, cx.w16(prefix + "pooler.dense.weight"), st.p(prefix + "pooler.dense.bias"),
                          epilogue=ops.EPI_RESID_F32)
     pooled = torch.empty_like(pre)
     ops.call("uniir_tanh_fwd", pre, pooled, pre.numel())
@@ -337,292 +538,46 @@ def bert_forward(st, prefix, cfg, ids, key_len, img16, Ti, save, cross=True, poo
     return pooled, stash
 
 
-def _class_rows(pack, M, L, dev):
-    """of the class token of every item: its row in the (dense or packed) row numbering as an index tensor, and the int32 row_map
-    that gives each of these M rows its DENSE row m * L (the coordinates of hidden dropout)"""
-    cmap = torch.arange(M, device=dev, dtype=torch.int32) * L
-    return (cmap.long() if pack is None else pack.row_off[:M].long()), cmap
-
-
-def _bert_last_layer_pooled(st, prefix, cfg, h32, h16, key_len, img16, Ti, M, L, R, cross, drop, ph, pa, pack, out_dense,
-                            dtype16=torch.bfloat16):
-    """The last BERT layer when only the class row of every item leaves the encoder (blip_ff.py:82-116 reads pooler_output,
-    blip_sf.py the class token): what that row needs from the other rows is their KEYS AND VALUES, so the q | k | v projection still
-    runs on all R rows -- the same GEMM as in the full layer, so K | V have its bits, a dense BERT passes row m * L of that buffer as
-    the query without a copy, and the backward's weight-gradient and d h32 products keep their shape -- and everything behind it on
-    the M class rows: the one-query self-attention (ops.onequery_fwd with key_len or the packed rows), attention.output.dense +
-    LayerNorm, the cross query, the one-query cross-attention over the Ti image tokens, its output dense + LayerNorm, the FFN and
-    output.LayerNorm.  The dropout seeds are drawn in the full layer's order; attention dropout sits at the coordinates of query 0 of
-    L (drop_tq = L, drop_q = 0), hidden dropout at the dense rows m * L (row_map).  -> the class rows fp32 [M, W], the layer's stash.
-    dtype16 = torch.float16: bert_forward's fp16 forward (no dropout; out_dense is its closure over the fp16 shadow): the one-query
-    attentions are ops.onequery_fwd_f16."""
-    W, I, eps = cfg["hidden_size"], cfg["intermediate_size"], cfg["layer_norm_eps"]
-    heads, i = cfg["num_attention_heads"], cfg["num_hidden_layers"] - 1
-    dev = h32.device
-    half = dtype16 == torch.float16
-    w16 = st.w16h if half else st.w16
-    b = f"{prefix}encoder.layer.{i}."
-    s, c = b + "attention.self.", b + "crossattention.self."
-    cls, cmap = _class_rows(pack, M, L, dev)
-    qkv = ops.linear_fwd(h16, w16(s + "query.weight", (3 * W, W)), st.p(s + "query.bias", (3 * W,)))
-    sa1 = drop.next() if pa else 0
-    if pack is None:
-        q, q_ld, kw = qkv, L * 3 * W, dict(key_len=key_len)
-    else:
-        q, q_ld, kw = qkv[cls, :W], W, dict(kv_row_off=pack.row_off)          # a copy of M rows
-    if half:
-        ao, lse1 = ops.onequery_fwd_f16(q, q_ld, qkv[:, W:], qkv[:, 2 * W:], 3 * W, M, L, heads, **kw)
-    else:
-        ao, lse1 = ops.onequery_fwd(q, q_ld, qkv[:, W:], qkv[:, 2 * W:], 3 * W, M, L, heads, drop_p=pa, drop_seed=sa1, drop_tq=L, drop_q=0, **kw)
-    h32c = torch.empty(M, W, device=dev, dtype=torch.float32)
-    ops.call("uniir_gather_rows", h32, None if pack is None else pack.row_off, h32c, M, L if pack is None else 0, W)
-    t1, so1 = out_dense(ao, b + "attention.output.dense.", h32c, cmap)
-    a32, a16 = _ln2(st, t1, b + "attention.output.LayerNorm.", eps, M, W, dtype16)
-    cq = ckv = co = lse2 = t2 = None
-    sa2 = so2 = 0
-    if cross:
-        cq = ops.linear_fwd(a16, w16(c + "query.weight"), st.p(c + "query.bias"))
-        ckv = ops.linear_fwd(img16, w16(c + "key.weight", (2 * W, img16.shape[1])), st.p(c + "key.bias", (2 * W,)))
-        sa2 = drop.next() if pa else 0
-        if half:
-            co, lse2 = ops.onequery_fwd_f16(cq, W, ckv, ckv[:, W:], 2 * W, M, Ti, heads)
-        else:
-            co, lse2 = ops.onequery_fwd(cq, W, ckv, ckv[:, W:], 2 * W, M, Ti, heads, drop_p=pa, drop_seed=sa2, drop_tq=L, drop_q=0)
-        t2, so2 = out_dense(co, b + "crossattention.output.dense.", a32, cmap)
-        c32, c16 = _ln2(st, t2, b + "crossattention.output.LayerNorm.", eps, M, W, dtype16)
-    else:
-        c32, c16 = a32, a16
-    f = torch.empty(M, I, device=dev, dtype=dtype16)
-    g = torch.empty(M, I, device=dev, dtype=dtype16)
-    ops.linear_fwd(c16, w16(b + "intermediate.dense.weight"), st.p(b + "intermediate.dense.bias"), out=f,
-                   epilogue=ops.EPI_BIAS_ACT, C2=g, act=ops.ACT_GELU_ERF)
-    t3, so3 = out_dense(g, b + "output.dense.", c32, cmap)
-    rows, _ = _ln2(st, t3, b + "output.LayerNorm.", eps, M, W, dtype16)
-    sv = dict(pooled=True, h16=h16, qkv=qkv, q=q, q_ld=q_ld, ao=ao, lse1=lse1, t1=t1, a16=a16, cq=cq, ckv=ckv, co=co, lse2=lse2, t2=t2,
-              c16=c16, f=f, t3=t3, seeds=(sa1, so1, sa2, so2, so3))
-    return rows, sv
-
-
-def _bert_last_layer_pooled_backward(st, prefix, cfg, drows, dimg, sv, stash, cross, colsum):
-    """backward of _bert_last_layer_pooled.  drows fp32 [M, W]: the gradient of the class rows.  Everything up to the self-attention
-    runs on M rows; the one-query backward writes dk | dv of EVERY key row (exact zeros behind a dense item's key_len) and dq of the
-    class rows into a zeroed [R, 3W] buffer -- the rows whose query gradient the full layer finds to be zero -- so the q | k | v
-    weight gradient and d h32 = dqkv @ Wqkv + dt1 are the full layer's products; dt1 is scattered into zeroed R rows.
-    -> d h32 fp32 [R, W]"""
-    W, I, eps = cfg["hidden_size"], cfg["intermediate_size"], cfg["layer_norm_eps"]
-    heads, i = cfg["num_attention_heads"], cfg["num_hidden_layers"] - 1
-    M, L, Ti, key_len, img16 = stash["M"], stash["L"], stash["Ti"], stash["key_len"], stash["img16"]
-    pack = stash.get("pack")
-    R, dev = (pack.R if pack is not None else M * L), drows.device
-    G = st.grad_view
-    f32 = dict(device=dev, dtype=torch.float32)
-    b16 = dict(device=dev, dtype=torch.bfloat16)
-    ph, pa = stash["ph"], stash["pa"]
-    b = f"{prefix}encoder.layer.{i}."
-    s, c = b + "attention.self.", b + "crossattention.self."
-    sa1, so1, sa2, so2, so3 = sv["seeds"]
-    cls, cmap = _class_rows(pack, M, L, dev)
-    # ---- feed-forward sublayer
-    d16 = torch.empty(M, W, **b16)
-    dt3 = ops.layernorm_bwd(sv["t3"], st.p(b + "output.LayerNorm.weight"), drows, G(b + "output.LayerNorm.weight"),
-                            G(b + "output.LayerNorm.bias"), eps, dx_bf16=d16, rows=M, width=W)
-    if ph:
-        ops.dropout_bf16_(d16, ph, so3, row_map=cmap)
-    df, g = torch.empty(M, I, **b16), torch.empty(M, I, **b16)
-    ops.linear_dgrad(d16, st.w16(b + "output.dense.weight"), out=df, aux=sv["f"], act_out=g,
-                     colsum=G(b + "intermediate.dense.bias"), act=ops.ACT_GELU_ERF)
-    ops.linear_wgrad(d16, g, G(b + "output.dense.weight"), dbias=G(b + "output.dense.bias"))
-    ops.linear_wgrad(df, sv["c16"], G(b + "intermediate.dense.weight"))
-    dc = torch.empty(M, W, **f32)
-    ops.gemm(df, st.w16(b + "intermediate.dense.weight"), dc, M, W, I, I, W, W, b_tmaj=True, epilogue=ops.EPI_RESID_F32, resid=dt3)
-    if not cross:
-        da = dc
-    else:
-        # ---- cross-attention sublayer
-        dt2 = ops.layernorm_bwd(sv["t2"], st.p(b + "crossattention.output.LayerNorm.weight"), dc,
-                                G(b + "crossattention.output.LayerNorm.weight"), G(b + "crossattention.output.LayerNorm.bias"), eps,
-                                dx_bf16=d16, rows=M, width=W)
-        if ph:
-            ops.dropout_bf16_(d16, ph, so2, row_map=cmap)
-        ops.linear_wgrad(d16, sv["co"], G(b + "crossattention.output.dense.weight"), dbias=G(b + "crossattention.output.dense.bias"))
-        dco = ops.linear_dgrad(d16, st.w16(b + "crossattention.output.dense.weight"))
-        dcq = torch.empty(M, W, **b16)
-        dckv = torch.empty(M * Ti, 2 * W, **b16)
-        ckv = sv["ckv"]
-        ops.onequery_bwd(sv["cq"], W, ckv, ckv[:, W:], 2 * W, sv["co"], dco, sv["lse2"], dcq, W, dckv, dckv[:, W:], 2 * W, M, Ti, heads,
-                         drop_p=pa, drop_seed=sa2, drop_tq=L, drop_q=0)
-        Ew = img16.shape[1]
-        ops.linear_wgrad(dckv, img16, G(c + "key.weight", (2 * W, Ew)), dbias=G(c + "key.bias", (2 * W,)))
-        ops.gemm(dckv, st.w16(c + "key.weight", (2 * W, Ew)), dimg, M * Ti, Ew, 2 * W, 2 * W, Ew, Ew, b_tmaj=True,
-                 epilogue=ops.EPI_RESID_F32, resid=dimg)
-        ops.linear_wgrad(dcq, sv["a16"], G(c + "query.weight"), dbias=G(c + "query.bias"))
-        da = torch.empty(M, W, **f32)
-        ops.gemm(dcq, st.w16(c + "query.weight"), da, M, W, W, W, W, W, b_tmaj=True, epilogue=ops.EPI_RESID_F32, resid=dt2)
-    # ---- self-attention sublayer
-    dt1 = ops.layernorm_bwd(sv["t1"], st.p(b + "attention.output.LayerNorm.weight"), da, G(b + "attention.output.LayerNorm.weight"),
-                            G(b + "attention.output.LayerNorm.bias"), eps, dx_bf16=d16, rows=M, width=W)
-    if ph:
-        ops.dropout_bf16_(d16, ph, so1, row_map=cmap)
-    ops.linear_wgrad(d16, sv["ao"], G(b + "attention.output.dense.weight"), dbias=G(b + "attention.output.dense.bias"))
-    dao = ops.linear_dgrad(d16, st.w16(b + "attention.output.dense.weight"))
-    qkv = sv["qkv"]
-    dqkv = torch.zeros(R, 3 * W, **b16)
-    if pack is None:
-        ops.onequery_bwd(qkv, L * 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, sv["ao"], dao, sv["lse1"], dqkv, L * 3 * W, dqkv[:, W:],
-                         dqkv[:, 2 * W:], 3 * W, M, L, heads, key_len=key_len, drop_p=pa, drop_seed=sa1, drop_tq=L, drop_q=0)
-    else:
-        dq = torch.empty(M, W, **b16)
-        ops.onequery_bwd(sv["q"], W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, sv["ao"], dao, sv["lse1"], dq, W, dqkv[:, W:], dqkv[:, 2 * W:],
-                         3 * W, M, L, heads, kv_row_off=pack.row_off, drop_p=pa, drop_seed=sa1, drop_tq=L, drop_q=0)
-        dqkv[cls, :W] = dq          # a copy of M rows
-    ops.linear_wgrad(dqkv, sv["h16"], G(s + "query.weight", (3 * W, W)), dbias=G(s + "query.bias", (3 * W,)))
-    dt1r = torch.zeros(R, W, **f32)
-    ops.call("uniir_scatter_rows", dt1, None if pack is None else pack.row_off, dt1r, M, L if pack is None else 0, W)
-    do = torch.empty(R, W, **f32)
-    ops.gemm(dqkv, st.w16(s + "query.weight", (3 * W, W)), do, R, W, 3 * W, 3 * W, W, W, b_tmaj=True, epilogue=ops.EPI_RESID_F32,
-             resid=dt1r)
-    return do
-
-
 def bert_backward(st, prefix, cfg, dpooled, stash, cross=True, pool=True):
     """returns d(img tokens) fp32 [M*Ti, enc_width] (None without cross-attention); parameter gradients accumulate into
     st.g32.  dpooled: gradient of what bert_forward returned (pooler output, or the class-token rows with pool=False)"""
-    W, I, eps = cfg["hidden_size"], cfg["intermediate_size"], cfg["layer_norm_eps"]
-    heads, layers = cfg["num_attention_heads"], cfg["num_hidden_layers"]
-    M, L, Ti, key_len, img16 = stash["M"], stash["L"], stash["Ti"], stash["key_len"], stash["img16"]
-    pack = stash.get("pack")
-    R, dev = (pack.R if pack is not None else M * L), dpooled.device
-    G = st.grad_view
-    f32 = dict(device=dev, dtype=torch.float32)
-    b16 = dict(device=dev, dtype=torch.bfloat16)
-
-    def colsum(x, cols, name, shape=None):
-        ops.call("uniir_colsum_bf16", x, cols, G(name, shape), x.shape[0], cols)
-
-    if not pool:
-        drows = dpooled.contiguous().float()
-    else:
-        drows = _pooler_backward(st, prefix, dpooled, stash, M, W, colsum)
-    if stash["layers"][-1].get("pooled"):
-        do = drows          # the last layer ran on the class rows: the scatter to R rows happens below it (_bert_layers_backward)
-    else:
-        do = torch.zeros(R, W, **f32)
-        if pack is None:
-            ops.call("uniir_scatter_rows", drows, None, do, M, L, W)
-        else:
-            ops.call("uniir_scatter_rows", drows, pack.row_off, do, M, 0, W)
-    dimg = torch.zeros(M * Ti, img16.shape[1], **f32) if cross else None
-    g = torch.empty(R, I, **b16) if not (layers == 1 and stash["layers"][-1].get("pooled")) else None
-    return _bert_layers_backward(st, prefix, cfg, do, dimg, g, stash, cross, colsum)
-
-
-def _pooler_backward(st, prefix, dpooled, stash, M, W, colsum):
-    dev = dpooled.device
-    G = st.grad_view
-    f32 = dict(device=dev, dtype=torch.float32)
-    b16 = dict(device=dev, dtype=torch.bfloat16)
-    # pooler: pooled = tanh(rows @ Wp^T + bp)
-    dpre = torch.empty(M, W, **f32)
-    ops.call("uniir_tanh_bwd", stash["pooled"], dpooled.contiguous(), dpre, dpre.numel())
-    dpre16 = torch.empty(M, W, **b16)
-    ops.call("uniir_cast_f32_to_bf16", dpre, dpre16, dpre.numel())
-    ops.linear_wgrad(dpre16, stash["rows16"], G(prefix + "pooler.dense.weight"))
-    colsum(dpre16, W, prefix + "pooler.dense.bias")
-    drows = torch.empty(M, W, **f32)
-    ops.gemm(dpre16, st.w16(prefix + "pooler.dense.weight"), drows, M, W, W, W, W, W, b_tmaj=True, epilogue=ops.EPI_F32)
-    return drows
-
-
-def _bert_layers_backward(st, prefix, cfg, do, dimg, g, stash, cross, colsum):
-    W, I, eps = cfg["hidden_size"], cfg["intermediate_size"], cfg["layer_norm_eps"]
-    heads, layers = cfg["num_attention_heads"], cfg["num_hidden_layers"]
-    M, L, Ti, key_len, img16 = stash["M"], stash["L"], stash["Ti"], stash["key_len"], stash["img16"]
-    pack = stash.get("pack")
-    R, dev = (pack.R if pack is not None else M * L), do.device
-    roff = pack.row_off if pack is not None else None
-    rmap = pack.row_map if pack is not None else None
-    self_kw = dict(key_len=key_len) if pack is None else dict(row_off=roff, kv_packed=True)
-    cross_kw = {} if pack is None else dict(row_off=roff, kv_packed=False)
-    G = st.grad_view
-    f32 = dict(device=dev, dtype=torch.float32)
-    b16 = dict(device=dev, dtype=torch.bfloat16)
-    ph, pa = stash["ph"], stash["pa"]
-    for i in reversed(range(layers)):
-        b = f"{prefix}encoder.layer.{i}."
-        s, c = b + "attention.self.", b + "crossattention.self."
+    cx = _BertCall.of_stash(st, prefix, cfg, stash, cross)
+    G, M, L, W = st.grad_view, cx.M, cx.L, cx.W
+    class_rows = _ClassRows(cx)
+    do = _pooler_backward(cx, dpooled, stash) if pool else dpooled.contiguous().float()
+    if not stash["layers"][-1].get("pooled"):          # else the last layer ran on the class rows and takes their gradient as it is
+        do = class_rows.spread(do)
+    dimg = cx.f32(M * cx.Ti, cx.img16.shape[1], zero=True) if cross else None
+    all_rows = _AllRows(cx, sum(not sv.get("pooled") for sv in stash["layers"]))
+    for i in reversed(range(cx.layers)):
         sv = stash["layers"][i]
         stash["layers"][i] = None
-        if sv.get("pooled"):          # the last layer on the class rows: do is [M, W] coming in, [R, W] going out
-            do = _bert_last_layer_pooled_backward(st, prefix, cfg, do, dimg, sv, stash, cross, colsum)
-            continue
-        sa1, so1, sa2, so2, so3 = sv["seeds"]
-        # ---- feed-forward sublayer: o = LN(g @ Wout^T + bout + c32), g = gelu(c16 @ Wi^T + bi)
-        d16 = torch.empty(R, W, **b16)
-        dt3 = ops.layernorm_bwd(sv["t3"], st.p(b + "output.LayerNorm.weight"), do, G(b + "output.LayerNorm.weight"),
-                                G(b + "output.LayerNorm.bias"), eps, dx_bf16=d16, rows=R, width=W)
-        if ph:      # the dense branch sees the masked gradient, the residual branch (dt3, fp32) the full one
-            ops.dropout_bf16_(d16, ph, so3, row_map=rmap)
-        df = torch.empty(R, I, **b16)
-        ops.linear_dgrad(d16, st.w16(b + "output.dense.weight"), out=df, aux=sv["f"], act_out=g,
-                         colsum=G(b + "intermediate.dense.bias"), act=ops.ACT_GELU_ERF)
-        ops.linear_wgrad(d16, g, G(b + "output.dense.weight"), dbias=G(b + "output.dense.bias"))
-        ops.linear_wgrad(df, sv["c16"], G(b + "intermediate.dense.weight"))
-        dc = torch.empty(R, W, **f32)       # d c32 = df @ Wi + dt3 (the residual branch)
-        ops.gemm(df, st.w16(b + "intermediate.dense.weight"), dc, R, W, I, I, W, W, b_tmaj=True,
-                 epilogue=ops.EPI_RESID_F32, resid=dt3)
-        if not cross:
-            da = dc                      # mode "text": c32 is a32
-        else:
-            # ---- cross-attention sublayer: c = LN(co @ Wco^T + bco + a32)
-            dt2 = ops.layernorm_bwd(sv["t2"], st.p(b + "crossattention.output.LayerNorm.weight"), dc,
-                                    G(b + "crossattention.output.LayerNorm.weight"),
-                                    G(b + "crossattention.output.LayerNorm.bias"), eps, dx_bf16=d16, rows=R, width=W)
-            if ph:
-                ops.dropout_bf16_(d16, ph, so2, row_map=rmap)
-            ops.linear_wgrad(d16, sv["co"], G(b + "crossattention.output.dense.weight"),
-                             dbias=G(b + "crossattention.output.dense.bias"))
-            dco = ops.linear_dgrad(d16, st.w16(b + "crossattention.output.dense.weight"))
-            dcq = torch.empty(R, W, **b16)
-            dckv = torch.empty(M * Ti, 2 * W, **b16)
-            ckv = sv["ckv"]
-            ops.attention_bwd_ex(sv["cq"], W, ckv, ckv[:, W:], 2 * W, sv["co"], dco, sv["lse2"], dcq, W, dckv, dckv[:, W:],
-                                 2 * W, M, L, Ti, heads, drop_p=pa, drop_seed=sa2, **cross_kw)
-            Ew = img16.shape[1]
-            ops.linear_wgrad(dckv, img16, G(c + "key.weight", (2 * W, Ew)), dbias=G(c + "key.bias", (2 * W,)))
-            ops.gemm(dckv, st.w16(c + "key.weight", (2 * W, Ew)), dimg, M * Ti, Ew, 2 * W, 2 * W, Ew, Ew, b_tmaj=True,
-                     epilogue=ops.EPI_RESID_F32, resid=dimg)          # dimg += dckv @ Wkv (in place: same element r/w)
-            ops.linear_wgrad(dcq, sv["a16"], G(c + "query.weight"), dbias=G(c + "query.bias"))
-            da = torch.empty(R, W, **f32)       # d a32 = dcq @ Wcq + dt2
-            ops.gemm(dcq, st.w16(c + "query.weight"), da, R, W, W, W, W, W, b_tmaj=True, epilogue=ops.EPI_RESID_F32,
-                     resid=dt2)
-        # ---- self-attention sublayer: a = LN(ao @ Wo^T + bo + h32)
-        dt1 = ops.layernorm_bwd(sv["t1"], st.p(b + "attention.output.LayerNorm.weight"), da,
-                                G(b + "attention.output.LayerNorm.weight"), G(b + "attention.output.LayerNorm.bias"),
-                                eps, dx_bf16=d16, rows=R, width=W)
-        if ph:
-            ops.dropout_bf16_(d16, ph, so1, row_map=rmap)
-        ops.linear_wgrad(d16, sv["ao"], G(b + "attention.output.dense.weight"), dbias=G(b + "attention.output.dense.bias"))
-        dao = ops.linear_dgrad(d16, st.w16(b + "attention.output.dense.weight"))
-        qkv = sv["qkv"]
-        dqkv = torch.empty(R, 3 * W, **b16)
-        ops.attention_bwd_ex(qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, sv["ao"], dao, sv["lse1"], dqkv, 3 * W,
-                             dqkv[:, W:], dqkv[:, 2 * W:], 3 * W, M, L, L, heads, drop_p=pa, drop_seed=sa1, **self_kw)
-        ops.linear_wgrad(dqkv, sv["h16"], G(s + "query.weight", (3 * W, W)), dbias=G(s + "query.bias", (3 * W,)))
-        do = torch.empty(R, W, **f32)       # d h32 = dqkv @ Wqkv + dt1
-        ops.gemm(dqkv, st.w16(s + "query.weight", (3 * W, W)), do, R, W, 3 * W, 3 * W, W, W, b_tmaj=True,
-                 epilogue=ops.EPI_RESID_F32, resid=dt1)
-    if ph:
-        ops.dropout_f32(do, ph, stash["s_emb"], out_f32=do, row_map=rmap)
+        do = _layer_backward(cx, class_rows if sv.get("pooled") else all_rows, i, sv, do, dimg)
+    if cx.ph:
+        ops.dropout_f32(do, cx.ph, stash["s_emb"], out_f32=do, row_map=cx.rmap)
     de = ops.layernorm_bwd(stash["e32"], st.p(prefix + "embeddings.LayerNorm.weight"), do,
-                           G(prefix + "embeddings.LayerNorm.weight"), G(prefix + "embeddings.LayerNorm.bias"), eps,
-                           rows=R, width=W)
-    if pack is None:
-        ops.call("uniir_text_embed_bwd", stash["ids"], de, G(prefix + "embeddings.word_embeddings.weight"),
-                 G(prefix + "embeddings.position_embeddings.weight"), M, L, W, cfg["vocab_size"])
+                           G(prefix + "embeddings.LayerNorm.weight"), G(prefix + "embeddings.LayerNorm.bias"), cx.eps,
+                           rows=cx.R, width=W)
+    dword, dpos = G(prefix + "embeddings.word_embeddings.weight"), G(prefix + "embeddings.position_embeddings.weight")
+    if cx.pack is None:
+        ops.call("uniir_text_embed_bwd", stash["ids"], de, dword, dpos, M, L, W, cx.vocab)
     else:
-        ops.call("uniir_text_embed_bwd_packed", stash["ids"], de, roff, G(prefix + "embeddings.word_embeddings.weight"),
-                 G(prefix + "embeddings.position_embeddings.weight"), M, L, W, cfg["vocab_size"])
+        ops.call("uniir_text_embed_bwd_packed", stash["ids"], de, cx.roff, dword, dpos, M, L, W, cx.vocab)
     return dimg
+
+
+def _pooler_backward(cx, dpooled, stash):
+    """pooler: pooled = tanh(rows @ Wp^T + bp) -> the gradient of the class rows fp32 [M, W]"""
+    st, G, M, W, name = cx.st, cx.st.grad_view, cx.M, cx.W, cx.prefix + "pooler.dense."
+    dpre = cx.f32(M, W)
+    ops.call("uniir_tanh_bwd", stash["pooled"], dpooled.contiguous(), dpre, dpre.numel())
+    dpre16 = cx.b16(M, W)
+    ops.call("uniir_cast_f32_to_bf16", dpre, dpre16, dpre.numel())
+    ops.linear_wgrad(dpre16, stash["rows16"], G(name + "weight"))
+    ops.call("uniir_colsum_bf16", dpre16, W, G(name + "bias"), M, W)
+    drows = cx.f32(M, W)
+    ops.gemm(dpre16, st.w16(name + "weight"), drows, M, W, W, W, W, W, b_tmaj=True, epilogue=ops.EPI_F32)
+    return drows
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -1036,8 +991,9 @@ class BLIPFeatureFusion(nn.Module):
                                "only (use_momentum=True needs precision='bf16')")
         return True
 
-    def encode_multimodal_input(self, txt_dict_batched, image_batched, txt_mask=None, img_mask=None, use_momentum=False):
-        """blip_ff.py:82-116: BERT(text) cross-attending to ViT(image) tokens -> pooler_output [n, embed_dim]"""
+    def _encode_inputs(self, txt_dict_batched, use_momentum):
+        """what every encode call starts with: the stores brought up to date, the token ids and key lengths, the TextPack
+        -> half (_embed_half), ids, key_len, pack; last_text_rows = (BERT rows run, rows of the padded batch)"""
         half = self._embed_half(use_momentum)
         if half:
             self._sync_half()          # _sync() plus the fp16 copies
@@ -1046,6 +1002,11 @@ class BLIPFeatureFusion(nn.Module):
         ids, key_len = self._text_inputs(txt_dict_batched)
         pack = self._text_pack(txt_dict_batched, key_len, ids.shape[1])
         self.last_text_rows = (pack.R if pack is not None else ids.numel(), ids.numel())
+        return half, ids, key_len, pack
+
+    def encode_multimodal_input(self, txt_dict_batched, image_batched, txt_mask=None, img_mask=None, use_momentum=False):
+        """blip_ff.py:82-116: BERT(text) cross-attending to ViT(image) tokens -> pooler_output [n, embed_dim]"""
+        half, ids, key_len, pack = self._encode_inputs(txt_dict_batched, use_momentum)
         if half:
             with torch.no_grad():
                 st = self._online
@@ -1202,14 +1163,7 @@ class BLIPScoreFusion(BLIPFeatureFusion):
         return emb, stash
 
     def encode_multimodal_input(self, txt_dict_batched, image_batched, txt_mask=None, img_mask=None, use_momentum=False):
-        half = self._embed_half(use_momentum)
-        if half:
-            self._sync_half()          # _sync() plus the fp16 copies
-        else:
-            self._sync()
-        ids, key_len = self._text_inputs(txt_dict_batched)
-        pack = self._text_pack(txt_dict_batched, key_len, ids.shape[1])
-        self.last_text_rows = (pack.R if pack is not None else ids.numel(), ids.numel())
+        half, ids, key_len, pack = self._encode_inputs(txt_dict_batched, use_momentum)
         M = ids.shape[0]
         dev = ids.device
         ones = torch.ones(M, dtype=torch.int64, device=dev)
