@@ -37,7 +37,8 @@ const char* uniir_strerror(int code);
 /* ABI version; bumped on any signature or struct-layout change (3: uniir_clip_tower.recompute; 4: uniir_reduce_stats;
  * 5: uniir_image_*; 6: uniir_attention_fwd_long / _bwd_long; still 6, new entry points only: uniir_attention_rel_fwd_long /
  * _rel_bwd_long; uniir_attention_one_fwd / _one_bwd, and the value 2 of uniir_clip_tower.pool_last_block; uniir_layernorm_fwd_f16,
- * uniir_patchify_f16, uniir_vit_assemble_f16: no layout changes). */
+ * uniir_patchify_f16, uniir_vit_assemble_f16: no layout changes; 7: uniir_attn_rel_fwd_f16, uniir_attn_rel_fwd_long_f16 and
+ * uniir_rmsnorm_fwd_f16 -- new entry points only, a caller that needs them asks for >= 7). */
 int uniir_abi_version(void);
 /* Reproducible reductions (round 6).  Bias, LayerNorm-weight and token-embedding gradients are sums over every row of a batch taken by
  * many workgroups; added with fp32 atomics they depend on the arrival order, and two runs of one training step differ in their last
@@ -180,7 +181,8 @@ int uniir_layernorm_bwd_ex(const float* x, int64_t x_stride, const float* gamma,
  *   On fp16 tensors (forward only): uniir_attention_fwd_f16 with the limits of uniir_attention_fwd / _fwd_packed (causal = 0 and
  *   dense rows: seq <= 1024, the BLIP ViT at 384 pixels; else 512), uniir_attention_one_fwd with f16 = 1, and the general form
  *   (_ex, _rows, _long without the causal mask and dropout) as uniir_attn_general_fwd_f16 with its one-query form
- *   uniir_onequery_fwd_f16: the BLIP MED BERT's eval-mode forward.  There is no fp16 backward.
+ *   uniir_onequery_fwd_f16: the BLIP MED BERT's eval-mode forward; the relative bias as uniir_attn_rel_fwd_f16 (seq <= 512) and
+ *   uniir_attn_rel_fwd_long_f16 (seq <= 1024): the CLIP_FF fusion stack's eval-mode forward.  There is no fp16 backward.
  * qkv bf16 [batch*seq][3*heads*64] as produced by nn.MultiheadAttention.in_proj ([q | k | v] per row);
  * out bf16 [batch*seq][heads*64]; lse f32 [batch][heads][seq] (natural log-sum-exp of scaled scores).
  * causal = 1 applies CLIP's build_attention_mask (key <= query).
@@ -678,6 +680,20 @@ int uniir_attention_rel_fwd_long(const void* qkv, void* out, float* lse, const f
 int uniir_attention_rel_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                  const float* rel_emb, const int32_t* rel_bucket, int32_t nbuckets, float scale, float* drel,
                                  int32_t batch, int32_t seq, int32_t heads, float drop_p, uint32_t drop_seed, void* stream);
+/* The fp16 forward of the stack (eval mode only: no dropout arguments; there is no fp16 backward).
+ * uniir_rmsnorm_fwd_f16: uniir_rmsnorm_fwd with an fp16 16-bit output -- y_f32 has the bits of uniir_rmsnorm_fwd's, y_f16 is that fp32
+ * value rounded once to fp16 (round to nearest even; beyond 65504 it becomes inf, as in every fp16 kernel here: nothing is clamped).
+ * uniir_attn_rel_fwd_f16 / uniir_attn_rel_fwd_long_f16: uniir_attention_rel_fwd / _rel_fwd_long without dropout on fp16 qkv / out
+ * (lse and rel_emb stay fp32): 1 <= seq <= 512 on the resident kernel, 1 <= seq <= 1024 on the streaming kernel at every size.  The
+ * same codes for the same conditions as their bf16 twins (the resident form tests no alignment, the streaming one refuses a qkv or
+ * out that is not 16-byte aligned with UNIIR_EALIGN); a refused call writes nothing; batch == 0 is UNIIR_OK.  The names start with
+ * uniir_attn_, not uniir_attention_: the set of uniir_attention_* entry points is closed. */
+int uniir_rmsnorm_fwd_f16(const float* x, int64_t x_stride, const float* gamma, void* y_f16, float* y_f32, int32_t rows,
+                          int32_t width, float eps, void* stream);
+int uniir_attn_rel_fwd_f16(const void* qkv, void* out, float* lse, const float* rel_emb, const int32_t* rel_bucket,
+                           int32_t nbuckets, float scale, int32_t batch, int32_t seq, int32_t heads, void* stream);
+int uniir_attn_rel_fwd_long_f16(const void* qkv, void* out, float* lse, const float* rel_emb, const int32_t* rel_bucket,
+                                int32_t nbuckets, float scale, int32_t batch, int32_t seq, int32_t heads, void* stream);
 int uniir_meanpool_fwd(const float* x, float* out, int32_t n, int32_t tokens, int32_t width, void* stream);
 int uniir_meanpool_bwd(const float* dout, float* dx, int32_t n, int32_t tokens, int32_t width, void* stream);
 

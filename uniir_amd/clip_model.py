@@ -248,6 +248,20 @@ class CLIP(nn.Module):
             self._h16_version = ver
         return st
 
+    def _sync_half_flat(self):
+        """_sync_shadow() plus the fp16 copies the per-op towers of CLIP_FF read under fp16 (clipff_model, dtype16 = torch.float16):
+        the store's own fp16 shadow (FlatStore.w16h) and the fp16 twin of _conv16.  Built on first use, rebuilt whenever the bf16
+        shadow was refreshed or a kernel moved the master weights (FlatStore.half_stale).  -> the store"""
+        st = self._sync_shadow()
+        conv = getattr(self, "_conv16h", None)
+        if conv is None or conv.device != st.dev or st.h16_buf is None or st.half_stale:
+            if conv is None or conv.device != st.dev:
+                self._conv16h = torch.zeros(self.cfg["vision_width"], self.kpad, device=st.dev, dtype=torch.float16)
+            vw, P = self.cfg["vision_width"], self.cfg["vision_patch_size"]
+            ops.call("uniir_cast_pad_rows_f16", self.visual.conv1.weight.data, self._conv16h, vw, 3 * P * P, self.kpad)
+        st.half_shadow()
+        return st
+
     def _refresh_conv(self):
         vw, P = self.cfg["vision_width"], self.cfg["vision_patch_size"]
         ops.call("uniir_cast_pad_rows", self.visual.conv1.weight.data, self._conv16, vw, 3 * P * P, self.kpad)

@@ -6,7 +6,12 @@ un-scaled attention with bucketed relative position bias, ReLU feed-forward, no 
 All arithmetic is in libuniir_hip.so; this file is the launch sequence + the flat store of the T5 parameters (state-dict
 keys `t5_layers.block.{i}.layer.{0,1}...` of transformers).  In train mode the T5 dropout sites (dropout_rate 0.1: stack
 input, attention probabilities, attention output, after the ReLU, feed-forward output, after the final norm) are applied
-with counter-based masks regenerated in backward (ops.DropSeeds); the CLIP towers have no dropout."""
+with counter-based masks regenerated in backward (ops.DropSeeds); the CLIP towers have no dropout.
+
+dtype16 = torch.float16 (t5_forward, vision_tokens_fwd, text_tokens_fwd): the eval-mode embedding forward with fp16 16-bit
+activations and weights from the stores' fp16 shadows (FlatStore.w16h) -- the same launch sequence, the fp16 twins of the entry
+points (uniir_rmsnorm_fwd_f16, uniir_attn_rel_fwd_f16 / _long_f16, UNIIR_DT_F16 GEMMs); the residual stream, the norm statistics,
+visual.proj's output, the final norm, the mean pool and the embedding stay fp32.  Forward only: no stash, no dropout."""
 import math
 
 import torch
@@ -62,16 +67,35 @@ def _rel_entry(which, T):
     return f"uniir_attention_rel_{which}" + ("_long" if T > ops.ATT_RESIDENT_MAX else "")
 
 
-def _rms(st, x, name, R, D, out_f32=False):
-    y16 = torch.empty(R, D, device=x.device, dtype=torch.bfloat16) if not out_f32 else None
+def _rms(st, x, name, R, D, out_f32=False, dtype16=torch.bfloat16):
+    y16 = torch.empty(R, D, device=x.device, dtype=dtype16) if not out_f32 else None
     y32 = torch.empty(R, D, device=x.device, dtype=torch.float32) if out_f32 else None
+    if dtype16 == torch.float16:          # the fp32 output too: the fp16 forward stays on its own entry point
+        ops.rmsnorm_fwd(x, st.p(name), T5_EPS, out_bf16=y16, out_f32=y32, rows=R, width=D, x_stride=D, dtype16=dtype16)
+        return y32 if out_f32 else y16
     ops.call("uniir_rmsnorm_fwd", x, D, st.p(name), y16, y32, R, D, T5_EPS)
     return y32 if out_f32 else y16
 
 
-def t5_forward(st, prefix, x, M, T, heads, layers, save, drop=None, p=T5_DROPOUT):
+def _check_dtype16(what, dtype16, save, drop=None):
+    """the fp16 forward keeps nothing for a backward and takes no dropout: anything else raises before a launch -> is it fp16?"""
+    if dtype16 not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"dtype16 is torch.bfloat16 or torch.float16, not {dtype16!r}")
+    if dtype16 == torch.float16:
+        if save:
+            raise RuntimeError(f"the fp16 {what} keeps nothing for a backward (save=True needs dtype16=torch.bfloat16)")
+        if drop is not None:
+            raise RuntimeError(f"the fp16 {what} is the eval-mode embedding path: no dropout (drop needs dtype16=torch.bfloat16)")
+    return dtype16 == torch.float16
+
+
+def t5_forward(st, prefix, x, M, T, heads, layers, save, drop=None, p=T5_DROPOUT, dtype16=torch.bfloat16):
     """x fp32 [M*T, D] (the concatenated tokens; overwritten by its dropped version in train mode) -> pooled fp32 [M, D]
-    (+ stash).  drop: ops.DropSeeds in train mode, None in eval mode"""
+    (+ stash).  drop: ops.DropSeeds in train mode, None in eval mode.
+    dtype16 = torch.float16 (eval mode, save False, drop None; anything else raises before a launch): the same sequence with fp16
+    buffers, the weights from st's fp16 shadow, uniir_rmsnorm_fwd_f16 and ops.attention_rel_fwd_f16"""
+    half = _check_dtype16("T5 forward", dtype16, save, drop)
+    w16 = st.w16h if half else st.w16
     R, D = x.shape
     inner = heads * 64
     dev = x.device
@@ -95,26 +119,29 @@ def t5_forward(st, prefix, x, M, T, heads, layers, save, drop=None, p=T5_DROPOUT
 
     for i in range(layers):
         a, f = f"{prefix}block.{i}.layer.0.", f"{prefix}block.{i}.layer.1."
-        h1 = _rms(st, x, a + "layer_norm.weight", R, D)
-        qkv = ops.linear_fwd(h1, st.w16(a + "SelfAttention.q.weight", (3 * inner, D)))
-        ao = torch.empty(R, inner, device=dev, dtype=torch.bfloat16)
-        lse = torch.empty(M, heads, T, device=dev, dtype=torch.float32)
+        h1 = _rms(st, x, a + "layer_norm.weight", R, D, dtype16=dtype16)
+        qkv = ops.linear_fwd(h1, w16(a + "SelfAttention.q.weight", (3 * inner, D)))
         sa = nxt()
-        ops.call(_rel_entry("fwd", T), qkv, ao, lse, rel, table, T5_BUCKETS, 1.0, M, T, heads, p, sa)
-        x2, so = branch(ao, st.w16(a + "SelfAttention.o.weight"), x)
-        h2 = _rms(st, x2, f + "layer_norm.weight", R, D)
-        wi = st.w16(f + "DenseReluDense.wi.weight")
-        ff = torch.empty(R, wi.shape[0], device=dev, dtype=torch.bfloat16)
-        g = torch.empty(R, wi.shape[0], device=dev, dtype=torch.bfloat16)
+        if half:
+            ao, lse = ops.attention_rel_fwd_f16(qkv, rel, table, M, T, heads, 1.0)
+        else:
+            ao = torch.empty(R, inner, device=dev, dtype=torch.bfloat16)
+            lse = torch.empty(M, heads, T, device=dev, dtype=torch.float32)
+            ops.call(_rel_entry("fwd", T), qkv, ao, lse, rel, table, T5_BUCKETS, 1.0, M, T, heads, p, sa)
+        x2, so = branch(ao, w16(a + "SelfAttention.o.weight"), x)
+        h2 = _rms(st, x2, f + "layer_norm.weight", R, D, dtype16=dtype16)
+        wi = w16(f + "DenseReluDense.wi.weight")
+        ff = torch.empty(R, wi.shape[0], device=dev, dtype=dtype16)
+        g = torch.empty(R, wi.shape[0], device=dev, dtype=dtype16)
         ops.linear_fwd(h2, wi, out=ff, epilogue=ops.EPI_BIAS_ACT, C2=g, act=ops.ACT_RELU)
         sg = nxt()
         if p:
             ops.dropout_bf16_(g, p, sg)
-        xn, sf = branch(g, st.w16(f + "DenseReluDense.wo.weight"), x2)
+        xn, sf = branch(g, w16(f + "DenseReluDense.wo.weight"), x2)
         if save:
             saved.append((x, h1, qkv, ao, lse, x2, h2, ff, (sa, so, sg, sf)))
         x = xn
-    y = _rms(st, x, prefix + "final_layer_norm.weight", R, D, out_f32=True)
+    y = _rms(st, x, prefix + "final_layer_norm.weight", R, D, out_f32=True, dtype16=dtype16)
     s_fin = nxt()
     if p:
         ops.dropout_f32(y, p, s_fin, out_f32=y)
@@ -198,8 +225,10 @@ def _recompute_from(model, which, save, M, R, W, heads, L):
     return 0
 
 
-def vision_tokens_fwd(model, image, save):
-    """clip_ff.py:35-59 -> fp32 [M*T, E] = ln_post(all tokens) @ proj"""
+def vision_tokens_fwd(model, image, save, dtype16=torch.bfloat16):
+    """clip_ff.py:35-59 -> fp32 [M*T, E] = ln_post(all tokens) @ proj.  dtype16 = torch.float16 (save False): fp16 patches, blocks
+    and ln_post output from the fp16 copies of the weights (CLIP._sync_half_flat() made them); the tokens stay fp32 (EPI_F32)"""
+    half = _check_dtype16("vision tower", dtype16, save)
     cfg, st = model.cfg, model._flat
     dev = image.device
     M = image.shape[0]
@@ -208,19 +237,21 @@ def vision_tokens_fwd(model, image, save):
     T = G_ + 1
     heads = W // 64
     p32 = st.p
-    patches = torch.empty(M * G_, model.kpad, device=dev, dtype=torch.bfloat16)
-    ops.call("uniir_patchify", image.float().contiguous(), patches, M, res, P, model.kpad)
-    po = ops.linear_fwd(patches, model._conv16)
+    patches = torch.empty(M * G_, model.kpad, device=dev, dtype=dtype16)
+    ops.call("uniir_patchify_f16" if half else "uniir_patchify", image.float().contiguous(), patches, M, res, P, model.kpad)
+    po = ops.linear_fwd(patches, model._conv16h if half else model._conv16)
     x0 = torch.empty(M * T, W, device=dev, dtype=torch.float32)
-    ops.call("uniir_vit_assemble", po, p32("visual.class_embedding"), p32("visual.positional_embedding"), x0, M, T, W)
+    ops.call("uniir_vit_assemble_f16" if half else "uniir_vit_assemble", po, p32("visual.class_embedding"),
+             p32("visual.positional_embedding"), x0, M, T, W)
     del po
     x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
     ops.layernorm_fwd(x0, p32("visual.ln_pre.weight"), p32("visual.ln_pre.bias"), out_f32=x, rows=M * T, width=W)
     x, saved = tower_fwd(st, lambda i: clip_block_names("visual.transformer", i), L, x, M, T, W, heads, False, save,
-                         recompute_from=_recompute_from(model, "image", save, M, M * T, W, heads, L))
-    ln = ops.layernorm_fwd(x, p32("visual.ln_post.weight"), p32("visual.ln_post.bias"), rows=M * T, width=W)
+                         recompute_from=_recompute_from(model, "image", save, M, M * T, W, heads, L), dtype16=dtype16)
+    ln = ops.layernorm_fwd(x, p32("visual.ln_post.weight"), p32("visual.ln_post.bias"), rows=M * T, width=W, dtype16=dtype16)
     tok = torch.empty(M * T, E, device=dev, dtype=torch.float32)
-    ops.gemm(ln, st.w16("visual.proj"), tok, M * T, E, W, W, E, E, b_tmaj=True, epilogue=ops.EPI_F32)
+    ops.gemm(ln, (st.w16h if half else st.w16)("visual.proj"), tok, M * T, E, W, W, E, E, b_tmaj=True, epilogue=ops.EPI_F32,
+             dtype=ops.DT_F16 if half else ops.DT_BF16)
     stash = dict(patches=patches, x0=x0, saved=saved, xf=x, ln=ln, M=M, T=T) if save else None
     return tok, T, stash
 
@@ -253,8 +284,9 @@ def vision_tokens_bwd(model, dtok, stash):
     ops.call("uniir_unpad_add", model._dconv, G("visual.conv1.weight"), W, 3 * P * P, model.kpad)
 
 
-def text_tokens_fwd(model, text, save):
-    """clip_ff.py:148-156 -> fp32 [M*77, W] = ln_final(all tokens)"""
+def text_tokens_fwd(model, text, save, dtype16=torch.bfloat16):
+    """clip_ff.py:148-156 -> fp32 [M*77, W] = ln_final(all tokens).  dtype16 = torch.float16 (save False): the causal blocks in fp16"""
+    _check_dtype16("text tower", dtype16, save)
     cfg, st = model.cfg, model._flat
     dev = text.device
     M = text.shape[0]
@@ -265,7 +297,7 @@ def text_tokens_fwd(model, text, save):
     ops.call("uniir_text_embed", text, p32("token_embedding.weight"), p32("positional_embedding"), x, eot, M, T, W,
              cfg["vocab_size"])
     x, saved = tower_fwd(st, lambda i: clip_block_names("transformer", i), L, x, M, T, W, heads, True, save,
-                         recompute_from=_recompute_from(model, "text", save, M, M * T, W, heads, L))
+                         recompute_from=_recompute_from(model, "text", save, M, M * T, W, heads, L), dtype16=dtype16)
     tok = torch.empty(M * T, W, device=dev, dtype=torch.float32)
     ops.layernorm_fwd(x, p32("ln_final.weight"), p32("ln_final.bias"), out_f32=tok, rows=M * T, width=W)
     stash = dict(text=text, saved=saved, xf=x, M=M, T=T) if save else None
@@ -294,14 +326,16 @@ class FusionFn(torch.autograd.Function):
     def forward(ctx, owner, text, image, anchor):
         save = bool(ctx.needs_input_grad[3])
         clip, st = owner.clip_model, owner._t5
-        ttok, Tt, tst = text_tokens_fwd(clip, text, save)
-        itok, Ti, ist = vision_tokens_fwd(clip, image, save)
+        # the owner's precision (CLIPFeatureFusion._embed_half() has refused what fp16 cannot serve): "fp16" = the embedding forward
+        dt = torch.float16 if owner.precision == "fp16" else torch.bfloat16
+        ttok, Tt, tst = text_tokens_fwd(clip, text, save, dtype16=dt)
+        itok, Ti, ist = vision_tokens_fwd(clip, image, save, dtype16=dt)
         M, D = text.shape[0], ttok.shape[1]
         x = torch.cat([ttok.view(M, Tt, D), itok.view(M, Ti, D)], dim=1).view(M * (Tt + Ti), D)     # a copy, no arithmetic
         del ttok, itok
         drop = ops.DropSeeds() if owner.training and owner.t5_dropout > 0 else None
         pooled, fst = t5_forward(st, "", x, M, Tt + Ti, owner.t5_heads, owner.t5_layers_n, save, drop=drop,
-                                 p=owner.t5_dropout)
+                                 p=owner.t5_dropout, dtype16=dt)
         ctx.owner, ctx.stashes, ctx.dims = owner, (tst, ist, fst), (M, Tt, Ti, D)
         return pooled
 

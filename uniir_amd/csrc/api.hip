@@ -17,4 +17,4 @@ extern "C" const char* uniir_strerror(int code) {
 // 4: new entry point uniir_reduce_stats
 // 5: new entry points uniir_image_batch_plan, uniir_image_preprocess_batch (uniir_image_desc / _plan / _batch_info)
 // 6: new entry points uniir_attention_fwd_long, uniir_attention_bwd_long
-extern "C" int uniir_abi_version(void) { return 6; }
+extern "C" int uniir_abi_version(void) { return 7; }

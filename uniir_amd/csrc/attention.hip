@@ -19,7 +19,11 @@ extern "C" void uniir_exp_attn_set(void* stamps, int mode) { g_att_stamps = (uns
 #endif
 
 // F16: q / k / v / out are fp16 instead of bf16 (plain or causal forward of the fp16 embedding towers; P <= 2^8 by the deferred
-// maximum, well inside fp16's range)
+// maximum, well inside fp16's range).  With REL (uniir_attn_rel_fwd_f16) the bound is the same one: scale and bias are folded into the
+// logit before the deferred maximum is tested (es = 1, the logit is in log2 units), a row's reference moves as soon as one of its own
+// logits exceeds it by more than ATT_DEFER, and the exponent taken afterwards is logit - m_run <= ATT_DEFER whatever scale or rel_emb
+// hold -- P <= 2^8 again.  At the other end fp16 keeps fewer bits of a P below 2^-14 (subnormal) and none below 2^-25; the row sum l
+// (fp32) has counted such a P before it is packed, and the error it leaves in O is absolute, at most 2^-25 per key of |v|.
 template <bool REL, bool DROP, bool F16 = false>
 __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -511,8 +515,9 @@ static int launch_attn_fwd(const AttnArgs& a0, int batch, hipStream_t st, bool f
         if (!drop) return att_launch<attn_fwd_kernel<true, false>>(big, g, b, sm, st, a);
         return att_launch<attn_fwd_kernel<true, true>>(big, g, b, sm, st, a);
     }
-    // the fp16 forward of the embedding towers: plain / causal / packed rows only
-    if (a.rel_emb || drop) return UNIIR_EUNSUPPORTED;
+    // the fp16 forward of the embedding towers: plain / causal / packed rows, or the relative bias; never dropout
+    if (drop) return UNIIR_EUNSUPPORTED;
+    if (a.rel_emb) return att_launch<attn_fwd_kernel<true, false, true>>(big, g, b, sm, st, a);
     return att_launch<attn_fwd_kernel<false, false, true>>(big, g, b, sm, st, a);
 }
 template <int NT>
@@ -797,6 +802,17 @@ extern "C" int uniir_attention_rel_fwd(const void* qkv, void* out, float* lse, c
     att_args_rel(a, rel_emb, rel_bucket, nbuckets);
     att_args_drop(a, drop_p, drop_seed);
     return launch_attn_fwd(a, batch, (hipStream_t)stream);
+}
+// ... on fp16 tensors, forward only and without dropout (the eval-mode T5 stack of CLIP_FF under fp16): attn_fwd_kernel<true, false,
+// true>.  The checks of uniir_attention_rel_fwd minus its dropout ones; like it, this tests no alignment (uniir_attn_rel_fwd_long_f16 does).
+extern "C" int uniir_attn_rel_fwd_f16(const void* qkv, void* out, float* lse, const float* rel_emb, const int32_t* rel_bucket,
+                                      int32_t nbuckets, float scale, int32_t batch, int32_t seq, int32_t heads, void* stream) {
+    if (att_null(qkv, out, lse, rel_emb, rel_bucket) || batch < 0 || heads <= 0 || nbuckets <= 0 || nbuckets > 64) return UNIIR_EINVAL;
+    if (batch == 0) return UNIIR_OK;
+    if (seq < 1 || seq > ATT_SEQ_MAX) return UNIIR_ESHAPE;
+    AttnArgs a = att_args_packed(qkv, out, lse, seq, heads, 0, scale);
+    att_args_rel(a, rel_emb, rel_bucket, nbuckets);
+    return launch_attn_fwd(a, batch, (hipStream_t)stream, true);
 }
 // The backward's tail, shared with uniir_attention_rel_bwd_long: the workgroups store their bucket sums in the stream's scratch
 // as [part][bucket][head] (nparts of them: one per item here, one per (item, key block) in the streaming form), `launch` runs the

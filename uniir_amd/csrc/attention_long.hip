@@ -4,7 +4,8 @@
 //   attn_xlong_* : the general form (Q separate from K | V, uniir_attention_fwd_long / _bwd_long) in bf16: per-item key counts
 //                  (key_len), packed query rows (q_row_off) and probability dropout (DROP).  BLIP MED cross-attention over the
 //                  577 image tokens of a 384-pixel ViT.  Every size from 1 x 1 to 1024 x 1024 runs here.
-//   attn_rlong_* : T5-style self-attention on the packed [q | k | v] buffer (uniir_attention_rel_fwd_long / _rel_bwd_long) in bf16:
+//   attn_rlong_* : T5-style self-attention on the packed [q | k | v] buffer (uniir_attention_rel_fwd_long / _rel_bwd_long) in bf16,
+//                  the forward without dropout in fp16 too (uniir_attn_rel_fwd_long_f16):
 //                  logits = scale * q.k + rel_emb[rel_bucket[key - query + seq - 1]][head] (REL), scale a run-time argument,
 //                  probability dropout, the bias gradient drel in a fixed order.  CLIP_FF at ViT-L/14@336px: 577 + 77 = 654 fused tokens.
 //
@@ -251,9 +252,9 @@ template <bool DROP, bool F16 = false>
 __global__ __launch_bounds__(AL_THREADS) void attn_xlong_fwd_kernel(AttnArgs a, int nqb) {
     al_fwd_body<F16, true, DROP>(a, nqb);
 }
-template <bool DROP>
+template <bool DROP, bool F16 = false>
 __global__ __launch_bounds__(AL_THREADS, 4) void attn_rlong_fwd_kernel(AttnArgs a, int nqb) {
-    al_fwd_body<false, false, DROP, true>(a, nqb);
+    al_fwd_body<F16, false, DROP, true>(a, nqb);
 }
 
 // the lane parts of the swizzled fragment addresses (attn_bwd_kernel): row fragments of k-step s, transposed fragments of column tile dt
@@ -623,7 +624,8 @@ static const int AL_DQ_LDS = 2 * 2 * AL_KV * 128 + 2 * AL_ROWS * 4;
 static int al_rel_tab_bytes(int seq) { return (2 * seq + 32) * 4; }
 static int al_rel_dkdv_bytes(int seq) { return 64 * 8 + (seq + 164) * 12; }
 
-// f16: AL_PLAIN (the fp16 forward of the towers) and AL_XL without dropout (uniir_attn_general_fwd_f16 / uniir_onequery_fwd_f16)
+// f16: AL_PLAIN (the fp16 forward of the towers), AL_XL without dropout (uniir_attn_general_fwd_f16 / uniir_onequery_fwd_f16) and
+// AL_REL without dropout (uniir_attn_rel_fwd_long_f16)
 static int al_launch_fwd(AlFamily fam, const AttnArgs& a, int batch, hipStream_t st, bool f16 = false) {
     const int nqb = (a.Tq + AL_ROWS - 1) / AL_ROWS;
     const long grid = (long)batch * a.H * nqb;
@@ -642,8 +644,11 @@ static int al_launch_fwd(AlFamily fam, const AttnArgs& a, int batch, hipStream_t
         if (!drop) return att_launch<attn_xlong_fwd_kernel<false>>(AL_FWD_LDS, g, b, AL_FWD_LDS, st, a, nqb);
         return att_launch<attn_xlong_fwd_kernel<true>>(AL_FWD_LDS, g, b, AL_FWD_LDS, st, a, nqb);
     }
-    if (f16) return UNIIR_EUNSUPPORTED;
     const int sm = AL_FWD_LDS + al_rel_tab_bytes(a.Tq), mx = AL_FWD_LDS + al_rel_tab_bytes(ATT_LONG_SEQ_MAX);
+    if (f16) {
+        if (drop) return UNIIR_EUNSUPPORTED;
+        return att_launch<attn_rlong_fwd_kernel<false, true>>(mx, g, b, sm, st, a, nqb);
+    }
     if (!drop) return att_launch<attn_rlong_fwd_kernel<false>>(mx, g, b, sm, st, a, nqb);
     return att_launch<attn_rlong_fwd_kernel<true>>(mx, g, b, sm, st, a, nqb);
 }
@@ -749,6 +754,18 @@ extern "C" int uniir_attention_rel_fwd_long(const void* qkv, void* out, float* l
     att_args_rel(a, rel_emb, rel_bucket, nbuckets);
     att_args_drop(a, drop_p, drop_seed);
     return al_launch_fwd(AL_REL, a, batch, (hipStream_t)stream);
+}
+// ... on fp16 tensors, forward only and without dropout: attn_rlong_fwd_kernel<false, true> at every size.  The checks of the call
+// above minus its dropout ones.  (P <= 2^8 in fp16: see attn_fwd_kernel -- the same deferred maximum on the same folded logits.)
+extern "C" int uniir_attn_rel_fwd_long_f16(const void* qkv, void* out, float* lse, const float* rel_emb, const int32_t* rel_bucket,
+                                           int32_t nbuckets, float scale, int32_t batch, int32_t seq, int32_t heads, void* stream) {
+    if (att_null(qkv, out, lse, rel_emb, rel_bucket) || batch < 0 || heads <= 0 || nbuckets <= 0 || nbuckets > 64) return UNIIR_EINVAL;
+    if (batch == 0) return UNIIR_OK;
+    if (seq < 1 || seq > ATT_LONG_SEQ_MAX) return UNIIR_ESHAPE;
+    if (att_misaligned16(qkv, out)) return UNIIR_EALIGN;
+    AttnArgs a = att_args_packed(qkv, out, lse, seq, heads, 0, scale);
+    att_args_rel(a, rel_emb, rel_bucket, nbuckets);
+    return al_launch_fwd(AL_REL, a, batch, (hipStream_t)stream, true);
 }
 static int al_launch_rel_bwd(const AttnArgs& a, int batch, hipStream_t st) { return al_launch_bwd(AL_REL, a, batch, st); }
 extern "C" int uniir_attention_rel_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,

@@ -310,21 +310,33 @@ extern "C" int uniir_layernorm_bwd_ex(const float* x, int64_t x_stride, const fl
 }
 
 // RMS norm (transformers T5LayerNorm, used by the CLIP_FF fusion stack): same kernels, rms = 1
-extern "C" int uniir_rmsnorm_fwd(const float* x, int64_t x_stride, const float* gamma, void* y_bf16, float* y_f32,
-                                 int32_t rows, int32_t width, float eps, void* stream) {
-    if (!x || !gamma || (!y_bf16 && !y_f32) || rows < 0) return UNIIR_EINVAL;
+// f16: the 16-bit output as fp16 (flags bit 1 of ln_fwd_kernel next to rms)
+static int rmsnorm_fwd_impl(const float* x, int64_t x_stride, const float* gamma, void* y_16, float* y_f32, int32_t rows,
+                            int32_t width, float eps, int f16, void* stream) {
+    if (!x || !gamma || (!y_16 && !y_f32) || rows < 0) return UNIIR_EINVAL;
     if (rows == 0) return UNIIR_OK;
     if (width % 4 || width > 64 * 4 * LN_MAXC || width <= 0 || x_stride % 4) return UNIIR_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
-    unsigned short* yb = (unsigned short*)y_bf16;
+    unsigned short* yb = (unsigned short*)y_16;
+    const int flags = f16 ? 3 : 1;
     switch (ln_nc(width)) {
-        case 2: launch_ln_fwd<2>(x, x_stride, gamma, nullptr, yb, y_f32, rows, width, eps, st, 1); break;
-        case 3: launch_ln_fwd<3>(x, x_stride, gamma, nullptr, yb, y_f32, rows, width, eps, st, 1); break;
-        case 4: launch_ln_fwd<4>(x, x_stride, gamma, nullptr, yb, y_f32, rows, width, eps, st, 1); break;
-        default: launch_ln_fwd<8>(x, x_stride, gamma, nullptr, yb, y_f32, rows, width, eps, st, 1); break;
+        case 2: launch_ln_fwd<2>(x, x_stride, gamma, nullptr, yb, y_f32, rows, width, eps, st, flags); break;
+        case 3: launch_ln_fwd<3>(x, x_stride, gamma, nullptr, yb, y_f32, rows, width, eps, st, flags); break;
+        case 4: launch_ln_fwd<4>(x, x_stride, gamma, nullptr, yb, y_f32, rows, width, eps, st, flags); break;
+        default: launch_ln_fwd<8>(x, x_stride, gamma, nullptr, yb, y_f32, rows, width, eps, st, flags); break;
     }
     HIP_LAUNCH_CHECK();
     return UNIIR_OK;
+}
+extern "C" int uniir_rmsnorm_fwd(const float* x, int64_t x_stride, const float* gamma, void* y_bf16, float* y_f32,
+                                 int32_t rows, int32_t width, float eps, void* stream) {
+    return rmsnorm_fwd_impl(x, x_stride, gamma, y_bf16, y_f32, rows, width, eps, 0, stream);
+}
+// the same with an fp16 16-bit output (the T5 stack's fp16 forward): y_f32 has the bits of uniir_rmsnorm_fwd's, y_f16 is that value
+// rounded to fp16
+extern "C" int uniir_rmsnorm_fwd_f16(const float* x, int64_t x_stride, const float* gamma, void* y_f16, float* y_f32,
+                                     int32_t rows, int32_t width, float eps, void* stream) {
+    return rmsnorm_fwd_impl(x, x_stride, gamma, y_f16, y_f32, rows, width, eps, 1, stream);
 }
 
 extern "C" int uniir_rmsnorm_bwd(const float* x, int64_t x_stride, const float* gamma, const void* dy, int32_t dy_is_f32,

@@ -290,6 +290,20 @@ def attention_fwd(qkv, batch, seq, heads, causal, *, out=None, lse=None):
     return out, lse
 
 
+def attention_fwd_causal_f16(qkv, batch, seq, heads, *, out=None, lse=None):
+    """attention_fwd with the causal mask on an fp16 qkv, seq <= 512 (uniir_attention_fwd_f16 with causal = 1, the kernel the C text
+    tower runs under fp16): the per-op fp16 text tower of CLIP_FF.  A wrapper of its own, so that attention_fwd keeps refusing what
+    no other per-op fp16 forward may ask for.  Returns fp16 out and fp32 lse."""
+    _all_fp16("attention_fwd_causal_f16", qkv, out)
+    if out is None:
+        out = torch.empty(batch * seq, heads * 64, device=qkv.device, dtype=torch.float16)
+    if lse is None:
+        lse = torch.empty(batch, heads, seq, device=qkv.device, dtype=torch.float32)
+    check(_lib.load().uniir_attention_fwd_f16(_p(qkv), _p(out), _p(lse), None, batch, seq, heads, 1, _stream()),
+          "attention_fwd_f16")
+    return out, lse
+
+
 def attention_bwd(qkv, out, dout, lse, batch, seq, heads, causal, *, dqkv=None):
     """d loss / d qkv of attention_fwd (bf16, same layout and the same limits on seq); bitwise reproducible at every length."""
     if dqkv is None:
@@ -414,6 +428,38 @@ def onequery_fwd_f16(q, q_ld, k, v, kv_ld, batch, tk, heads, *, key_len=None, kv
     check(_lib.load().uniir_onequery_fwd_f16(_p(q), q_ld, _p(k), _p(v), kv_ld, _p(out), heads * 64, _p(lse), _p(key_len),
                                              _p(kv_row_off), batch, tk, heads, _stream()), "onequery_fwd_f16")
     return out, lse
+
+
+def attention_rel_fwd_f16(qkv, rel_emb, table, batch, seq, heads, scale=1.0):
+    """T5-style self-attention on an fp16 packed qkv [batch*seq, 3*heads*64], forward only and without dropout: logits = scale * q.k
+    + rel_emb[table[key - query + seq - 1]][head] (rel_emb fp32 [buckets, heads], table int32 [2 seq - 1]).  Up to ATT_RESIDENT_MAX
+    tokens uniir_attn_rel_fwd_f16, above it uniir_attn_rel_fwd_long_f16 (up to 1024) -- the rule of the bf16 stack
+    (clipff_model._rel_entry).  Returns fp16 out [batch*seq, heads*64] and fp32 lse [batch, heads, seq]."""
+    _all_fp16("attention_rel_fwd_f16", qkv)
+    out = torch.empty(batch * seq, heads * 64, device=qkv.device, dtype=torch.float16)
+    lse = torch.empty(batch, heads, seq, device=qkv.device, dtype=torch.float32)
+    name = "uniir_attn_rel_fwd_long_f16" if seq > ATT_RESIDENT_MAX else "uniir_attn_rel_fwd_f16"
+    check(getattr(_lib.load(), name)(_p(qkv), _p(out), _p(lse), _p(rel_emb), _p(table), int(rel_emb.shape[0]), float(scale), batch, seq,
+                                     heads, _stream()), name[len("uniir_"):])
+    return out, lse
+
+
+def rmsnorm_fwd(x, gamma, eps, *, out_bf16=None, out_f32=None, rows=None, width=None, x_stride=None, dtype16=torch.bfloat16):
+    """T5's RMS norm of fp32 rows, in the style of layernorm_fwd: out_bf16 is the 16-bit output; an fp16 tensor there (or dtype16 =
+    torch.float16 when there is none: this function allocates it, or the call has the fp32 output alone) takes
+    uniir_rmsnorm_fwd_f16 -- the same fp32 result, rounded to fp16"""
+    width = width or x.shape[-1]
+    rows = rows if rows is not None else x.numel() // width
+    x_stride = x_stride or width
+    if out_bf16 is None and out_f32 is None:
+        out_bf16 = torch.empty(rows, width, device=x.device, dtype=dtype16)
+    if (out_bf16.dtype if out_bf16 is not None else dtype16) == torch.float16:
+        check(_lib.load().uniir_rmsnorm_fwd_f16(_p(x), x_stride, _p(gamma), _p(out_bf16), _p(out_f32), rows, width, eps, _stream()),
+              "rmsnorm_fwd_f16")
+        return out_bf16 if out_bf16 is not None else out_f32
+    check(_lib.load().uniir_rmsnorm_fwd(_p(x), x_stride, _p(gamma), _p(out_bf16), _p(out_f32), rows, width, eps, _stream()),
+          "rmsnorm_fwd")
+    return out_bf16 if out_bf16 is not None else out_f32
 
 
 def attention_bwd_ex(q, q_ld, k, v, kv_ld, out, dout, lse, dq, dq_ld, dk, dv, dkv_ld, batch, tq, tk, heads, *,

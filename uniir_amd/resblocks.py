@@ -61,7 +61,10 @@ def block_sublayers(b, x, bufs, g, M, T, W, heads, causal, eps, act, row_scale):
     R = M * T
     ops.layernorm_fwd(x, b.p("ln1w"), b.p("ln1b"), eps, out_bf16=h1, rows=R, width=W)
     ops.linear_fwd(h1, b.w16("wqkv"), b.p("bqkv"), out=qkv)
-    ao, lse = ops.attention_fwd(qkv, M, T, heads, causal, out=ao, lse=lse)      # (a forward-only pass passes None: fresh ones)
+    if causal and qkv.dtype == torch.float16:      # CLIP_FF's text tower under fp16: the causal fp16 forward has a wrapper of its own
+        ao, lse = ops.attention_fwd_causal_f16(qkv, M, T, heads, out=ao, lse=lse)
+    else:
+        ao, lse = ops.attention_fwd(qkv, M, T, heads, causal, out=ao, lse=lse)      # (a forward-only pass passes None: fresh ones)
     ops.linear_fwd(ao, b.w16("wo"), b.p("bo"), out=x2, epilogue=ops.EPI_RESID_F32, resid=x, row_scale=row_scale)
     ops.layernorm_fwd(x2, b.p("ln2w"), b.p("ln2b"), eps, out_bf16=h2, rows=R, width=W)
     if f is not None:

@@ -7,7 +7,13 @@ ViT-L/14@336px -> 768: 577 image tokens, 654 fused ones, the streaming relative-
 T5Config defaults d_ff 2048 / ReLU / 32 buckets), encode_text :148-156, encode_image :158-159, encode_multimodal_input
 :161-192 (the masks are accepted and unused, like there), compute_inbatch_contrastive_loss :194-265 (identical to
 CLIP_SF's, incl. the hard-negative branch), encode_mbeir_batch :272-298.  T5 dropout 0.1 is not applied.
+
+precision = "fp16": the embedding forward with fp16 activations and fp16 copies of the weights (clipff_model, dtype16 =
+torch.float16) -- the reference embedder's autocast(fp16).  Eval mode under torch.no_grad() only; the embedder switches to it for an
+extraction when embed_fp16 is set (UNIIR_CLIPFF_EMBED_FP16=1 at construction) and its config asks for use_fp16.
 """
+import os
+
 import torch
 from torch import nn
 
@@ -56,6 +62,12 @@ class CLIPFeatureFusion(nn.Module):
             self.gather_embeddings = None
             self.in_batch_neg_num = None
         del self.clip_model.text_projection      # clip_ff.py:104 (unused: the text tower is not pooled / projected)
+        # "bf16": the towers without pooling and the T5 stack in bf16, forward and backward.  "fp16": the same launch sequence on fp16
+        # activations and fp16 copies of the weights, forward only (eval mode, no_grad).  Anything else raises at the next encode call.
+        self.precision = "bf16"
+        # Whether the embedder's use_fp16 switches precision to "fp16" for an extraction (src/common/mbeir_embedder.py
+        # _tower_precision).  Off by default, so that no existing run changes: UNIIR_CLIPFF_EMBED_FP16=1 switches it on at construction.
+        self.embed_fp16 = os.environ.get("UNIIR_CLIPFF_EMBED_FP16", "0") not in ("", "0")
         self._t5 = None
         self._t5_version = -1
         if device is not None and str(device) != "cpu":
@@ -97,9 +109,26 @@ class CLIPFeatureFusion(nn.Module):
 
         return tokenizer_wrapper
 
+    def _embed_half(self):
+        """whether this encode call is the fp16 embedding forward (precision == "fp16"); what that path cannot serve raises"""
+        if self.precision not in ("bf16", "fp16"):
+            raise RuntimeError(f"unknown precision {self.precision!r}")
+        if self.precision == "bf16":
+            return False
+        if self.training:
+            raise RuntimeError("precision='fp16' is a forward-only embedding path; call model.eval() first or use precision='bf16'")
+        if torch.is_grad_enabled():
+            raise RuntimeError("precision='fp16' is the embedder's forward-only path; run it under torch.no_grad() or switch "
+                               "back to precision='bf16' for training")
+        return True
+
     def encode_multimodal_input(self, txt_tensor, img_tensor, txt_mask=None, img_mask=None):
-        self.clip_model._sync_shadow()
-        self._ensure_t5()
+        if self._embed_half():          # the fp16 copies of both stores, rebuilt when the weights moved since they were made
+            self.clip_model._sync_half_flat()
+            self._ensure_t5().half_shadow()
+        else:
+            self.clip_model._sync_shadow()
+            self._ensure_t5()
         anchor = torch.zeros(1, device=img_tensor.device, requires_grad=torch.is_grad_enabled())
         return FusionFn.apply(self, txt_tensor.to(torch.int32).contiguous(), img_tensor.contiguous(), anchor)
 

@@ -100,6 +100,7 @@ class NativeAdamW(torch.optim.Optimizer):
                 b1, b2 = group["betas"]
                 ops.call("uniir_adamw_step", st.p32[lo:hi], st.g32[lo:hi], m[lo:hi], v[lo:hi], st.w16_buf[lo:hi], hi - lo,
                          float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], self.opt_step, 1.0 / world)
+            st.mark_half_stale()               # the kernel wrote p32 and the bf16 shadow itself: an fp16 shadow of the store is behind
             if i == 0:
                 self.clip._refresh_conv()      # the padded bf16 patch-embedding weights are not part of the shadow
 
