@@ -38,7 +38,8 @@ const char* uniir_strerror(int code);
  * 5: uniir_image_*; 6: uniir_attention_fwd_long / _bwd_long; still 6, new entry points only: uniir_attention_rel_fwd_long /
  * _rel_bwd_long; uniir_attention_one_fwd / _one_bwd, and the value 2 of uniir_clip_tower.pool_last_block; uniir_layernorm_fwd_f16,
  * uniir_patchify_f16, uniir_vit_assemble_f16: no layout changes; 7: uniir_attn_rel_fwd_f16, uniir_attn_rel_fwd_long_f16 and
- * uniir_rmsnorm_fwd_f16 -- new entry points only, a caller that needs them asks for >= 7). */
+ * uniir_rmsnorm_fwd_f16 -- new entry points only, a caller that needs them asks for >= 7; still 7, a new entry point only:
+ * uniir_attn_f32_rel_fwd, which a caller finds by its symbol). */
 int uniir_abi_version(void);
 /* Reproducible reductions (round 6).  Bias, LayerNorm-weight and token-embedding gradients are sums over every row of a batch taken by
  * many workgroups; added with fp32 atomics they depend on the arrival order, and two runs of one training step differ in their last
@@ -694,6 +695,16 @@ int uniir_attn_rel_fwd_f16(const void* qkv, void* out, float* lse, const float* 
                            int32_t nbuckets, float scale, int32_t batch, int32_t seq, int32_t heads, void* stream);
 int uniir_attn_rel_fwd_long_f16(const void* qkv, void* out, float* lse, const float* rel_emb, const int32_t* rel_bucket,
                                 int32_t nbuckets, float scale, int32_t batch, int32_t seq, int32_t heads, void* stream);
+/* The fp32 forward of the stack (CLIPFeatureFusion.precision = "fp32": uniir_rmsnorm_fwd's y_f32, uniir_sgemm, uniir_bias_act_f32).
+ * uniir_attn_f32_rel_fwd: the fp32 twin of uniir_attn_rel_fwd_f16, without lse -- fp32 packed qkv [batch*seq, 3*heads*64] -> fp32 out
+ * [batch*seq, heads*64], logit(i, j) = scale * <q_i, k_j> + rel_emb[rel_bucket[j - i + seq - 1]][head], softmax over j, times V;
+ * rel_bucket has 2 seq - 1 entries in [0, nbuckets), rel_emb is [nbuckets][heads].  The kernel of uniir_attention_f32_fwd ([FP32])
+ * with the head's diagonal biases in LDS: fp32 VALU, one rounding more per logit; with an all-zero rel_emb it has the bits of
+ * uniir_attention_f32_fwd on the same buffer.  1 <= seq <= 1024 at one kernel.  UNIIR_EINVAL: a NULL operand, heads <= 0, batch < 0,
+ * nbuckets outside 1..64; UNIIR_ESHAPE: seq outside 1..1024; a refused call writes nothing; batch == 0 is UNIIR_OK.  No alignment
+ * requirement beyond that of a float. */
+int uniir_attn_f32_rel_fwd(const float* qkv, float* out, const float* rel_emb, const int32_t* rel_bucket, int32_t nbuckets,
+                           float scale, int32_t batch, int32_t seq, int32_t heads, void* stream);
 int uniir_meanpool_fwd(const float* x, float* out, int32_t n, int32_t tokens, int32_t width, void* stream);
 int uniir_meanpool_bwd(const float* dout, float* dx, int32_t n, int32_t tokens, int32_t width, void* stream);
 

@@ -169,6 +169,7 @@ SIGNATURES = {
     "uniir_rmsnorm_fwd_f16": (c_int, [P, c_i64, P, P, P, c_int, c_int, c_float, S]),
     "uniir_attn_rel_fwd_f16": (c_int, [P, P, P, P, P, c_int, c_float, c_int, c_int, c_int, S]),
     "uniir_attn_rel_fwd_long_f16": (c_int, [P, P, P, P, P, c_int, c_float, c_int, c_int, c_int, S]),
+    "uniir_attn_f32_rel_fwd": (c_int, [P, P, P, P, c_int, c_float, c_int, c_int, c_int, S]),
     "uniir_meanpool_fwd": (c_int, [P, P, c_int, c_int, c_int, S]),
     "uniir_meanpool_bwd": (c_int, [P, P, c_int, c_int, c_int, S]),
     "uniir_dropout_f32": (c_int, [P, P, P, P, c_i64, c_int, c_float, C.c_uint32, P, c_int, S]),

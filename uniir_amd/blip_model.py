@@ -8,7 +8,8 @@ All arithmetic is in libuniir_hip.so; this file is the launch sequence, the flat
 stash.  Differences from the reference, stated once:
   * bf16 MFMA GEMMs with fp32 accumulation / fp32 LayerNorm, softmax statistics, residual stream, loss (the reference
     runs fp16 autocast); no GradScaler is needed; the eval-mode embedding forward alone also runs on fp16 operands
-    (BLIPFeatureFusion.precision = "fp16", the reference embedder's autocast);
+    (BLIPFeatureFusion.precision = "fp16", the reference embedder's autocast) or in fp32 (precision = "fp32", its model.float()
+    forward: vit_forward_f32 / bert_forward_f32);
   * train mode applies the reference's dropout sites -- BERT hidden / attention-probability dropout 0.1 (med.py:84,
     175,198,212,341; online and momentum encoders alike, both are in train mode) and DropPath of ViT-large (vit.py:79-80,
     blip.py:249-254) -- with counter-based masks regenerated in backward (ops.DropSeeds); the masks are a different random
@@ -26,6 +27,7 @@ import torch
 from torch import nn
 
 from . import _lib, comm, ops
+from .clip_model import _linear_f32
 from .flat_store import FlatStore
 from .resblocks import tower_bwd, tower_fwd
 
@@ -581,6 +583,90 @@ def _pooler_backward(cx, dpooled, stash):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# fp32 forward (precision = "fp32"): the reference's model.float() embedding forward, the launch sequence of
+# clip_model._encode_fp32 for BLIP's two encoders -- every GEMM the exact-fp32 MFMA uniir_sgemm on the fp32 masters of the
+# store (no shadow is read or built), uniir_bias_act_f32 for bias / erf-GELU / residual, the fp32 LayerNorm output,
+# uniir_attention_f32_fwd for the ViT, BERT's self-attention (key_len) and its cross-attention (tq != tk).  It shares
+# nothing with the dtype16 plumbing above.  Forward only; every row dense and every layer full.
+# ------------------------------------------------------------------------------------------------------------
+def _ln_f32(x, w, b, eps):
+    y = torch.empty_like(x)
+    ops.layernorm_fwd(x, w, b, eps, out_f32=y, rows=x.shape[0], width=x.shape[1])
+    return y
+
+
+def _attention_f32(q, q_ld, k, v, kv_ld, key_len, M, tq, tk, heads):
+    out = torch.empty(M * tq, heads * 64, device=q.device, dtype=torch.float32)
+    ops.call("uniir_attention_f32_fwd", q, q_ld, k, v, kv_ld, out, heads * 64, key_len, M, tq, tk, heads, 0, 0.125)
+    return out
+
+
+def vit_forward_f32(st, prefix, cfg, img_size, images):
+    """vit_forward in fp32 -> fp32 tokens [M*T, D] after the final norm, and T"""
+    D, P, depth, heads = cfg["embed_dim"], cfg["patch_size"], cfg["depth"], cfg["num_heads"]
+    M, g = images.shape[0], img_size // P
+    T = g * g + 1
+    p = lambda name: st.p(prefix + name)          # noqa: E731
+    # im2col is a pure permutation (no arithmetic): [M,3,g,P,g,P] -> [M*g*g, 3*P*P], the order proj.weight.view(D,-1) has
+    patches = images.float().contiguous().view(M, 3, g, P, g, P).permute(0, 2, 4, 1, 3, 5).reshape(M * g * g, 3 * P * P).contiguous()
+    po = _linear_f32(patches, p("patch_embed.proj.weight").view(D, 3 * P * P), p("patch_embed.proj.bias"))
+    x = torch.empty(M * T, D, device=images.device, dtype=torch.float32)
+    ops.call("uniir_vit_assemble_f32", po, p("cls_token"), p("pos_embed"), x, M, T, D)
+    for i in range(depth):
+        n = _vit_blk_names(prefix, i)
+        h = _ln_f32(x, st.p(n["ln1w"]), st.p(n["ln1b"]), VIT_EPS)
+        qkv = _linear_f32(h, st.p(n["wqkv"]), st.p(n["bqkv"]))
+        ao = _attention_f32(qkv, 3 * D, qkv[:, D:], qkv[:, 2 * D:], 3 * D, None, M, T, T, heads)
+        x = _linear_f32(ao, st.p(n["wo"]), st.p(n["bo"]), resid=x)
+        h = _ln_f32(x, st.p(n["ln2w"]), st.p(n["ln2b"]), VIT_EPS)
+        f = _linear_f32(h, st.p(n["wfc"]), st.p(n["bfc"]), act=ops.ACT_GELU_ERF)
+        x = _linear_f32(f, st.p(n["wproj"]), st.p(n["bproj"]), resid=x)
+    return _ln_f32(x, p("norm.weight"), p("norm.bias"), VIT_EPS), T
+
+
+def bert_forward_f32(st, prefix, cfg, ids, key_len, img, Ti, cross=True, pool=True):
+    """bert_forward in fp32 on the dense [M, L] rows -> fp32 [M, W]: the tanh pooler's output, or (pool=False) the class rows.
+    img fp32 [M*Ti, enc_width] (None with cross=False, mode "text").  The padding mask is key_len: a padded key is skipped, which
+    is the fp32 softmax the reference gets by adding -10000 to its logit (exp underflows to an exact 0)."""
+    M, L = ids.shape
+    W, eps, heads = cfg["hidden_size"], cfg["layer_norm_eps"], cfg["num_attention_heads"]
+    dev = ids.device
+    p = lambda name, shape=None: st.p(prefix + name, shape)          # noqa: E731
+
+    def sublayer(x, name, resid):
+        """dense + residual -> LayerNorm (BertSelfOutput / BertOutput)"""
+        return _ln_f32(_linear_f32(x, p(name + "dense.weight"), p(name + "dense.bias"), resid=resid), p(name + "LayerNorm.weight"),
+                       p(name + "LayerNorm.bias"), eps)
+
+    e = torch.empty(M * L, W, device=dev, dtype=torch.float32)
+    scratch = torch.empty(M, device=dev, dtype=torch.int32)
+    ops.call("uniir_text_embed", ids, p("embeddings.word_embeddings.weight"), p("embeddings.position_embeddings.weight"), e, scratch,
+             M, L, W, cfg["vocab_size"])
+    h = _ln_f32(e, p("embeddings.LayerNorm.weight"), p("embeddings.LayerNorm.bias"), eps)
+    for i in range(cfg["num_hidden_layers"]):
+        b = f"encoder.layer.{i}."
+        s, c = b + "attention.self.", b + "crossattention.self."
+        qkv = _linear_f32(h, p(s + "query.weight", (3 * W, W)), p(s + "query.bias", (3 * W,)))
+        ao = _attention_f32(qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, key_len, M, L, L, heads)
+        h = sublayer(ao, b + "attention.output.", h)
+        if cross:
+            cq = _linear_f32(h, p(c + "query.weight"), p(c + "query.bias"))
+            ckv = _linear_f32(img, p(c + "key.weight", (2 * W, img.shape[1])), p(c + "key.bias", (2 * W,)))
+            co = _attention_f32(cq, W, ckv, ckv[:, W:], 2 * W, None, M, L, Ti, heads)
+            h = sublayer(co, b + "crossattention.output.", h)
+        f = _linear_f32(h, p(b + "intermediate.dense.weight"), p(b + "intermediate.dense.bias"), act=ops.ACT_GELU_ERF)
+        h = sublayer(f, b + "output.", h)
+    rows = torch.empty(M, W, device=dev, dtype=torch.float32)
+    ops.call("uniir_gather_rows", h, None, rows, M, L, W)          # the class token = row 0 of every item
+    if not pool:
+        return rows
+    pre = _linear_f32(rows, p("pooler.dense.weight"), p("pooler.dense.bias"))
+    pooled = torch.empty_like(pre)
+    ops.call("uniir_tanh_fwd", pre, pooled, pre.numel())
+    return pooled
+
+
+# ------------------------------------------------------------------------------------------------------------
 # module
 # ------------------------------------------------------------------------------------------------------------
 class _EncodeFn(torch.autograd.Function):
@@ -783,10 +869,20 @@ class BLIPFeatureFusion(nn.Module):
         # encode_mbeir_batch and forward(encode_mbeir_batch=True) -- runs ViT and BERT (and BLIP_SF's projections) on fp16 activations
         # from the online store's fp16 shadow, under no_grad, and returns fp32 embeddings as always: the reference embedder's
         # autocast(fp16), 1e-3 from the fp32 oracle instead of bf16's 6e-3.  Eval mode and the online encoder only.  A plain attribute.
+        # "fp32": the same calls run the reference's model.float() forward -- what an embed YAML with use_fp16: False means -- in exact-fp32
+        # MFMA GEMMs, fp32 attention and LayerNorm on the fp32 masters of the online store (vit_forward_f32 / bert_forward_f32: a launch
+        # sequence of its own, no shadow is read or built).  Eval mode, torch.no_grad() and the online encoder only.  pack_text,
+        # pool_last_layer and vit_grad_ckpt change nothing on it: every row is dense and every layer full (skipping padded keys and adding
+        # -10000 to their logits are the same fp32 softmax).  Reference precision, not throughput (profiles/embed_fp32.txt).
         self.precision = "bf16"
         # Whether the embedder's use_fp16 switches precision to "fp16" for an extraction (src/common/mbeir_embedder.py
         # _tower_precision).  Off by default, so that no existing run changes: UNIIR_BLIP_EMBED_FP16=1 switches it on at construction.
         self.embed_fp16 = os.environ.get("UNIIR_BLIP_EMBED_FP16", "0") not in ("", "0")
+        # Whether the embedder's use_fp16: False switches precision to "fp32" for an extraction (the reference's autocast(enabled=False)
+        # on a model.float() model).  Off by default, so that no existing run changes: UNIIR_EMBED_FP32=1 switches it on at construction.
+        # It is also what makes "fp32" a precision this module knows: without it precision = "fp32" raises `unknown precision`, as it
+        # did before the fp32 forward existed, so a model that has not opted in behaves in every respect as it always did.
+        self.embed_fp32 = os.environ.get("UNIIR_EMBED_FP32", "0") not in ("", "0")
         self.path_log = []                # one line per BERT pass whose last layer ran on the class rows (the newest 64)
 
     def _path_log(self):
@@ -978,36 +1074,49 @@ class BLIPFeatureFusion(nn.Module):
                                 dtype16=dt)
         return tok.view(image_batched.shape[0], T, -1)
 
-    def _embed_half(self, use_momentum):
-        """whether this encode call is the fp16 embedding forward (precision == "fp16"); what that path cannot serve raises"""
-        if self.precision not in ("bf16", "fp16"):
-            raise RuntimeError(f"unknown precision {self.precision!r}")
-        if self.precision == "bf16":
-            return False
+    def _embed_mode(self, use_momentum):
+        """the precision of this encode call: "bf16", or the forward-only embedding path "fp16" / "fp32"; what that path cannot serve
+        raises"""
+        mode = self.precision
+        if mode not in ("bf16", "fp16", "fp32"):
+            raise RuntimeError(f"unknown precision {mode!r}")
+        if mode == "fp32" and not self.embed_fp32:          # the fp32 forward exists for a module that opted in, and only for it
+            raise RuntimeError("unknown precision 'fp32' for a model that has not opted in to the fp32 embedding forward: set "
+                               "embed_fp32 = True (UNIIR_EMBED_FP32=1 at construction) first")
+        if mode == "bf16":
+            return mode
         if self.training:
-            raise RuntimeError("precision='fp16' is a forward-only embedding path; call model.eval() first or use precision='bf16'")
+            raise RuntimeError(f"precision='{mode}' is a forward-only embedding path; call model.eval() first or use precision='bf16'")
         if use_momentum:
-            raise RuntimeError("precision='fp16' is the online encoder's embedding path: the fp16 shadow exists for the online store "
-                               "only (use_momentum=True needs precision='bf16')")
-        return True
+            raise RuntimeError(f"precision='{mode}' is the online encoder's embedding path" + (": the fp16 shadow exists for the online "
+                               "store only" if mode == "fp16" else "") + " (use_momentum=True needs precision='bf16')")
+        if mode == "fp32" and torch.is_grad_enabled():
+            raise RuntimeError("precision='fp32' is a forward-only path (embedding extraction / parity); run it under torch.no_grad() or "
+                               "switch back to precision='bf16' for training")
+        return mode
 
     def _encode_inputs(self, txt_dict_batched, use_momentum):
         """what every encode call starts with: the stores brought up to date, the token ids and key lengths, the TextPack
-        -> half (_embed_half), ids, key_len, pack; last_text_rows = (BERT rows run, rows of the padded batch)"""
-        half = self._embed_half(use_momentum)
-        if half:
+        -> mode (_embed_mode), ids, key_len, pack; last_text_rows = (BERT rows run, rows of the padded batch).  "fp32" runs the dense
+        rows: no pack"""
+        mode = self._embed_mode(use_momentum)
+        if mode == "fp16":
             self._sync_half()          # _sync() plus the fp16 copies
         else:
             self._sync()
         ids, key_len = self._text_inputs(txt_dict_batched)
-        pack = self._text_pack(txt_dict_batched, key_len, ids.shape[1])
+        pack = self._text_pack(txt_dict_batched, key_len, ids.shape[1]) if mode != "fp32" else None
         self.last_text_rows = (pack.R if pack is not None else ids.numel(), ids.numel())
-        return half, ids, key_len, pack
+        return mode, ids, key_len, pack
 
     def encode_multimodal_input(self, txt_dict_batched, image_batched, txt_mask=None, img_mask=None, use_momentum=False):
         """blip_ff.py:82-116: BERT(text) cross-attending to ViT(image) tokens -> pooler_output [n, embed_dim]"""
-        half, ids, key_len, pack = self._encode_inputs(txt_dict_batched, use_momentum)
-        if half:
+        mode, ids, key_len, pack = self._encode_inputs(txt_dict_batched, use_momentum)
+        if mode == "fp32":
+            st = self._online
+            tok, Ti = vit_forward_f32(st, "visual_encoder.", self.vit_cfg, self.image_size, image_batched)
+            return bert_forward_f32(st, "text_encoder.", self.med_cfg, ids, key_len, tok, Ti)
+        if mode == "fp16":
             with torch.no_grad():
                 st = self._online
                 tok, Ti, _ = vit_forward(st, self._conv16h, "visual_encoder.", self.vit_cfg, self.image_size, image_batched, False,
@@ -1162,14 +1271,29 @@ class BLIPScoreFusion(BLIPFeatureFusion):
         stash = dict(vst=vst, bst=bst, T=T, tfeat16=tfeat16, ifeat16=ifeat16, tmask=tmask, imask=imask) if save else None
         return emb, stash
 
+    def _encode_sf_f32(self, st, ids, key_len, images, tmask, imask):
+        """_encode_sf in fp32 (precision = "fp32"): vit_forward_f32 / bert_forward_f32 in mode "text", the two projections by
+        uniir_sgemm, the mask fusion as the bf16 path does it"""
+        M, E = ids.shape[0], self.embed_dim
+        tok, T = vit_forward_f32(st, "visual_encoder.", self.vit_cfg, self.image_size, images)
+        ifeat = tok.view(M, T, -1)[:, 0].contiguous()                     # class-token rows (a copy)
+        tfeat = bert_forward_f32(st, "text_encoder.", self.med_cfg, ids, key_len, None, 0, cross=False, pool=False)
+        temb = _linear_f32(tfeat, st.p("text_proj.weight"), st.p("text_proj.bias"))
+        iemb = _linear_f32(ifeat, st.p("vision_proj.weight"), st.p("vision_proj.bias"))
+        emb = torch.empty(M, E, device=ids.device, dtype=torch.float32)
+        ops.call("uniir_fuse_embeddings", temb, iemb, tmask, imask, emb, M, E)
+        return emb
+
     def encode_multimodal_input(self, txt_dict_batched, image_batched, txt_mask=None, img_mask=None, use_momentum=False):
-        half, ids, key_len, pack = self._encode_inputs(txt_dict_batched, use_momentum)
+        mode, ids, key_len, pack = self._encode_inputs(txt_dict_batched, use_momentum)
         M = ids.shape[0]
         dev = ids.device
         ones = torch.ones(M, dtype=torch.int64, device=dev)
         tmask = ones if txt_mask is None else txt_mask.to(dev).to(torch.int64).contiguous()
         imask = ones if img_mask is None else img_mask.to(dev).to(torch.int64).contiguous()
-        if half:
+        if mode == "fp32":
+            return self._encode_sf_f32(self._online, ids, key_len, image_batched, tmask, imask)
+        if mode == "fp16":
             with torch.no_grad():
                 return self._encode_sf(self._online, self._conv16h, ids, key_len, image_batched, tmask, imask, False, pack, torch.float16)[0]
         if use_momentum:

@@ -151,6 +151,10 @@ class CLIP(nn.Module):
         # fp32 path; weights are read from an fp16 shadow that is refreshed with the bf16 one.  "fp32": the reference's model.float()
         # forward in exact-fp32 MFMA GEMMs + fp32 attention (csrc/fp32_path.hip): reference-precision embeddings, no backward
         self.precision = "bf16"
+        # Whether the embedder's use_fp16: False switches precision to "fp32" for an extraction (src/common/mbeir_embedder.py
+        # _tower_precision: the reference's autocast(enabled=False) on a model.float() model).  Off by default, so that no existing run
+        # changes: UNIIR_EMBED_FP32=1 switches it on at construction.
+        self.embed_fp32 = os.environ.get("UNIIR_EMBED_FP32", "0") not in ("", "0")
         # exact text-row packing (csrc/tower.hip *_packed): the text tower runs on the tokens up to each caption's EOT only.  Rows
         # behind the EOT never reach the pooled feature under the causal mask (clip_sf.py:43-44), so results are those of the dense
         # tower (embeddings and activation gradients bitwise, weight gradients up to the order of fp32 additions).
@@ -523,33 +527,49 @@ def _tower_fwd_f32(model, prefix, layers, x, M, T, W, heads, causal, p32):
     return x
 
 
+def _image_blocks_f32(model, image, p32):
+    """the vision tower up to its last residual block, every token: image [M,3,res,res] -> x fp32 [M*T, W], T"""
+    cfg = model.cfg
+    dev, M = image.device, image.shape[0]
+    W, P, L = cfg["vision_width"], cfg["vision_patch_size"], cfg["vision_layers"]
+    res = cfg["image_resolution"]
+    g = res // P
+    T = g * g + 1
+    # im2col is a pure permutation (no arithmetic): [M,3,g,P,g,P] -> [M*g*g, 3*P*P], the order conv1.weight.view(W,-1) has
+    patches = image.float().view(M, 3, g, P, g, P).permute(0, 2, 4, 1, 3, 5).reshape(M * g * g, 3 * P * P).contiguous()
+    po = _linear_f32(patches, p32("visual.conv1.weight").view(W, 3 * P * P))
+    x0 = torch.empty(M * T, W, device=dev, dtype=torch.float32)
+    ops.call("uniir_vit_assemble_f32", po, p32("visual.class_embedding"), p32("visual.positional_embedding"), x0, M, T, W)
+    x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
+    ops.layernorm_fwd(x0, p32("visual.ln_pre.weight"), p32("visual.ln_pre.bias"), out_f32=x, rows=M * T, width=W)
+    return _tower_fwd_f32(model, "visual.transformer", L, x, M, T, W, W // 64, False, p32), T
+
+
+def _text_blocks_f32(model, text, p32):
+    """the text tower up to its last residual block, every token: text int32 [M,ctx] -> x fp32 [M*T, W], the EOT positions, T"""
+    cfg = model.cfg
+    dev, M = text.device, text.shape[0]
+    W, L, T = cfg["transformer_width"], cfg["transformer_layers"], cfg["context_length"]
+    x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
+    eot = torch.empty(M, device=dev, dtype=torch.int32)
+    ops.call("uniir_text_embed", text, p32("token_embedding.weight"), p32("positional_embedding"), x, eot, M, T, W,
+             cfg["vocab_size"])
+    return _tower_fwd_f32(model, "transformer", L, x, M, T, W, cfg["transformer_heads"], True, p32), eot, T
+
+
 def _encode_fp32(model, which, inp, p32):
     cfg = model.cfg
     dev = inp.device
     E, M = cfg["embed_dim"], inp.shape[0]
     if which == "image":
-        W, P, L = cfg["vision_width"], cfg["vision_patch_size"], cfg["vision_layers"]
-        res = cfg["image_resolution"]
-        g = res // P
-        T = g * g + 1
-        # im2col is a pure permutation (no arithmetic): [M,3,g,P,g,P] -> [M*g*g, 3*P*P], the order conv1.weight.view(W,-1) has
-        patches = inp.float().view(M, 3, g, P, g, P).permute(0, 2, 4, 1, 3, 5).reshape(M * g * g, 3 * P * P).contiguous()
-        po = _linear_f32(patches, p32("visual.conv1.weight").view(W, 3 * P * P))
-        x0 = torch.empty(M * T, W, device=dev, dtype=torch.float32)
-        ops.call("uniir_vit_assemble_f32", po, p32("visual.class_embedding"), p32("visual.positional_embedding"), x0, M, T, W)
-        x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
-        ops.layernorm_fwd(x0, p32("visual.ln_pre.weight"), p32("visual.ln_pre.bias"), out_f32=x, rows=M * T, width=W)
-        x = _tower_fwd_f32(model, "visual.transformer", L, x, M, T, W, W // 64, False, p32)
+        W = cfg["vision_width"]
+        x, T = _image_blocks_f32(model, inp, p32)
         rows = torch.empty(M, W, device=dev, dtype=torch.float32)
         ops.call("uniir_gather_rows", x, None, rows, M, T, W)
         lnw, lnb, proj = "visual.ln_post.weight", "visual.ln_post.bias", "visual.proj"
     else:
-        W, L, T = cfg["transformer_width"], cfg["transformer_layers"], cfg["context_length"]
-        x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
-        eot = torch.empty(M, device=dev, dtype=torch.int32)
-        ops.call("uniir_text_embed", inp, p32("token_embedding.weight"), p32("positional_embedding"), x, eot, M, T, W,
-                 cfg["vocab_size"])
-        x = _tower_fwd_f32(model, "transformer", L, x, M, T, W, cfg["transformer_heads"], True, p32)
+        W = cfg["transformer_width"]
+        x, eot, T = _text_blocks_f32(model, inp, p32)
         rows = torch.empty(M, W, device=dev, dtype=torch.float32)
         ops.call("uniir_gather_rows", x, eot, rows, M, T, W)
         lnw, lnb, proj = "ln_final.weight", "ln_final.bias", "text_projection"

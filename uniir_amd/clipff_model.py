@@ -11,12 +11,16 @@ with counter-based masks regenerated in backward (ops.DropSeeds); the CLIP tower
 dtype16 = torch.float16 (t5_forward, vision_tokens_fwd, text_tokens_fwd): the eval-mode embedding forward with fp16 16-bit
 activations and weights from the stores' fp16 shadows (FlatStore.w16h) -- the same launch sequence, the fp16 twins of the entry
 points (uniir_rmsnorm_fwd_f16, uniir_attn_rel_fwd_f16 / _long_f16, UNIIR_DT_F16 GEMMs); the residual stream, the norm statistics,
-visual.proj's output, the final norm, the mean pool and the embedding stay fp32.  Forward only: no stash, no dropout."""
+visual.proj's output, the final norm, the mean pool and the embedding stay fp32.  Forward only: no stash, no dropout.
+
+fusion_forward_f32 (CLIPFeatureFusion.precision = "fp32"): the eval-mode embedding forward in fp32 on the fp32 masters of both stores,
+a launch sequence of its own (uniir_sgemm, uniir_attn_f32_rel_fwd); it does not go through the dtype16 argument."""
 import math
 
 import torch
 
 from . import ops
+from .clip_model import _image_blocks_f32, _linear_f32, _text_blocks_f32
 from .resblocks import block_set_bytes, clip_block_names, tower_bwd, tower_fwd
 
 T5_EPS = 1e-6
@@ -319,6 +323,69 @@ def text_tokens_bwd(model, dtok, stash):
              G("positional_embedding"), M, T, W, cfg["vocab_size"])
 
 
+# ------------------------------------------------------------------------------------------------------------
+# fp32 forward (CLIPFeatureFusion.precision = "fp32"): the reference's model.float() embedding forward.  The towers without pooling
+# are clip_model's fp32 blocks (_image_blocks_f32 / _text_blocks_f32, the stems and blocks of clip_model._encode_fp32) followed by
+# ln_post + visual.proj / ln_final on every token; the T5 stack is uniir_rmsnorm_fwd's fp32 output, uniir_sgemm, the fp32
+# relative-bias attention uniir_attn_f32_rel_fwd (csrc/fp32_path.hip) and ReLU through uniir_bias_act_f32.  Both stores' fp32 masters
+# are read directly.  Forward only, eval mode: no stash, no dropout.
+# ------------------------------------------------------------------------------------------------------------
+def t5_forward_f32(st, prefix, x, M, T, heads, layers):
+    """x fp32 [M*T, D] (the concatenated tokens) -> pooled fp32 [M, D]: t5_forward's eval-mode sequence in fp32"""
+    R, D = x.shape
+    inner = heads * 64
+    dev = x.device
+    table = _table(T, dev)
+    rel = st.p(prefix + "block.0.layer.0.SelfAttention.relative_attention_bias.weight")
+
+    def rms(x, name):
+        y = torch.empty(R, D, device=dev, dtype=torch.float32)
+        ops.call("uniir_rmsnorm_fwd", x, D, st.p(name), None, y, R, D, T5_EPS)
+        return y
+
+    for i in range(layers):
+        a, f = f"{prefix}block.{i}.layer.0.", f"{prefix}block.{i}.layer.1."
+        qkv = _linear_f32(rms(x, a + "layer_norm.weight"), st.p(a + "SelfAttention.q.weight", (3 * inner, D)))
+        ao = torch.empty(R, inner, device=dev, dtype=torch.float32)
+        ops.call("uniir_attn_f32_rel_fwd", qkv, ao, rel, table, T5_BUCKETS, 1.0, M, T, heads)
+        x = _linear_f32(ao, st.p(a + "SelfAttention.o.weight"), resid=x)
+        g = _linear_f32(rms(x, f + "layer_norm.weight"), st.p(f + "DenseReluDense.wi.weight"), act=ops.ACT_RELU)
+        x = _linear_f32(g, st.p(f + "DenseReluDense.wo.weight"), resid=x)
+    pooled = torch.empty(M, D, device=dev, dtype=torch.float32)
+    ops.call("uniir_meanpool_fwd", rms(x, prefix + "final_layer_norm.weight"), pooled, M, T, D)
+    return pooled
+
+
+def vision_tokens_f32(model, image):
+    """vision_tokens_fwd in fp32 -> fp32 [M*T, E] = ln_post(all tokens) @ proj, and T"""
+    cfg, p32 = model.cfg, model._flat.p
+    W, E = cfg["vision_width"], cfg["embed_dim"]
+    x, T = _image_blocks_f32(model, image, p32)
+    ln = torch.empty_like(x)
+    ops.layernorm_fwd(x, p32("visual.ln_post.weight"), p32("visual.ln_post.bias"), out_f32=ln, rows=x.shape[0], width=W)
+    tok = torch.empty(x.shape[0], E, device=x.device, dtype=torch.float32)
+    ops.call("uniir_sgemm", ln, W, 1, p32("visual.proj"), E, 1, tok, E, x.shape[0], E, W, 1.0)      # ln @ proj, proj [W, E]
+    return tok, T
+
+
+def text_tokens_f32(model, text):
+    """text_tokens_fwd in fp32 -> fp32 [M*77, W] = ln_final(all tokens), and the context length"""
+    cfg, p32 = model.cfg, model._flat.p
+    x, _, T = _text_blocks_f32(model, text, p32)
+    tok = torch.empty_like(x)
+    ops.layernorm_fwd(x, p32("ln_final.weight"), p32("ln_final.bias"), out_f32=tok, rows=x.shape[0], width=cfg["transformer_width"])
+    return tok, T
+
+
+def fusion_forward_f32(owner, text, image):
+    """FusionFn.forward in fp32 (no autograd node: the caller has refused grad mode)"""
+    ttok, Tt = text_tokens_f32(owner.clip_model, text)
+    itok, Ti = vision_tokens_f32(owner.clip_model, image)
+    M, D = text.shape[0], ttok.shape[1]
+    x = torch.cat([ttok.view(M, Tt, D), itok.view(M, Ti, D)], dim=1).view(M * (Tt + Ti), D)     # a copy, no arithmetic
+    return t5_forward_f32(owner._t5, "", x, M, Tt + Ti, owner.t5_heads, owner.t5_layers_n)
+
+
 class FusionFn(torch.autograd.Function):
     """(clip module, T5 store, text int32 [M,77], image [M,3,H,W]) -> fused embedding fp32 [M, D]"""
 
@@ -326,7 +393,7 @@ class FusionFn(torch.autograd.Function):
     def forward(ctx, owner, text, image, anchor):
         save = bool(ctx.needs_input_grad[3])
         clip, st = owner.clip_model, owner._t5
-        # the owner's precision (CLIPFeatureFusion._embed_half() has refused what fp16 cannot serve): "fp16" = the embedding forward
+        # the owner's precision (CLIPFeatureFusion._embed_mode() has refused what fp16 cannot serve): "fp16" = the embedding forward
         dt = torch.float16 if owner.precision == "fp16" else torch.bfloat16
         ttok, Tt, tst = text_tokens_fwd(clip, text, save, dtype16=dt)
         itok, Ti, ist = vision_tokens_fwd(clip, image, save, dtype16=dt)

@@ -68,21 +68,33 @@ extern "C" int uniir_vit_assemble_f32(const float* patch_out, const float* class
 
 // fp32 attention, head_dim 64: one workgroup per (item, head), one thread per query row (256 rows per pass), keys and
 // values streamed through LDS 32 rows at a time, online softmax (running max / sum / output in registers), all fp32 VALU.
+// REL (uniir_attn_f32_rel_fwd, the T5 stack of CLIP_FF): the workgroup first writes its head's Tq + Tk - 1 diagonal biases
+// rel_emb[rel_bucket[d]][h] into LDS (at most 2047 floats beside the 16 KB of K / V tiles; the first barrier of the key loop
+// publishes them) and each thread adds bias[key - query + Tq - 1] to its logit after the dot product: one more rounding, nothing
+// else moves.  Consecutive lanes are consecutive queries, so they read consecutive (descending) addresses: no bank conflicts.
+// Without REL the body is the kernel uniir_attention_f32_fwd always had, instruction for instruction.
 #define A32_KB 32
+#define A32_REL_MAX 1024          // queries = keys of the REL form: 2 * 1024 - 1 biases
+template <bool REL>
 __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restrict__ q, long q_ld,
                                                             const float* __restrict__ k, const float* __restrict__ v,
                                                             long kv_ld, float* __restrict__ out, long out_ld,
                                                             const int* __restrict__ klen, int Tq, int Tk, int H, int causal,
-                                                            float scale) {
+                                                            float scale, const float* __restrict__ rel_emb,
+                                                            const int* __restrict__ rel_bucket) {
     __shared__ float ks[A32_KB][64];
     __shared__ float vs[A32_KB][64];
+    __shared__ float bias[REL ? 2 * A32_REL_MAX : 1];
     const int m = blockIdx.x / H, h = blockIdx.x % H, tid = threadIdx.x;
     const int kvalid = klen ? min(Tk, klen[m]) : Tk;
     const float* kbase = k + (long)m * Tk * kv_ld + h * 64;
     const float* vbase = v + (long)m * Tk * kv_ld + h * 64;
+    if (REL)
+        for (int d = tid; d < Tq + Tk - 1; d += 256) bias[d] = rel_emb[rel_bucket[d] * H + h];
     for (int q0 = 0; q0 < Tq; q0 += 256) {
         const int qi = q0 + tid;
         const bool live = qi < Tq;
+        const int boff = live ? Tq - 1 - qi : 0;          // bias[key + boff]; a lane without a query stays inside the table
         float qr[64], acc[64];
 #pragma unroll
         for (int d = 0; d < 64; ++d) {
@@ -105,6 +117,7 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
                 float s = 0.f;
 #pragma unroll
                 for (int d = 0; d < 64; ++d) s = fmaf(qr[d], ks[r][d], s);
+                if (REL) s += bias[k0 + r + boff];
                 const float mn = fmaxf(mx, s);
                 const float alpha = expf(mx - mn), p = expf(s - mn);      // exp(-inf) = 0 on the first key
                 l = l * alpha + p;
@@ -128,8 +141,23 @@ extern "C" int uniir_attention_f32_fwd(const float* q, int64_t q_ld, const float
     if (!q || !k || !v || !out || batch < 0 || heads <= 0 || tq < 1 || tk < 1) return UNIIR_EINVAL;
     if (batch == 0) return UNIIR_OK;
     if (causal && tq != tk) return UNIIR_ESHAPE;
-    hipLaunchKernelGGL(attention_f32_kernel, dim3(batch * heads), dim3(256), 0, (hipStream_t)stream, q, (long)q_ld, k, v,
-                       (long)kv_ld, out, (long)out_ld, key_len, tq, tk, heads, causal, scale);
+    hipLaunchKernelGGL(attention_f32_kernel<false>, dim3(batch * heads), dim3(256), 0, (hipStream_t)stream, q, (long)q_ld, k, v,
+                       (long)kv_ld, out, (long)out_ld, key_len, tq, tk, heads, causal, scale, (const float*)nullptr,
+                       (const int*)nullptr);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+// T5-style self-attention of the fp32 CLIP_FF forward on a packed qkv [batch*seq, 3*heads*64]:
+// logit(i, j) = scale * <q_i, k_j> + rel_emb[rel_bucket[j - i + seq - 1]][head] -- the fp32 twin of uniir_attn_rel_fwd_f16, no lse
+extern "C" int uniir_attn_f32_rel_fwd(const float* qkv, float* out, const float* rel_emb, const int32_t* rel_bucket,
+                                      int32_t nbuckets, float scale, int32_t batch, int32_t seq, int32_t heads, void* stream) {
+    if (!qkv || !out || !rel_emb || !rel_bucket || batch < 0 || heads <= 0 || nbuckets <= 0 || nbuckets > 64) return UNIIR_EINVAL;
+    if (batch == 0) return UNIIR_OK;
+    if (seq < 1 || seq > A32_REL_MAX) return UNIIR_ESHAPE;
+    const long W = (long)heads * 64;
+    hipLaunchKernelGGL(attention_f32_kernel<true>, dim3(batch * heads), dim3(256), 0, (hipStream_t)stream, qkv, 3 * W, qkv + W,
+                       qkv + 2 * W, 3 * W, out, W, (const int*)nullptr, seq, seq, heads, 0, scale, rel_emb, rel_bucket);
     HIP_LAUNCH_CHECK();
     return UNIIR_OK;
 }

@@ -60,7 +60,10 @@ def _tower_precision(model, use_fp16):
     # model does the same when it opted in (BLIPFeatureFusion.embed_fp16, UNIIR_BLIP_EMBED_FP16=1); without that its extraction stays
     # in bf16 whatever use_fp16 says, as it always was.  CLIP_FF is the BLIP case: its encode path follows the precision of the
     # CLIPFeatureFusion module itself, which is switched only when the module opted in (embed_fp16, UNIIR_CLIPFF_EMBED_FP16=1); the
-    # precision of its inner CLIP module is switched as for CLIP_SF and read by nothing on that path
+    # precision of its inner CLIP module is switched as for CLIP_SF and read by nothing on that path.
+    # use_fp16: False is autocast(enabled=False) on the reference's model.float() model, an fp32 forward: a module that opted in
+    # (embed_fp32, UNIIR_EMBED_FP32=1 at construction; each of the CLIP module, the BLIP module and the CLIP_FF module carries its own)
+    # takes its precision = "fp32" for the extraction, in the same way; without that the extraction stays in bf16, as it always was
     clip = _clip_towers(model)
     blip = _blip_module(model) if clip is None else _clipff_module(model)
     restore = restore_blip = None
@@ -68,6 +71,10 @@ def _tower_precision(model, use_fp16):
         restore, clip.precision = clip.precision, "fp16"
     if blip is not None and use_fp16 and blip.embed_fp16 and blip.precision == "bf16":
         restore_blip, blip.precision = blip.precision, "fp16"
+    if clip is not None and not use_fp16 and getattr(clip, "embed_fp32", False) and clip.precision == "bf16":
+        restore, clip.precision = clip.precision, "fp32"
+    if blip is not None and not use_fp16 and getattr(blip, "embed_fp32", False) and blip.precision == "bf16":
+        restore_blip, blip.precision = blip.precision, "fp32"
     try:
         yield
     finally:

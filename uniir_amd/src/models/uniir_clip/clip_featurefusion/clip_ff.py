@@ -11,6 +11,11 @@ CLIP_SF's, incl. the hard-negative branch), encode_mbeir_batch :272-298.  T5 dro
 precision = "fp16": the embedding forward with fp16 activations and fp16 copies of the weights (clipff_model, dtype16 =
 torch.float16) -- the reference embedder's autocast(fp16).  Eval mode under torch.no_grad() only; the embedder switches to it for an
 extraction when embed_fp16 is set (UNIIR_CLIPFF_EMBED_FP16=1 at construction) and its config asks for use_fp16.
+
+precision = "fp32": the reference's model.float() forward -- what use_fp16: False means there -- on the fp32 masters of both stores
+(clipff_model.fusion_forward_f32: exact-fp32 MFMA GEMMs, fp32 attention with the relative bias in uniir_attn_f32_rel_fwd).  The same
+guards, on a module that opted in with embed_fp32 (UNIIR_EMBED_FP32=1 at construction; without it "fp32" stays an unknown precision):
+the embedder then switches to it when its config has use_fp16: False.
 """
 import os
 
@@ -19,7 +24,7 @@ from torch import nn
 
 from uniir_amd import clip_front
 from uniir_amd.blip_model import _attach
-from uniir_amd.clipff_model import FusionFn, t5_param_shapes
+from uniir_amd.clipff_model import FusionFn, fusion_forward_f32, t5_param_shapes
 from uniir_amd.flat_store import FlatStore
 from uniir_amd.losses import HardNegNCEFn, InBatchNCEFn
 
@@ -63,11 +68,16 @@ class CLIPFeatureFusion(nn.Module):
             self.in_batch_neg_num = None
         del self.clip_model.text_projection      # clip_ff.py:104 (unused: the text tower is not pooled / projected)
         # "bf16": the towers without pooling and the T5 stack in bf16, forward and backward.  "fp16": the same launch sequence on fp16
-        # activations and fp16 copies of the weights, forward only (eval mode, no_grad).  Anything else raises at the next encode call.
+        # activations and fp16 copies of the weights, forward only (eval mode, no_grad).  "fp32": the fp32 forward on the fp32 masters of
+        # both stores, forward only under the same guards.  Anything else raises at the next encode call.
         self.precision = "bf16"
         # Whether the embedder's use_fp16 switches precision to "fp16" for an extraction (src/common/mbeir_embedder.py
         # _tower_precision).  Off by default, so that no existing run changes: UNIIR_CLIPFF_EMBED_FP16=1 switches it on at construction.
         self.embed_fp16 = os.environ.get("UNIIR_CLIPFF_EMBED_FP16", "0") not in ("", "0")
+        # Whether the embedder's use_fp16: False switches precision to "fp32" for an extraction (the reference's autocast(enabled=False)
+        # on a model.float() model).  Off by default: UNIIR_EMBED_FP32=1 switches it on at construction.  It is also what makes "fp32" a
+        # precision this module knows: without it precision = "fp32" raises `unknown precision`, as it did before the fp32 forward existed.
+        self.embed_fp32 = os.environ.get("UNIIR_EMBED_FP32", "0") not in ("", "0")
         self._t5 = None
         self._t5_version = -1
         if device is not None and str(device) != "cpu":
@@ -109,26 +119,34 @@ class CLIPFeatureFusion(nn.Module):
 
         return tokenizer_wrapper
 
-    def _embed_half(self):
-        """whether this encode call is the fp16 embedding forward (precision == "fp16"); what that path cannot serve raises"""
-        if self.precision not in ("bf16", "fp16"):
-            raise RuntimeError(f"unknown precision {self.precision!r}")
-        if self.precision == "bf16":
-            return False
+    def _embed_mode(self):
+        """the precision of this encode call: "bf16", or the forward-only embedding path "fp16" / "fp32"; what that path cannot serve
+        raises"""
+        mode = self.precision
+        if mode not in ("bf16", "fp16", "fp32"):
+            raise RuntimeError(f"unknown precision {mode!r}")
+        if mode == "fp32" and not self.embed_fp32:          # the fp32 forward exists for a module that opted in, and only for it
+            raise RuntimeError("unknown precision 'fp32' for a model that has not opted in to the fp32 embedding forward: set "
+                               "embed_fp32 = True (UNIIR_EMBED_FP32=1 at construction) first")
+        if mode == "bf16":
+            return mode
         if self.training:
-            raise RuntimeError("precision='fp16' is a forward-only embedding path; call model.eval() first or use precision='bf16'")
+            raise RuntimeError(f"precision='{mode}' is a forward-only embedding path; call model.eval() first or use precision='bf16'")
         if torch.is_grad_enabled():
-            raise RuntimeError("precision='fp16' is the embedder's forward-only path; run it under torch.no_grad() or switch "
+            raise RuntimeError(f"precision='{mode}' is the embedder's forward-only path; run it under torch.no_grad() or switch "
                                "back to precision='bf16' for training")
-        return True
+        return mode
 
     def encode_multimodal_input(self, txt_tensor, img_tensor, txt_mask=None, img_mask=None):
-        if self._embed_half():          # the fp16 copies of both stores, rebuilt when the weights moved since they were made
+        mode = self._embed_mode()
+        if mode == "fp16":          # the fp16 copies of both stores, rebuilt when the weights moved since they were made
             self.clip_model._sync_half_flat()
             self._ensure_t5().half_shadow()
         else:
             self.clip_model._sync_shadow()
             self._ensure_t5()
+        if mode == "fp32":          # the fp32 masters of both stores
+            return fusion_forward_f32(self, txt_tensor.to(torch.int32).contiguous(), img_tensor.contiguous())
         anchor = torch.zeros(1, device=img_tensor.device, requires_grad=torch.is_grad_enabled())
         return FusionFn.apply(self, txt_tensor.to(torch.int32).contiguous(), img_tensor.contiguous(), anchor)
 
