@@ -123,13 +123,17 @@ def _fakes():
 
 
 @contextlib.contextmanager
-def recording(st):
+def recording(st, fakes=None, recorder=Recorder):
+    """fakes: op -> what stands in for it, for the set of ops a trace meets (default: the MED BERT's, RECORDED); recorder: the Recorder
+    class (it finds the real functions as rec.real)"""
     from uniir_amd import ops
-    rec, fakes = Recorder(st), _fakes()
-    assert set(fakes) == set(RECORDED)
-    real = {n: getattr(ops, n) for n in RECORDED}
+    if fakes is None:
+        fakes = _fakes()
+        assert set(fakes) == set(RECORDED)
+    rec = recorder(st)
+    rec.real = real = {n: getattr(ops, n) for n in fakes}
     try:
-        for n in RECORDED:
+        for n in fakes:
             setattr(ops, n, rec.wrap(n, fakes[n]))
         yield rec
     finally:

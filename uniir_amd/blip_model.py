@@ -21,14 +21,14 @@ stash.  Differences from the reference, stated once:
 import functools
 import json
 import logging
-import os
 
 import torch
 from torch import nn
 
 from . import _lib, comm, ops
-from .clip_model import _linear_f32
 from .flat_store import FlatStore
+from .fp32_forward import attention_f32, layernorm_f32, linear_f32, patch_tokens_f32, tower_fwd_f32
+from .precision import check_mode, embed_mode, env_flag
 from .resblocks import tower_bwd, tower_fwd
 
 VIT_CONFIGS = {   # src/models/uniir_blip/backbone/blip.py:229-255 (create_vit)
@@ -583,45 +583,18 @@ def _pooler_backward(cx, dpooled, stash):
 
 
 # ------------------------------------------------------------------------------------------------------------
-# fp32 forward (precision = "fp32"): the reference's model.float() embedding forward, the launch sequence of
-# clip_model._encode_fp32 for BLIP's two encoders -- every GEMM the exact-fp32 MFMA uniir_sgemm on the fp32 masters of the
-# store (no shadow is read or built), uniir_bias_act_f32 for bias / erf-GELU / residual, the fp32 LayerNorm output,
-# uniir_attention_f32_fwd for the ViT, BERT's self-attention (key_len) and its cross-attention (tq != tk).  It shares
-# nothing with the dtype16 plumbing above.  Forward only; every row dense and every layer full.
+# fp32 forward (precision = "fp32"): the reference's model.float() embedding forward of BLIP's two encoders on the fp32 launch layer
+# (fp32_forward.py), on the fp32 masters of the store: the ViT is its pre-LN tower, BERT's self-attention takes key_len and its
+# cross-attention tq != tk.  It shares nothing with the dtype16 plumbing above.  Forward only; every row dense and every layer full.
 # ------------------------------------------------------------------------------------------------------------
-def _ln_f32(x, w, b, eps):
-    y = torch.empty_like(x)
-    ops.layernorm_fwd(x, w, b, eps, out_f32=y, rows=x.shape[0], width=x.shape[1])
-    return y
-
-
-def _attention_f32(q, q_ld, k, v, kv_ld, key_len, M, tq, tk, heads):
-    out = torch.empty(M * tq, heads * 64, device=q.device, dtype=torch.float32)
-    ops.call("uniir_attention_f32_fwd", q, q_ld, k, v, kv_ld, out, heads * 64, key_len, M, tq, tk, heads, 0, 0.125)
-    return out
-
-
 def vit_forward_f32(st, prefix, cfg, img_size, images):
     """vit_forward in fp32 -> fp32 tokens [M*T, D] after the final norm, and T"""
-    D, P, depth, heads = cfg["embed_dim"], cfg["patch_size"], cfg["depth"], cfg["num_heads"]
-    M, g = images.shape[0], img_size // P
-    T = g * g + 1
     p = lambda name: st.p(prefix + name)          # noqa: E731
-    # im2col is a pure permutation (no arithmetic): [M,3,g,P,g,P] -> [M*g*g, 3*P*P], the order proj.weight.view(D,-1) has
-    patches = images.float().contiguous().view(M, 3, g, P, g, P).permute(0, 2, 4, 1, 3, 5).reshape(M * g * g, 3 * P * P).contiguous()
-    po = _linear_f32(patches, p("patch_embed.proj.weight").view(D, 3 * P * P), p("patch_embed.proj.bias"))
-    x = torch.empty(M * T, D, device=images.device, dtype=torch.float32)
-    ops.call("uniir_vit_assemble_f32", po, p("cls_token"), p("pos_embed"), x, M, T, D)
-    for i in range(depth):
-        n = _vit_blk_names(prefix, i)
-        h = _ln_f32(x, st.p(n["ln1w"]), st.p(n["ln1b"]), VIT_EPS)
-        qkv = _linear_f32(h, st.p(n["wqkv"]), st.p(n["bqkv"]))
-        ao = _attention_f32(qkv, 3 * D, qkv[:, D:], qkv[:, 2 * D:], 3 * D, None, M, T, T, heads)
-        x = _linear_f32(ao, st.p(n["wo"]), st.p(n["bo"]), resid=x)
-        h = _ln_f32(x, st.p(n["ln2w"]), st.p(n["ln2b"]), VIT_EPS)
-        f = _linear_f32(h, st.p(n["wfc"]), st.p(n["bfc"]), act=ops.ACT_GELU_ERF)
-        x = _linear_f32(f, st.p(n["wproj"]), st.p(n["bproj"]), resid=x)
-    return _ln_f32(x, p("norm.weight"), p("norm.bias"), VIT_EPS), T
+    x, T = patch_tokens_f32(images, cfg["patch_size"], p("patch_embed.proj.weight"), p("patch_embed.proj.bias"), p("cls_token"),
+                            p("pos_embed"))
+    x = tower_fwd_f32(st.p, lambda i: _vit_blk_names(prefix, i), cfg["depth"], x, images.shape[0], T, cfg["embed_dim"],
+                      cfg["num_heads"], False, eps=VIT_EPS, act=ops.ACT_GELU_ERF)
+    return layernorm_f32(x, p("norm.weight"), p("norm.bias"), VIT_EPS), T
 
 
 def bert_forward_f32(st, prefix, cfg, ids, key_len, img, Ti, cross=True, pool=True):
@@ -635,32 +608,32 @@ def bert_forward_f32(st, prefix, cfg, ids, key_len, img, Ti, cross=True, pool=Tr
 
     def sublayer(x, name, resid):
         """dense + residual -> LayerNorm (BertSelfOutput / BertOutput)"""
-        return _ln_f32(_linear_f32(x, p(name + "dense.weight"), p(name + "dense.bias"), resid=resid), p(name + "LayerNorm.weight"),
-                       p(name + "LayerNorm.bias"), eps)
+        y = linear_f32(x, p(name + "dense.weight"), p(name + "dense.bias"), resid=resid)
+        return layernorm_f32(y, p(name + "LayerNorm.weight"), p(name + "LayerNorm.bias"), eps)
 
     e = torch.empty(M * L, W, device=dev, dtype=torch.float32)
     scratch = torch.empty(M, device=dev, dtype=torch.int32)
     ops.call("uniir_text_embed", ids, p("embeddings.word_embeddings.weight"), p("embeddings.position_embeddings.weight"), e, scratch,
              M, L, W, cfg["vocab_size"])
-    h = _ln_f32(e, p("embeddings.LayerNorm.weight"), p("embeddings.LayerNorm.bias"), eps)
+    h = layernorm_f32(e, p("embeddings.LayerNorm.weight"), p("embeddings.LayerNorm.bias"), eps)
     for i in range(cfg["num_hidden_layers"]):
         b = f"encoder.layer.{i}."
         s, c = b + "attention.self.", b + "crossattention.self."
-        qkv = _linear_f32(h, p(s + "query.weight", (3 * W, W)), p(s + "query.bias", (3 * W,)))
-        ao = _attention_f32(qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, key_len, M, L, L, heads)
+        qkv = linear_f32(h, p(s + "query.weight", (3 * W, W)), p(s + "query.bias", (3 * W,)))
+        ao = attention_f32(qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, key_len, M, L, L, heads)
         h = sublayer(ao, b + "attention.output.", h)
         if cross:
-            cq = _linear_f32(h, p(c + "query.weight"), p(c + "query.bias"))
-            ckv = _linear_f32(img, p(c + "key.weight", (2 * W, img.shape[1])), p(c + "key.bias", (2 * W,)))
-            co = _attention_f32(cq, W, ckv, ckv[:, W:], 2 * W, None, M, L, Ti, heads)
+            cq = linear_f32(h, p(c + "query.weight"), p(c + "query.bias"))
+            ckv = linear_f32(img, p(c + "key.weight", (2 * W, img.shape[1])), p(c + "key.bias", (2 * W,)))
+            co = attention_f32(cq, W, ckv, ckv[:, W:], 2 * W, None, M, L, Ti, heads)
             h = sublayer(co, b + "crossattention.output.", h)
-        f = _linear_f32(h, p(b + "intermediate.dense.weight"), p(b + "intermediate.dense.bias"), act=ops.ACT_GELU_ERF)
+        f = linear_f32(h, p(b + "intermediate.dense.weight"), p(b + "intermediate.dense.bias"), act=ops.ACT_GELU_ERF)
         h = sublayer(f, b + "output.", h)
     rows = torch.empty(M, W, device=dev, dtype=torch.float32)
     ops.call("uniir_gather_rows", h, None, rows, M, L, W)          # the class token = row 0 of every item
     if not pool:
         return rows
-    pre = _linear_f32(rows, p("pooler.dense.weight"), p("pooler.dense.bias"))
+    pre = linear_f32(rows, p("pooler.dense.weight"), p("pooler.dense.bias"))
     pooled = torch.empty_like(pre)
     ops.call("uniir_tanh_fwd", pre, pooled, pre.numel())
     return pooled
@@ -864,25 +837,15 @@ class BLIPFeatureFusion(nn.Module):
         # Embeddings, train-mode outputs and the loss are bitwise those of the full layer; weight gradients are the same sums over
         # fewer rows.  Off by default (profiles/blip_pooled_last_layer.txt has the measurement): UNIIR_BLIP_POOL_LAST_LAYER=1
         # switches it on at construction.  A plain attribute: may be changed between steps; must be the same on every rank.
-        self.pool_last_layer = os.environ.get("UNIIR_BLIP_POOL_LAST_LAYER", "0") not in ("", "0")
-        # The 16-bit type of the embedding forward: "bf16" (the training kernels), or "fp16": encode_multimodal_input -- and with it
-        # encode_mbeir_batch and forward(encode_mbeir_batch=True) -- runs ViT and BERT (and BLIP_SF's projections) on fp16 activations
-        # from the online store's fp16 shadow, under no_grad, and returns fp32 embeddings as always: the reference embedder's
-        # autocast(fp16), 1e-3 from the fp32 oracle instead of bf16's 6e-3.  Eval mode and the online encoder only.  A plain attribute.
-        # "fp32": the same calls run the reference's model.float() forward -- what an embed YAML with use_fp16: False means -- in exact-fp32
-        # MFMA GEMMs, fp32 attention and LayerNorm on the fp32 masters of the online store (vit_forward_f32 / bert_forward_f32: a launch
-        # sequence of its own, no shadow is read or built).  Eval mode, torch.no_grad() and the online encoder only.  pack_text,
-        # pool_last_layer and vit_grad_ckpt change nothing on it: every row is dense and every layer full (skipping padded keys and adding
-        # -10000 to their logits are the same fp32 softmax).  Reference precision, not throughput (profiles/embed_fp32.txt).
+        self.pool_last_layer = env_flag("UNIIR_BLIP_POOL_LAST_LAYER")
+        # precision / embed_fp16 / embed_fp32: precision.py.  Here "fp16" and "fp32" are what encode_multimodal_input -- and with it
+        # encode_mbeir_batch and forward(encode_mbeir_batch=True) -- runs: ViT and BERT (and BLIP_SF's projections), eval mode and the
+        # online encoder only ("fp16" from the online store's fp16 shadow under a no_grad of its own, "fp32" under the caller's).  On
+        # "fp32" pack_text, pool_last_layer and vit_grad_ckpt change nothing: every row is dense and every layer full (skipping padded
+        # keys and adding -10000 to their logits are the same fp32 softmax).
         self.precision = "bf16"
-        # Whether the embedder's use_fp16 switches precision to "fp16" for an extraction (src/common/mbeir_embedder.py
-        # _tower_precision).  Off by default, so that no existing run changes: UNIIR_BLIP_EMBED_FP16=1 switches it on at construction.
-        self.embed_fp16 = os.environ.get("UNIIR_BLIP_EMBED_FP16", "0") not in ("", "0")
-        # Whether the embedder's use_fp16: False switches precision to "fp32" for an extraction (the reference's autocast(enabled=False)
-        # on a model.float() model).  Off by default, so that no existing run changes: UNIIR_EMBED_FP32=1 switches it on at construction.
-        # It is also what makes "fp32" a precision this module knows: without it precision = "fp32" raises `unknown precision`, as it
-        # did before the fp32 forward existed, so a model that has not opted in behaves in every respect as it always did.
-        self.embed_fp32 = os.environ.get("UNIIR_EMBED_FP32", "0") not in ("", "0")
+        self.embed_fp16 = env_flag("UNIIR_BLIP_EMBED_FP16")
+        self.embed_fp32 = env_flag("UNIIR_EMBED_FP32")
         self.path_log = []                # one line per BERT pass whose last layer ran on the class rows (the newest 64)
 
     def _path_log(self):
@@ -1059,12 +1022,8 @@ class BLIPFeatureFusion(nn.Module):
         activations from fp16 copies of the weights (vit_forward's dtype16) -- the reference embedder's arithmetic
         (mbeir_embedder.py:52-56: autocast(fp16)), 577 tokens at 384 pixels included.  fp16 is an eval-mode path: in training mode
         it raises (DropPath belongs to the bf16 training forward)."""
-        if precision not in ("bf16", "fp16"):
-            raise RuntimeError(f"unknown precision {precision!r}")
+        check_mode(precision, ("bf16", "fp16"), self.training)
         if precision == "fp16":
-            if self.training:
-                raise RuntimeError("precision='fp16' is a forward-only embedding path; call model.eval() first or use "
-                                   "precision='bf16'")
             st = self._sync_half()
             conv, dt, drop = self._conv16h, torch.float16, None
         else:
@@ -1075,25 +1034,7 @@ class BLIPFeatureFusion(nn.Module):
         return tok.view(image_batched.shape[0], T, -1)
 
     def _embed_mode(self, use_momentum):
-        """the precision of this encode call: "bf16", or the forward-only embedding path "fp16" / "fp32"; what that path cannot serve
-        raises"""
-        mode = self.precision
-        if mode not in ("bf16", "fp16", "fp32"):
-            raise RuntimeError(f"unknown precision {mode!r}")
-        if mode == "fp32" and not self.embed_fp32:          # the fp32 forward exists for a module that opted in, and only for it
-            raise RuntimeError("unknown precision 'fp32' for a model that has not opted in to the fp32 embedding forward: set "
-                               "embed_fp32 = True (UNIIR_EMBED_FP32=1 at construction) first")
-        if mode == "bf16":
-            return mode
-        if self.training:
-            raise RuntimeError(f"precision='{mode}' is a forward-only embedding path; call model.eval() first or use precision='bf16'")
-        if use_momentum:
-            raise RuntimeError(f"precision='{mode}' is the online encoder's embedding path" + (": the fp16 shadow exists for the online "
-                               "store only" if mode == "fp16" else "") + " (use_momentum=True needs precision='bf16')")
-        if mode == "fp32" and torch.is_grad_enabled():
-            raise RuntimeError("precision='fp32' is a forward-only path (embedding extraction / parity); run it under torch.no_grad() or "
-                               "switch back to precision='bf16' for training")
-        return mode
+        return embed_mode(self, use_momentum=use_momentum)
 
     def _encode_inputs(self, txt_dict_batched, use_momentum):
         """what every encode call starts with: the stores brought up to date, the token ids and key lengths, the TextPack
@@ -1278,8 +1219,8 @@ class BLIPScoreFusion(BLIPFeatureFusion):
         tok, T = vit_forward_f32(st, "visual_encoder.", self.vit_cfg, self.image_size, images)
         ifeat = tok.view(M, T, -1)[:, 0].contiguous()                     # class-token rows (a copy)
         tfeat = bert_forward_f32(st, "text_encoder.", self.med_cfg, ids, key_len, None, 0, cross=False, pool=False)
-        temb = _linear_f32(tfeat, st.p("text_proj.weight"), st.p("text_proj.bias"))
-        iemb = _linear_f32(ifeat, st.p("vision_proj.weight"), st.p("vision_proj.bias"))
+        temb = linear_f32(tfeat, st.p("text_proj.weight"), st.p("text_proj.bias"))
+        iemb = linear_f32(ifeat, st.p("vision_proj.weight"), st.p("vision_proj.bias"))
         emb = torch.empty(M, E, device=ids.device, dtype=torch.float32)
         ops.call("uniir_fuse_embeddings", temb, iemb, tmask, imask, emb, M, E)
         return emb

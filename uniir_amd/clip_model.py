@@ -18,6 +18,9 @@ from torch import nn
 
 from . import _lib, ops
 from .flat_store import FlatStore
+from .fp32_forward import layernorm_f32, linear_f32, patch_tokens_f32, tower_fwd_f32
+from .precision import env_flag
+from .resblocks import clip_block_names
 
 _SIDE_STREAMS = {}          # device index -> the torch stream that carries the text leg of two-stream towers (CLIP.side_leg)
 
@@ -145,16 +148,10 @@ class CLIP(nn.Module):
         self.logit_scale = nn.Parameter(torch.ones([]) * math.log(1 / 0.07))
         self._flat = None          # the FlatStore of the parameters (built lazily on the device, _ensure_flat)
         self.kpad = (3 * P * P + 63) // 64 * 64
-        # "bf16": MFMA towers, forward + backward (training / fast extraction).  "fp16": the same MFMA towers with fp16 operands and
-        # activations, FORWARD ONLY -- the reference embedder's precision (mbeir_embedder.py:52-56: autocast(fp16) then .half()),
-        # same speed as bf16 (the fp16 MFMA rate is the bf16 rate), 3 more mantissa bits: embeddings 1e-3 instead of 6e-3 from the
-        # fp32 path; weights are read from an fp16 shadow that is refreshed with the bf16 one.  "fp32": the reference's model.float()
-        # forward in exact-fp32 MFMA GEMMs + fp32 attention (csrc/fp32_path.hip): reference-precision embeddings, no backward
+        # precision / embed_fp32: precision.py.  Here "fp16" and "fp32" are the C towers' forward-only paths (_TowerFn); the weights of
+        # "fp16" are read from an fp16 shadow that is refreshed with the bf16 one.
         self.precision = "bf16"
-        # Whether the embedder's use_fp16: False switches precision to "fp32" for an extraction (src/common/mbeir_embedder.py
-        # _tower_precision: the reference's autocast(enabled=False) on a model.float() model).  Off by default, so that no existing run
-        # changes: UNIIR_EMBED_FP32=1 switches it on at construction.
-        self.embed_fp32 = os.environ.get("UNIIR_EMBED_FP32", "0") not in ("", "0")
+        self.embed_fp32 = env_flag("UNIIR_EMBED_FP32")
         # exact text-row packing (csrc/tower.hip *_packed): the text tower runs on the tokens up to each caption's EOT only.  Rows
         # behind the EOT never reach the pooled feature under the causal mask (clip_sf.py:43-44), so results are those of the dense
         # tower (embeddings and activation gradients bitwise, weight gradients up to the order of fp32 additions).
@@ -177,14 +174,14 @@ class CLIP(nn.Module):
         # bit; the gradients upstream of the last block's attention agree with the full block's to bf16 rounding (another valid bf16
         # backward kernel), so it is off by default: UNIIR_POOL_LAST_BLOCK_LONG=1 switches it on at construction.  Without
         # pool_last_block it does nothing; at 512 tokens and below it changes nothing.  Must be the same on every rank.
-        self.pool_last_block_long = os.environ.get("UNIIR_POOL_LAST_BLOCK_LONG", "0") not in ("", "0")
+        self.pool_last_block_long = env_flag("UNIIR_POOL_LAST_BLOCK_LONG")
         # Activation recomputation in the C towers (uniir_clip_tower.recompute, csrc/tower.hip): the training forward keeps only the
         # fp32 residual stream that enters each block (4 of the 28 - 36 stashed bytes per row x width element per layer) and the
         # backward rebuilds each block's intermediates from it, with the forward's own launches, right before that block's backward.
         # Bitwise the results of the stored run with stash_act = True (act(f) exists once in the shared layer buffers, so stash_act
         # has nothing to decide here); costs one more pass over the blocks' sublayers minus their c_proj GEMM per step.  For batches
         # whose stash does not fit.  UNIIR_RECOMPUTE_BLOCKS=1 switches it on at construction; must be the same on every rank.
-        self.recompute_blocks = os.environ.get("UNIIR_RECOMPUTE_BLOCKS", "0") not in ("", "0")
+        self.recompute_blocks = env_flag("UNIIR_RECOMPUTE_BLOCKS")
         self._recompute_logged = set()    # towers whose "recomputation is on" line is in stash_log already
         self._full_last_logged = set()    # towers whose "full last block" / "pooled last block above 512 tokens" line is in stash_log already
         self.stash_margin_bytes = 16 << 30
@@ -496,88 +493,42 @@ class CLIP(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------------------
-# fp32 forward (precision = "fp32"): the same block sequence on uniir_sgemm (exact-fp32 MFMA) + uniir_bias_act_f32 +
-# uniir_attention_f32_fwd + the fp32 LayerNorm kernel.  openai/CLIP model.py semantics as restated in SURVEY.md 3.2.
+# fp32 forward (precision = "fp32"): the same block sequence on the fp32 launch layer (fp32_forward.py).  openai/CLIP model.py
+# semantics as restated in SURVEY.md 3.2.
 # ------------------------------------------------------------------------------------------------------------
-def _linear_f32(x, w, bias=None, *, act=-1, resid=None):
-    """y[M,N] = act(x[M,K] @ w[N,K]^T + bias) (+ resid), all fp32"""
-    M, K = x.shape
-    N = w.shape[0]
-    y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-    ops.call("uniir_sgemm", x, K, 1, w, 1, K, y, N, M, N, K, 1.0)
-    if bias is not None or resid is not None or act >= 0:
-        ops.call("uniir_bias_act_f32", y, bias, resid, M, N, act)
-    return y
-
-
-def _tower_fwd_f32(model, prefix, layers, x, M, T, W, heads, causal, p32):
-    R = M * T
-    for i in range(layers):
-        p = f"{prefix}.resblocks.{i}"
-        h = torch.empty(R, W, device=x.device, dtype=torch.float32)
-        ops.layernorm_fwd(x, p32(f"{p}.ln_1.weight"), p32(f"{p}.ln_1.bias"), out_f32=h, rows=R, width=W)
-        qkv = _linear_f32(h, p32(f"{p}.attn.in_proj_weight"), p32(f"{p}.attn.in_proj_bias"))
-        ao = torch.empty(R, W, device=x.device, dtype=torch.float32)
-        ops.call("uniir_attention_f32_fwd", qkv, 3 * W, qkv[:, W:], qkv[:, 2 * W:], 3 * W, ao, W, None, M, T, T, heads,
-                 int(causal), 0.125)
-        x = _linear_f32(ao, p32(f"{p}.attn.out_proj.weight"), p32(f"{p}.attn.out_proj.bias"), resid=x)
-        ops.layernorm_fwd(x, p32(f"{p}.ln_2.weight"), p32(f"{p}.ln_2.bias"), out_f32=h, rows=R, width=W)
-        g = _linear_f32(h, p32(f"{p}.mlp.c_fc.weight"), p32(f"{p}.mlp.c_fc.bias"), act=ops.ACT_QUICKGELU)
-        x = _linear_f32(g, p32(f"{p}.mlp.c_proj.weight"), p32(f"{p}.mlp.c_proj.bias"), resid=x)
-    return x
-
-
-def _image_blocks_f32(model, image, p32):
+def image_blocks_f32(model, image):
     """the vision tower up to its last residual block, every token: image [M,3,res,res] -> x fp32 [M*T, W], T"""
-    cfg = model.cfg
-    dev, M = image.device, image.shape[0]
-    W, P, L = cfg["vision_width"], cfg["vision_patch_size"], cfg["vision_layers"]
-    res = cfg["image_resolution"]
-    g = res // P
-    T = g * g + 1
-    # im2col is a pure permutation (no arithmetic): [M,3,g,P,g,P] -> [M*g*g, 3*P*P], the order conv1.weight.view(W,-1) has
-    patches = image.float().view(M, 3, g, P, g, P).permute(0, 2, 4, 1, 3, 5).reshape(M * g * g, 3 * P * P).contiguous()
-    po = _linear_f32(patches, p32("visual.conv1.weight").view(W, 3 * P * P))
-    x0 = torch.empty(M * T, W, device=dev, dtype=torch.float32)
-    ops.call("uniir_vit_assemble_f32", po, p32("visual.class_embedding"), p32("visual.positional_embedding"), x0, M, T, W)
-    x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
-    ops.layernorm_fwd(x0, p32("visual.ln_pre.weight"), p32("visual.ln_pre.bias"), out_f32=x, rows=M * T, width=W)
-    return _tower_fwd_f32(model, "visual.transformer", L, x, M, T, W, W // 64, False, p32), T
+    cfg, p32 = model.cfg, model._flat.p
+    W, M = cfg["vision_width"], image.shape[0]
+    x0, T = patch_tokens_f32(image, cfg["vision_patch_size"], p32("visual.conv1.weight"), None, p32("visual.class_embedding"),
+                             p32("visual.positional_embedding"))
+    x = layernorm_f32(x0, p32("visual.ln_pre.weight"), p32("visual.ln_pre.bias"))
+    return tower_fwd_f32(p32, lambda i: clip_block_names("visual.transformer", i), cfg["vision_layers"], x, M, T, W, W // 64, False), T
 
 
-def _text_blocks_f32(model, text, p32):
+def text_blocks_f32(model, text):
     """the text tower up to its last residual block, every token: text int32 [M,ctx] -> x fp32 [M*T, W], the EOT positions, T"""
-    cfg = model.cfg
+    cfg, p32 = model.cfg, model._flat.p
     dev, M = text.device, text.shape[0]
     W, L, T = cfg["transformer_width"], cfg["transformer_layers"], cfg["context_length"]
     x = torch.empty(M * T, W, device=dev, dtype=torch.float32)
     eot = torch.empty(M, device=dev, dtype=torch.int32)
     ops.call("uniir_text_embed", text, p32("token_embedding.weight"), p32("positional_embedding"), x, eot, M, T, W,
              cfg["vocab_size"])
-    return _tower_fwd_f32(model, "transformer", L, x, M, T, W, cfg["transformer_heads"], True, p32), eot, T
+    return tower_fwd_f32(p32, lambda i: clip_block_names("transformer", i), L, x, M, T, W, cfg["transformer_heads"], True), eot, T
 
 
 def _encode_fp32(model, which, inp, p32):
-    cfg = model.cfg
-    dev = inp.device
-    E, M = cfg["embed_dim"], inp.shape[0]
+    M = inp.shape[0]
     if which == "image":
-        W = cfg["vision_width"]
-        x, T = _image_blocks_f32(model, inp, p32)
-        rows = torch.empty(M, W, device=dev, dtype=torch.float32)
-        ops.call("uniir_gather_rows", x, None, rows, M, T, W)
+        (x, T), eot = image_blocks_f32(model, inp), None
         lnw, lnb, proj = "visual.ln_post.weight", "visual.ln_post.bias", "visual.proj"
     else:
-        W = cfg["transformer_width"]
-        x, eot, T = _text_blocks_f32(model, inp, p32)
-        rows = torch.empty(M, W, device=dev, dtype=torch.float32)
-        ops.call("uniir_gather_rows", x, eot, rows, M, T, W)
+        x, eot, T = text_blocks_f32(model, inp)
         lnw, lnb, proj = "ln_final.weight", "ln_final.bias", "text_projection"
-    pooled = torch.empty(M, W, device=dev, dtype=torch.float32)
-    ops.layernorm_fwd(rows, p32(lnw), p32(lnb), out_f32=pooled, rows=M, width=W)
-    emb = torch.empty(M, E, device=dev, dtype=torch.float32)
-    ops.call("uniir_sgemm", pooled, W, 1, p32(proj), E, 1, emb, E, M, E, W, 1.0)      # pooled @ proj, proj [W, E]
-    return emb
+    rows = torch.empty(M, x.shape[1], device=inp.device, dtype=torch.float32)
+    ops.call("uniir_gather_rows", x, eot, rows, M, T, x.shape[1])
+    return linear_f32(layernorm_f32(rows, p32(lnw), p32(lnb)), p32(proj), w_kn=True)          # pooled @ proj, proj [W, E]
 
 
 def _join_backward(st, demb):

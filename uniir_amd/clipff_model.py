@@ -20,7 +20,8 @@ import math
 import torch
 
 from . import ops
-from .clip_model import _image_blocks_f32, _linear_f32, _text_blocks_f32
+from .clip_model import image_blocks_f32, text_blocks_f32
+from .fp32_forward import layernorm_f32, linear_f32, rmsnorm_f32
 from .resblocks import block_set_bytes, clip_block_names, tower_bwd, tower_fwd
 
 T5_EPS = 1e-6
@@ -324,57 +325,42 @@ def text_tokens_bwd(model, dtok, stash):
 
 
 # ------------------------------------------------------------------------------------------------------------
-# fp32 forward (CLIPFeatureFusion.precision = "fp32"): the reference's model.float() embedding forward.  The towers without pooling
-# are clip_model's fp32 blocks (_image_blocks_f32 / _text_blocks_f32, the stems and blocks of clip_model._encode_fp32) followed by
-# ln_post + visual.proj / ln_final on every token; the T5 stack is uniir_rmsnorm_fwd's fp32 output, uniir_sgemm, the fp32
-# relative-bias attention uniir_attn_f32_rel_fwd (csrc/fp32_path.hip) and ReLU through uniir_bias_act_f32.  Both stores' fp32 masters
-# are read directly.  Forward only, eval mode: no stash, no dropout.
+# fp32 forward (CLIPFeatureFusion.precision = "fp32"): the reference's model.float() embedding forward on the fp32 launch layer
+# (fp32_forward.py).  The towers without pooling are clip_model's fp32 blocks followed by ln_post + visual.proj / ln_final on every
+# token; the T5 stack adds the fp32 relative-bias attention uniir_attn_f32_rel_fwd (csrc/fp32_path.hip).  Both stores' fp32 masters are
+# read directly.  Forward only, eval mode: no stash, no dropout.
 # ------------------------------------------------------------------------------------------------------------
 def t5_forward_f32(st, prefix, x, M, T, heads, layers):
     """x fp32 [M*T, D] (the concatenated tokens) -> pooled fp32 [M, D]: t5_forward's eval-mode sequence in fp32"""
     R, D = x.shape
     inner = heads * 64
-    dev = x.device
-    table = _table(T, dev)
+    table = _table(T, x.device)
     rel = st.p(prefix + "block.0.layer.0.SelfAttention.relative_attention_bias.weight")
-
-    def rms(x, name):
-        y = torch.empty(R, D, device=dev, dtype=torch.float32)
-        ops.call("uniir_rmsnorm_fwd", x, D, st.p(name), None, y, R, D, T5_EPS)
-        return y
-
     for i in range(layers):
         a, f = f"{prefix}block.{i}.layer.0.", f"{prefix}block.{i}.layer.1."
-        qkv = _linear_f32(rms(x, a + "layer_norm.weight"), st.p(a + "SelfAttention.q.weight", (3 * inner, D)))
-        ao = torch.empty(R, inner, device=dev, dtype=torch.float32)
+        qkv = linear_f32(rmsnorm_f32(x, st.p(a + "layer_norm.weight"), T5_EPS), st.p(a + "SelfAttention.q.weight", (3 * inner, D)))
+        ao = torch.empty(R, inner, device=x.device, dtype=torch.float32)
         ops.call("uniir_attn_f32_rel_fwd", qkv, ao, rel, table, T5_BUCKETS, 1.0, M, T, heads)
-        x = _linear_f32(ao, st.p(a + "SelfAttention.o.weight"), resid=x)
-        g = _linear_f32(rms(x, f + "layer_norm.weight"), st.p(f + "DenseReluDense.wi.weight"), act=ops.ACT_RELU)
-        x = _linear_f32(g, st.p(f + "DenseReluDense.wo.weight"), resid=x)
-    pooled = torch.empty(M, D, device=dev, dtype=torch.float32)
-    ops.call("uniir_meanpool_fwd", rms(x, prefix + "final_layer_norm.weight"), pooled, M, T, D)
+        x = linear_f32(ao, st.p(a + "SelfAttention.o.weight"), resid=x)
+        g = linear_f32(rmsnorm_f32(x, st.p(f + "layer_norm.weight"), T5_EPS), st.p(f + "DenseReluDense.wi.weight"), act=ops.ACT_RELU)
+        x = linear_f32(g, st.p(f + "DenseReluDense.wo.weight"), resid=x)
+    pooled = torch.empty(M, D, device=x.device, dtype=torch.float32)
+    ops.call("uniir_meanpool_fwd", rmsnorm_f32(x, st.p(prefix + "final_layer_norm.weight"), T5_EPS), pooled, M, T, D)
     return pooled
 
 
 def vision_tokens_f32(model, image):
     """vision_tokens_fwd in fp32 -> fp32 [M*T, E] = ln_post(all tokens) @ proj, and T"""
-    cfg, p32 = model.cfg, model._flat.p
-    W, E = cfg["vision_width"], cfg["embed_dim"]
-    x, T = _image_blocks_f32(model, image, p32)
-    ln = torch.empty_like(x)
-    ops.layernorm_fwd(x, p32("visual.ln_post.weight"), p32("visual.ln_post.bias"), out_f32=ln, rows=x.shape[0], width=W)
-    tok = torch.empty(x.shape[0], E, device=x.device, dtype=torch.float32)
-    ops.call("uniir_sgemm", ln, W, 1, p32("visual.proj"), E, 1, tok, E, x.shape[0], E, W, 1.0)      # ln @ proj, proj [W, E]
-    return tok, T
+    p32 = model._flat.p
+    x, T = image_blocks_f32(model, image)
+    ln = layernorm_f32(x, p32("visual.ln_post.weight"), p32("visual.ln_post.bias"))
+    return linear_f32(ln, p32("visual.proj"), w_kn=True), T          # ln @ proj, proj [W, E]
 
 
 def text_tokens_f32(model, text):
     """text_tokens_fwd in fp32 -> fp32 [M*77, W] = ln_final(all tokens), and the context length"""
-    cfg, p32 = model.cfg, model._flat.p
-    x, _, T = _text_blocks_f32(model, text, p32)
-    tok = torch.empty_like(x)
-    ops.layernorm_fwd(x, p32("ln_final.weight"), p32("ln_final.bias"), out_f32=tok, rows=x.shape[0], width=cfg["transformer_width"])
-    return tok, T
+    x, _, T = text_blocks_f32(model, text)
+    return layernorm_f32(x, model._flat.p("ln_final.weight"), model._flat.p("ln_final.bias")), T
 
 
 def fusion_forward_f32(owner, text, image):

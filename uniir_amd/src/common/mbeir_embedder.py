@@ -33,55 +33,36 @@ from dist_utils import ContiguousDistributedSampler
 from utils import build_model_from_config, set_seed
 
 
-def _clip_towers(model):
-    """the uniir_amd CLIP module behind a CLIP_SF / CLIP_FF model (DDP-wrapped or not), or None (BLIP)"""
+def _precision_carriers(model):
+    """(module, is it a CLIP tower module?) for every module of `model` (DDP-wrapped or not) that carries a precision
+    (uniir_amd/precision.py): the CLIP module behind a CLIP_SF / CLIP_FF model, whose towers always took fp16, and the model itself
+    when it has embed_fp16 (BLIP_FF / BLIP_SF, and CLIP_FF, whose encode path follows its own precision, not the inner CLIP module's)"""
     inner = getattr(model, "module", model)
     clip = getattr(inner, "clip_model", None)
-    return clip if hasattr(clip, "precision") else None
-
-
-def _clipff_module(model):
-    """the uniir_amd CLIP_FF module (DDP-wrapped or not), or None: the model around a CLIP module that carries its own precision and
-    embed_fp16 (its T5 stack and the towers without pooling follow the module's precision, not the inner CLIP module's)"""
-    inner = getattr(model, "module", model)
-    return inner if _clip_towers(model) is not None and hasattr(inner, "embed_fp16") and hasattr(inner, "precision") else None
-
-
-def _blip_module(model):
-    """the uniir_amd BLIP_FF / BLIP_SF module (DDP-wrapped or not), or None (CLIP): it carries its own precision and embed_fp16"""
-    inner = getattr(model, "module", model)
-    return inner if hasattr(inner, "embed_fp16") and hasattr(inner, "precision") else None
+    return ([(clip, True)] if hasattr(clip, "precision") else []) + (
+        [(inner, False)] if hasattr(inner, "embed_fp16") and hasattr(inner, "precision") else [])
 
 
 @contextlib.contextmanager
 def _tower_precision(model, use_fp16):
-    # the reference runs the towers under torch.cuda.amp.autocast(enabled=use_fp16) (:52-56) -- fp16 matmuls: the CLIP towers here take
-    # their fp16 forward for the extraction (clip_model.precision = "fp16") and go back to what they were set to afterwards.  A BLIP
-    # model does the same when it opted in (BLIPFeatureFusion.embed_fp16, UNIIR_BLIP_EMBED_FP16=1); without that its extraction stays
-    # in bf16 whatever use_fp16 says, as it always was.  CLIP_FF is the BLIP case: its encode path follows the precision of the
-    # CLIPFeatureFusion module itself, which is switched only when the module opted in (embed_fp16, UNIIR_CLIPFF_EMBED_FP16=1); the
-    # precision of its inner CLIP module is switched as for CLIP_SF and read by nothing on that path.
-    # use_fp16: False is autocast(enabled=False) on the reference's model.float() model, an fp32 forward: a module that opted in
-    # (embed_fp32, UNIIR_EMBED_FP32=1 at construction; each of the CLIP module, the BLIP module and the CLIP_FF module carries its own)
-    # takes its precision = "fp32" for the extraction, in the same way; without that the extraction stays in bf16, as it always was
-    clip = _clip_towers(model)
-    blip = _blip_module(model) if clip is None else _clipff_module(model)
-    restore = restore_blip = None
-    if clip is not None and use_fp16 and clip.precision == "bf16":
-        restore, clip.precision = clip.precision, "fp16"
-    if blip is not None and use_fp16 and blip.embed_fp16 and blip.precision == "bf16":
-        restore_blip, blip.precision = blip.precision, "fp16"
-    if clip is not None and not use_fp16 and getattr(clip, "embed_fp32", False) and clip.precision == "bf16":
-        restore, clip.precision = clip.precision, "fp32"
-    if blip is not None and not use_fp16 and getattr(blip, "embed_fp32", False) and blip.precision == "bf16":
-        restore_blip, blip.precision = blip.precision, "fp32"
+    # the reference runs the towers under torch.cuda.amp.autocast(enabled=use_fp16) (:52-56) on a model.float() model: fp16 matmuls, or
+    # (use_fp16: False) an fp32 forward.  Every carrier that stands at "bf16" takes that precision for the extraction if it may -- "fp16":
+    # a CLIP tower module always, any other with embed_fp16; "fp32": with embed_fp32 -- and goes back afterwards.  Without the opt-in
+    # the extraction stays in bf16 whatever use_fp16 says, as it always was; a precision set by hand stays.
+    switched = []
     try:
+        for m, tower in _precision_carriers(model):
+            if use_fp16:
+                target = "fp16" if tower or m.embed_fp16 else None
+            else:
+                target = "fp32" if getattr(m, "embed_fp32", False) else None
+            if target is not None and m.precision == "bf16":
+                switched.append(m)
+                m.precision = target
         yield
     finally:
-        if restore is not None:
-            clip.precision = restore
-        if restore_blip is not None:
-            blip.precision = restore_blip
+        for m in switched:
+            m.precision = "bf16"
 
 
 @torch.no_grad()

@@ -8,17 +8,10 @@ T5Config defaults d_ff 2048 / ReLU / 32 buckets), encode_text :148-156, encode_i
 :161-192 (the masks are accepted and unused, like there), compute_inbatch_contrastive_loss :194-265 (identical to
 CLIP_SF's, incl. the hard-negative branch), encode_mbeir_batch :272-298.  T5 dropout 0.1 is not applied.
 
-precision = "fp16": the embedding forward with fp16 activations and fp16 copies of the weights (clipff_model, dtype16 =
-torch.float16) -- the reference embedder's autocast(fp16).  Eval mode under torch.no_grad() only; the embedder switches to it for an
-extraction when embed_fp16 is set (UNIIR_CLIPFF_EMBED_FP16=1 at construction) and its config asks for use_fp16.
-
-precision = "fp32": the reference's model.float() forward -- what use_fp16: False means there -- on the fp32 masters of both stores
-(clipff_model.fusion_forward_f32: exact-fp32 MFMA GEMMs, fp32 attention with the relative bias in uniir_attn_f32_rel_fwd).  The same
-guards, on a module that opted in with embed_fp32 (UNIIR_EMBED_FP32=1 at construction; without it "fp32" stays an unknown precision):
-the embedder then switches to it when its config has use_fp16: False.
+precision (uniir_amd/precision.py) = "fp16": the embedding forward with fp16 activations and fp16 copies of the weights (clipff_model,
+dtype16 = torch.float16); "fp32": on the fp32 masters of both stores (clipff_model.fusion_forward_f32: exact-fp32 MFMA GEMMs, fp32
+attention with the relative bias in uniir_attn_f32_rel_fwd).  Both in eval mode under torch.no_grad() only.
 """
-import os
-
 import torch
 from torch import nn
 
@@ -27,6 +20,7 @@ from uniir_amd.blip_model import _attach
 from uniir_amd.clipff_model import FusionFn, fusion_forward_f32, t5_param_shapes
 from uniir_amd.flat_store import FlatStore
 from uniir_amd.losses import HardNegNCEFn, InBatchNCEFn
+from uniir_amd.precision import embed_mode, env_flag
 
 _T5_DMODEL = {"ViT-B/32": 512, "ViT-L/14": 768, "ViT-L/14@336px": 768}      # @336px: 77 + 577 = 654 fused tokens
 
@@ -67,17 +61,11 @@ class CLIPFeatureFusion(nn.Module):
             self.gather_embeddings = None
             self.in_batch_neg_num = None
         del self.clip_model.text_projection      # clip_ff.py:104 (unused: the text tower is not pooled / projected)
-        # "bf16": the towers without pooling and the T5 stack in bf16, forward and backward.  "fp16": the same launch sequence on fp16
-        # activations and fp16 copies of the weights, forward only (eval mode, no_grad).  "fp32": the fp32 forward on the fp32 masters of
-        # both stores, forward only under the same guards.  Anything else raises at the next encode call.
+        # precision / embed_fp16 / embed_fp32: uniir_amd/precision.py.  Here they govern the towers without pooling and the T5 stack of
+        # an encode call, on both stores; the precision of the inner CLIP module is read by nothing on that path.
         self.precision = "bf16"
-        # Whether the embedder's use_fp16 switches precision to "fp16" for an extraction (src/common/mbeir_embedder.py
-        # _tower_precision).  Off by default, so that no existing run changes: UNIIR_CLIPFF_EMBED_FP16=1 switches it on at construction.
-        self.embed_fp16 = os.environ.get("UNIIR_CLIPFF_EMBED_FP16", "0") not in ("", "0")
-        # Whether the embedder's use_fp16: False switches precision to "fp32" for an extraction (the reference's autocast(enabled=False)
-        # on a model.float() model).  Off by default: UNIIR_EMBED_FP32=1 switches it on at construction.  It is also what makes "fp32" a
-        # precision this module knows: without it precision = "fp32" raises `unknown precision`, as it did before the fp32 forward existed.
-        self.embed_fp32 = os.environ.get("UNIIR_EMBED_FP32", "0") not in ("", "0")
+        self.embed_fp16 = env_flag("UNIIR_CLIPFF_EMBED_FP16")
+        self.embed_fp32 = env_flag("UNIIR_EMBED_FP32")
         self._t5 = None
         self._t5_version = -1
         if device is not None and str(device) != "cpu":
@@ -120,22 +108,7 @@ class CLIPFeatureFusion(nn.Module):
         return tokenizer_wrapper
 
     def _embed_mode(self):
-        """the precision of this encode call: "bf16", or the forward-only embedding path "fp16" / "fp32"; what that path cannot serve
-        raises"""
-        mode = self.precision
-        if mode not in ("bf16", "fp16", "fp32"):
-            raise RuntimeError(f"unknown precision {mode!r}")
-        if mode == "fp32" and not self.embed_fp32:          # the fp32 forward exists for a module that opted in, and only for it
-            raise RuntimeError("unknown precision 'fp32' for a model that has not opted in to the fp32 embedding forward: set "
-                               "embed_fp32 = True (UNIIR_EMBED_FP32=1 at construction) first")
-        if mode == "bf16":
-            return mode
-        if self.training:
-            raise RuntimeError(f"precision='{mode}' is a forward-only embedding path; call model.eval() first or use precision='bf16'")
-        if torch.is_grad_enabled():
-            raise RuntimeError(f"precision='{mode}' is the embedder's forward-only path; run it under torch.no_grad() or switch "
-                               "back to precision='bf16' for training")
-        return mode
+        return embed_mode(self, fp16_refuses_grad=True)
 
     def encode_multimodal_input(self, txt_tensor, img_tensor, txt_mask=None, img_mask=None):
         mode = self._embed_mode()
