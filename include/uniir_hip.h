@@ -761,6 +761,21 @@ int uniir_topk_ip_multi(const void* pool_f16, const float* pool_inv_norm, const 
  * small inputs, and for tuning.  Process-wide host setting.  uniir_topk_ip_sweep_queries: the value a search of this shape uses. */
 int uniir_topk_set_chunk(int32_t queries_per_sweep);
 int32_t uniir_topk_ip_sweep_queries(int32_t dim, int64_t rows);
+/* The same search over an fp32 pool (an extraction with use_fp16 = False kept as fp32 rows: UNIIR_POOL_FP32).  New entry points only,
+ * found by their symbols.  The arithmetic is that of uniir_topk_ip with fp32 inputs where it converts fp16 to fp32: inverse norms
+ * (float)(1.0 / (double)sqrtf(s)), s the sequential fp32 sum of squares without fma, 0 when s is not > 0; query and row elements
+ * scaled by them and rounded to fp32; score s = s + qn[j] * xn[j] sequentially without fma; order (score desc, id asc), missing
+ * results (-inf, -1).  Bit for bit for finite inputs in the normal range.
+ *   uniir_pool_inv_norms_f32: dim % 4 == 0, x 16-byte aligned.
+ *   uniir_topk_ip_f32: k <= 56, dim % 64 == 0, rows * dim * 4 < 2 GiB (UNIIR_ESHAPE otherwise, before anything is launched; a larger
+ *     shard is searched as the row ranges of retrieval.subshard_bounds(n, dim, 4) and merged with uniir_topk_merge); pool, queries
+ *     and inverse norms 16-byte, workspace 256-byte aligned (UNIIR_EALIGN); workspace of uniir_topk_ip_f32_workspace_bytes (0 for
+ *     nq == 0 or k == 0).  Sweeps of <= 1024 queries, or of uniir_topk_set_chunk's value. */
+int uniir_pool_inv_norms_f32(const float* x, int64_t n, int32_t dim, float* inv_norm, void* stream);
+int64_t uniir_topk_ip_f32_workspace_bytes(int32_t nq, int32_t k, int64_t rows, int32_t dim);
+int uniir_topk_ip_f32(const float* pool_f32, const float* pool_inv_norm, const int64_t* pool_ids, int64_t rows, int32_t dim,
+                      const float* queries_f32, int32_t nq, int32_t k, float* out_scores, int64_t* out_ids, void* workspace,
+                      int64_t workspace_bytes, void* stream);
 /* k-way merge of per-shard results (score desc, id asc): in [nshard][nq][k] -> out [nq][k] */
 int uniir_topk_merge(const float* scores, const int64_t* ids, int32_t nshard, int32_t nq, int32_t k,
                      float* out_scores, int64_t* out_ids, void* stream);

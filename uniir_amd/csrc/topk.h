@@ -45,3 +45,9 @@ bool launch_fused_tail(const void* pool_f16, const float* pinv, const int64_t* p
                        const void* queries_f16, int32_t nq, int32_t kc, int32_t k, const float* gmax, int32_t* cand,
                        float* exact, float* out_scores, int64_t* out_ids, hipStream_t st, const float* wmax, int nw,
                        const TkMulti* mu = nullptr, int nsub = 1);
+// topk_f32.hip (the fp32 twin of the one-call search) shares two host-side pieces with the fp16 search: the explicit sweep width of
+// uniir_topk_set_chunk (0 = automatic) and the type-free sort behind an exact re-score (topk_tail_sort_kernel: exact / cand
+// [nq][ncand <= 2048] -> the k best by (score desc, id asc), FAISS padding)
+int tk_sweep_override();
+void launch_tail_sort(const float* exact, const int32_t* cand, const int64_t* pool_ids, int32_t nq, int32_t ncand, int32_t k,
+                      float* out_scores, int64_t* out_ids, hipStream_t st);

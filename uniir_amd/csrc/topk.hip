@@ -1300,6 +1300,7 @@ extern "C" int uniir_topk_set_chunk(int32_t queries_per_sweep) {
     g_tki_chunk = queries_per_sweep;
     return UNIIR_OK;
 }
+int tk_sweep_override() { return g_tki_chunk; }
 extern "C" int32_t uniir_topk_ip_sweep_queries(int32_t dim, int64_t rows) {
     if (g_tki_chunk) return g_tki_chunk;
     return stream_shared_ok(dim, rows, 256) ? 256 : TKI_CHUNK_MAX;

@@ -27,6 +27,26 @@ static inline __host__ __device__ float tk_slack_cos(int dim) {
     const float s = 1.78f * bound;
     return s > TK_SLACK_COS ? s : TK_SLACK_COS;
 }
+// The same rule over fp32 rows (topk_f32.hip).  u = 2^-24.  Both scores are compared with the real number
+//   T = (sum_j q_j x_j) * ic * iq,   ic, iq = the COMPUTED fp32 inverse norms of the row and the query
+// (the rule needs |approx - exact| only, so the error of the inverse norms themselves, common to both, drops out).
+//   scan   : v_mfma_f32_16x16x4_f32 on the operands as stored: the products are exact inside the fma, the dim accumulation steps
+//            round to fp32 (in whatever order -- the kernel permutes k within 16-column steps), then one multiplication by ic:
+//            |approx - T / iq| <= (dim + 1) u' sum_j |q_j x_j| ic <= (dim + 1) u' |q| |x| ic, u' = u / (1 - (dim + 1) u).  |x| ic is
+//            1 up to the error of ic, ((dim + 1) / 2 + 2) u < 2e-4 of it for dim <= 4096, so in the scan's units (scores x |q|,
+//            the query un-normalised)                     d_a = (dim + 1) x 1.001 x 2^-24 of |q|.
+//            No range condition: fp32 operands of any normal magnitude multiply and add without overflow as long as the dot
+//            product itself is finite, so rows scaled by 1e-4 or 3e4 obey the same bound (an fp16 scan would overflow on them).
+//   rescore: qn_j = fl(q_j iq), xn_j = fl(x_j ic), fl(qn_j xn_j), dim - 1 additions: (dim + 2) roundings on every term,
+//            sum_j |qn_j xn_j| <= |qn| |xn| <= 1.001:    d_e = (dim + 2) x 1.001 x 2^-24 in cosine units.
+// As above, a row of the exact top k has a group maximum of at least tau_k - 2 (d_a + d_e) = tau_k - 2 (2 dim + 3) 1.001 u: 1.84e-4
+// at dim 768 (the fp16 search: 2.81e-4).  The slack keeps the 1.78 x margin and the 5e-4 floor of tk_slack_cos (the margin
+// passes the floor above dim 1177).
+static inline __host__ __device__ float tk_slack_cos_f32(int dim) {
+    const float bound = 2.f * (float)(2 * dim + 3) * 1.001f * 5.9604645e-8f;
+    const float s = 1.78f * bound;
+    return s > TK_SLACK_COS ? s : TK_SLACK_COS;
+}
 struct GselBound {
     int k;              // entries wanted
     float slack_cos;    // tk_slack_cos(dim)

@@ -642,6 +642,12 @@ __global__ __launch_bounds__(1024) void topk_tail_sort_kernel(const float* __res
     }
 }
 
+void launch_tail_sort(const float* exact, const int32_t* cand, const int64_t* pool_ids, int32_t nq, int32_t ncand, int32_t k,
+                      float* out_scores, int64_t* out_ids, hipStream_t st) {
+    const TkMulti one = {};
+    hipLaunchKernelGGL(topk_tail_sort_kernel, dim3(nq, 1), dim3(1024), 0, st, exact, cand, (const long long*)pool_ids, ncand, k,
+                       out_scores, (long long*)out_ids, one);
+}
 // can the fused tail (selection + query norm + exact re-score | sort) serve this search?
 bool fused_tail_ok(int64_t rows, int32_t dim, int32_t kc) {
     const long ngroups = (rows + TK_G - 1) / TK_G;

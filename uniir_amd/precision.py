@@ -13,6 +13,11 @@ BLIPScoreFusion, CLIPFeatureFusion).  Three plain attributes, which a constructo
               at construction.  On BLIP and CLIP_FF it is also what makes "fp32" a precision the module knows: without it "fp32" raises
               `unknown precision`, so a model that has not opted in behaves in every respect as it did before the fp32 forward existed.
 
+pool_fp32() is the storage switch that goes with embed_fp32: UNIIR_POOL_FP32=1, read when used.  With it an extraction under
+use_fp16: False keeps its fp32 rows (the .npy, the .index container, the resident shards) and the search runs on them
+(uniir_topk_ip_f32: the oracle's arithmetic over fp32 rows); without it, or under use_fp16: True, every row is rounded to fp16 as
+before and every file keeps its bytes.
+
 embed_mode() is the rule of an encode call of BLIP and CLIP_FF.  clip_model._TowerFn keeps its own three lines: the C towers ask
 whether THIS call records a backward (needs_input_grad), not for grad mode, know no train-mode guard and no opt-in, so routing them
 through embed_mode() would take a flag per guard."""
@@ -26,6 +31,11 @@ PRECISIONS = ("bf16", "fp16", "fp32")
 def env_flag(name):
     """an opt-in switch of the environment: set, and neither empty nor "0" """
     return os.environ.get(name, "0") not in ("", "0")
+
+
+def pool_fp32():
+    """keep (and search) fp32 embedding rows where use_fp16 is False: UNIIR_POOL_FP32=1, read at every use"""
+    return env_flag("UNIIR_POOL_FP32")
 
 
 def check_mode(mode, known, training, hint=""):

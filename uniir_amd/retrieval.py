@@ -3,6 +3,8 @@
 Mirrors what UniIR's src/common/mbeir_retriever.py does with faiss (create_index :69-103: fp16 -> fp32,
 normalize_L2, add_with_ids; search_index :188-232: normalize queries, exact top-k) but keeps the pool in its
 stored fp16 form resident in HBM: a pool shard is (fp16 [n,d] rows, fp32 inverse norms, int64 ids).
+A shard may also hold fp32 rows (an extraction with use_fp16: False kept as fp32, precision.pool_fp32): the same search in the
+same arithmetic over 4-byte rows (uniir_topk_ip_f32), at about the fp32 MFMA's cost (profiles/topk_fp32.txt).
 """
 import torch
 
@@ -15,7 +17,8 @@ class PoolShard:
     """One GPU's slice of the candidate pool, resident in HBM."""
 
     def __init__(self, embeddings_f16: torch.Tensor, ids: torch.Tensor):
-        if embeddings_f16.dtype != torch.float16 or not embeddings_f16.is_cuda:
+        # fp16 rows, or fp32 rows (kept as they are: emb.dtype tells the searches which entry points to call)
+        if embeddings_f16.dtype not in (torch.float16, torch.float32) or not embeddings_f16.is_cuda:
             raise RuntimeError("PoolShard needs a CUDA fp16 [n, d] tensor")
         self.emb = embeddings_f16.contiguous()
         self.ids = ids.to(device=self.emb.device, dtype=torch.int64).contiguous()
@@ -24,7 +27,8 @@ class PoolShard:
             raise RuntimeError("embedding dim must be a multiple of 64")
         self.inv_norm = torch.empty(max(self.n, 1), device=self.emb.device, dtype=torch.float32)
         if self.n:
-            ops.call("uniir_pool_inv_norms", self.emb, self.n, self.dim, self.inv_norm)
+            ops.call("uniir_pool_inv_norms" if self.emb.dtype == torch.float16 else "uniir_pool_inv_norms_f32", self.emb, self.n,
+                     self.dim, self.inv_norm)
 
 
 def query_inv_norms(queries_f16: torch.Tensor) -> torch.Tensor:
@@ -57,17 +61,18 @@ FUSED_TAIL_ROWS = 1024 * 2 * 24 * 16     # csrc/topk_select.h: the register-resi
                                          # TK_SELREG group maxima = 49 152 groups of 16 rows = 786 432 rows
 
 
-def subshard_bounds(n, dim):
+def subshard_bounds(n, dim, itemsize=2):
     """Row ranges of the LOGICAL sub-shards a resident shard is searched in: one range while n * dim * 2 < 2 GiB, else equal ranges
     (on 32-row boundaries: aligned inverse norms, an even number of whole scan groups) that each stay below it AND within the fused
     tail's 786 432 rows.  Round 5: the ranges used to be as large as the 2-GiB bound allows (1.12 M rows at dim 768), which put every
     sub-shard search on the unfused tail (separate selection + re-score launches, strided passes over the group maxima) -- the
     16-19 % per-row penalty of the 256-query sweeps on the 5.6 M pool (12.3 ms for 1024 queries against 8 x 1.29).  The 5.6 M x 768
     M-BEIR pool on ONE GPU (8.6 GB, mbeir_retriever.py:196-206 with a single visible device) is 8 ranges of 700 000 rows -- the shards
-    of the 8-GPU layout."""
-    if n * dim * 2 < SUBSHARD_BYTES:
+    of the 8-GPU layout.  itemsize: bytes per element of the rows (2: fp16, the default; 4: an fp32 shard -- the same rule with
+    dim * 4 bytes per row: 699 050 rows of dim 768 are one range, 5.6 M are 9)."""
+    if n * dim * itemsize < SUBSHARD_BYTES:
         return [(0, n)]
-    max_rows = min(((SUBSHARD_BYTES - 1) // (dim * 2)) // 32 * 32, FUSED_TAIL_ROWS)
+    max_rows = min(((SUBSHARD_BYTES - 1) // (dim * itemsize)) // 32 * 32, FUSED_TAIL_ROWS)
     parts = -(-n // max_rows)
     per = -(-(-(-n // parts)) // 32) * 32
     return [(lo, min(lo + per, n)) for lo in range(0, n, per)]
@@ -105,8 +110,12 @@ def search_shard(shard: PoolShard, queries_f16: torch.Tensor, k: int, q_inv=None
     a shard of >= 2 GiB goes to uniir_topk_ip_multi, which searches it as the equal sub-shards of subshard_bounds and merges on
     (score desc, id asc) -- the search of the whole shard (ids are unique).
     k > 56 (FAISS Flat accepts up to 2048; Recall@100, larger hard-negative mining depths): assembled from row slices of the
-    shard, see _search_large_k."""
+    shard, see _search_large_k.
+    An fp32 shard takes fp16 or fp32 queries (cast up: exact) and goes to uniir_topk_ip_f32; >= 2 GiB of fp32 rows are searched as
+    the ranges of subshard_bounds(n, dim, 4) in a host loop and merged."""
     from . import _lib
+    if shard.emb.dtype == torch.float32:
+        return _search_shard_f32(shard, queries_f16, k)
     queries_f16 = queries_f16.contiguous()
     nq = queries_f16.shape[0]
     dev = queries_f16.device
@@ -126,6 +135,29 @@ def search_shard(shard: PoolShard, queries_f16: torch.Tensor, k: int, q_inv=None
         workspace = _workspace(dev, need)
     ops.call("uniir_topk_ip_multi" if multi else "uniir_topk_ip", shard.emb, shard.inv_norm, shard.ids, shard.n, shard.dim,
              queries_f16, nq, k, out_s, out_i, workspace, workspace.numel())
+    return out_s, out_i
+
+
+def _search_shard_f32(shard, queries, k):
+    """search_shard over fp32 rows"""
+    from . import _lib
+    if queries.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError("an fp32 shard is searched with fp16 or fp32 queries")
+    queries = queries.float().contiguous()
+    nq, dev = queries.shape[0], queries.device
+    if nq == 0 or shard.n == 0:
+        return (torch.full((nq, k), float("-inf"), device=dev, dtype=torch.float32),
+                torch.full((nq, k), -1, device=dev, dtype=torch.int64))
+    if k > MAX_K_DIRECT:
+        return _search_large_k(shard, queries, k)
+    if shard.n * shard.dim * 4 >= SUBSHARD_BYTES:
+        res = [_search_shard_f32(_shard_view(shard, lo, hi), queries, k) for lo, hi in subshard_bounds(shard.n, shard.dim, 4)]
+        return merge_shards(torch.stack([r[0] for r in res]), torch.stack([r[1] for r in res]))
+    out_s = torch.empty(nq, k, device=dev, dtype=torch.float32)
+    out_i = torch.empty(nq, k, device=dev, dtype=torch.int64)
+    workspace = _workspace(dev, _lib.load().uniir_topk_ip_f32_workspace_bytes(nq, k, shard.n, shard.dim))
+    ops.call("uniir_topk_ip_f32", shard.emb, shard.inv_norm, shard.ids, shard.n, shard.dim, queries, nq, k, out_s, out_i, workspace,
+             workspace.numel())
     return out_s, out_i
 
 
@@ -177,9 +209,12 @@ def merge_shards(scores, ids):
 # (src/common/mbeir_embedder.py:63-116, mbeir_retriever.py:69-117,197-206).  Here each rank keeps the fp16 rows it
 # encoded (its ContiguousDistributedSampler slice) in HBM as its pool shard; queries travel, the pool never does.
 # ------------------------------------------------------------------------------------------------------------
-def embed_resident(model, data_loader, device):
+def embed_resident(model, data_loader, device, dtype=torch.float16):
     """the embedder loop of mbeir_embedder.generate_embeds_and_ids_for_dataset_with_gather without the gather:
-    -> (fp16 [n, d] on `device`, hashed ids int64 [n] on `device`) of this rank's slice"""
+    -> (fp16 [n, d] on `device`, hashed ids int64 [n] on `device`) of this rank's slice.  dtype=torch.float32 keeps the model's
+    fp32 rows (a model on its fp32 embedding forward) for an fp32 PoolShard."""
+    if dtype not in (torch.float16, torch.float32):
+        raise RuntimeError("embed_resident keeps fp16 or fp32 rows")
     chunks, ids = [], []
     with torch.no_grad():
         for batch in data_loader:
@@ -192,9 +227,9 @@ def embed_resident(model, data_loader, device):
                     for kk, vv in v.items():
                         v[kk] = vv.to(device)
             emb, batch_ids = model(batch, encode_mbeir_batch=True)
-            chunks.append(emb.half())          # the reference stores fp16 too (use_fp16=True)
+            chunks.append(emb.to(dtype))       # the reference stores fp16 too (use_fp16=True)
             ids.extend(int(i) for i in batch_ids)
-    emb = torch.cat(chunks, dim=0) if chunks else torch.zeros(0, 64, dtype=torch.float16, device=device)
+    emb = torch.cat(chunks, dim=0) if chunks else torch.zeros(0, 64, dtype=dtype, device=device)
     return emb.contiguous(), torch.tensor(ids, dtype=torch.int64, device=device)
 
 

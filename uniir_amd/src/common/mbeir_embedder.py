@@ -68,7 +68,14 @@ def _tower_precision(model, use_fp16):
 @torch.no_grad()
 def generate_embeds_and_ids_for_dataset_with_gather(model, data_loader, device, use_fp16=True):
     with _tower_precision(model, use_fp16):
-        return _generate(model, data_loader, device)
+        return _generate(model, data_loader, device, _store_dtype(use_fp16))
+
+
+def _store_dtype(use_fp16):
+    """the dtype an extraction keeps: fp16 like the reference's .half() per batch, or -- UNIIR_POOL_FP32=1 and use_fp16: False --
+    the model's fp32 rows (uniir_amd/precision.py pool_fp32; the reference's retriever reads either .npy with astype("float32"))"""
+    from uniir_amd import precision
+    return torch.float32 if (not use_fp16 and precision.pool_fp32()) else torch.float16
 
 
 @torch.no_grad()
@@ -77,15 +84,16 @@ def generate_embeds_and_ids_on_device(model, data_loader, device, use_fp16=True)
     gets it: -> (fp16 [n, d] on `device`, hashed ids in rank order).  The rank shards are all-gathered instead of being
     gathered to rank 0 (the UniRAG complement queries are searched by every rank, interactive_retriever.py)."""
     from uniir_amd import comm
+    store = _store_dtype(use_fp16)
     with _tower_precision(model, use_fp16):
-        chunks, id_list = _embed_local(model, data_loader, device)
+        chunks, id_list = _embed_local(model, data_loader, device, store)
     dim = chunks[0].shape[1] if chunks else 0
     if comm.world() > 1:                   # ranks without queries learn the width from the others
         gloo = dist.get_backend() == "gloo"
         dims = torch.zeros(comm.world(), dtype=torch.int64, device="cpu" if gloo else device)
         dist.all_gather_into_tensor(dims, torch.tensor([dim], dtype=torch.int64, device=dims.device))
         dim = int(dims.max())
-    local = torch.cat(chunks, dim=0) if chunks else torch.zeros(0, max(dim, 1), dtype=torch.float16, device=device)
+    local = torch.cat(chunks, dim=0) if chunks else torch.zeros(0, max(dim, 1), dtype=store, device=device)
     emb, _ = comm.all_gather_varlen(local)
     if comm.world() > 1:
         ids = [None] * comm.world()
@@ -95,8 +103,9 @@ def generate_embeds_and_ids_on_device(model, data_loader, device, use_fp16=True)
     return emb.contiguous(), id_list
 
 
-def _embed_local(model, data_loader, device):
-    """this rank's forward passes: fp16 chunks on the device and the hashed ids, in loader order"""
+def _embed_local(model, data_loader, device, store=torch.float16):
+    """this rank's forward passes: chunks of dtype `store` (fp16 unless _store_dtype says fp32) on the device and the hashed ids, in
+    loader order"""
     chunks, id_list = [], []
     for batch in data_loader:
         for k, v in batch.items():
@@ -108,17 +117,18 @@ def _embed_local(model, data_loader, device):
                 for kk, vv in v.items():
                     v[kk] = vv.to(device)
         emb, ids = model(batch, encode_mbeir_batch=True)
-        chunks.append(emb.half())          # fp16 on disk, like the reference
+        chunks.append(emb.half() if store == torch.float16 else emb.float())          # fp16 on disk, like the reference
         id_list.extend(ids)
     return chunks, id_list
 
 
-def _generate(model, data_loader, device):
-    chunks, id_list = _embed_local(model, data_loader, device)
+def _generate(model, data_loader, device, store=torch.float16):
+    np_store = np.float16 if store == torch.float16 else np.float32
+    chunks, id_list = _embed_local(model, data_loader, device, store)
     dim = chunks[0].shape[1] if chunks else None
     if not dist.is_initialized():
         if not chunks:
-            return np.zeros((0, 0), dtype=np.float16), id_list
+            return np.zeros((0, 0), dtype=np_store), id_list
         return torch.cat(chunks, dim=0).cpu().numpy(), id_list
     world, rank = dist.get_world_size(), dist.get_rank()
     # exchange sizes and the embedding width first (some ranks may hold nothing)
@@ -127,8 +137,8 @@ def _generate(model, data_loader, device):
     dist.all_gather(metas, meta)
     sizes = [int(m[0]) for m in metas]
     dim = max(int(m[1]) for m in metas)
-    local = torch.cat(chunks, dim=0) if chunks else torch.zeros(0, dim, dtype=torch.float16, device=device)
-    padded = torch.zeros(max(max(sizes), 1), dim, dtype=torch.float16, device=device)
+    local = torch.cat(chunks, dim=0) if chunks else torch.zeros(0, dim, dtype=store, device=device)
+    padded = torch.zeros(max(max(sizes), 1), dim, dtype=store, device=device)
     padded[: local.shape[0]] = local
     gathered = [torch.empty_like(padded) for _ in range(world)] if rank == 0 else None
     ids_gathered = [None] * world if rank == 0 else None

@@ -59,8 +59,12 @@ def create_index(config):
             "The dimension of the index does not match the dimension of the embeddings!"
         index_path = os.path.join(config.uniir_dir, index_config.index_dir_name, expt, split, f"mbeir_{name}_{split}.index")
         os.makedirs(os.path.dirname(index_path), exist_ok=True)
-        with open(index_path, "wb") as f:   # stored un-normalised fp16 (exact); normalisation happens on the device
-            np.savez(f, emb=emb.astype(np.float16), ids=ids)
+        # stored un-normalised fp16 (exact); normalisation happens on the device.  UNIIR_POOL_FP32=1: an fp32 .npy (an extraction
+        # with use_fp16: False under the same switch) stays fp32 in the container and is searched as fp32 rows
+        from uniir_amd import precision
+        keep = np.float32 if (precision.pool_fp32() and emb.dtype == np.float32) else np.float16
+        with open(index_path, "wb") as f:
+            np.savez(f, emb=emb.astype(keep), ids=ids)
         print(f"Successfully indexed {len(ids)} documents\nIndex saved to: {index_path}")
         del emb, ids
         gc.collect()
@@ -74,7 +78,8 @@ def compute_recall_at_k(relevant_docs, retrieved_indices, k):
 
 
 def _device_shards(cand_index_path):
-    """row-shard the pool over the visible GPUs (FAISS shard=True semantics); cached per (path, mtime).  Under
+    """row-shard the pool over the visible GPUs (FAISS shard=True semantics) in the container's dtype (fp16, or the fp32 rows
+    create_index kept under UNIIR_POOL_FP32); cached per (path, mtime).  Under
     torch.distributed every rank holds the whole pool on its own device (the other devices belong to the other ranks)."""
     from uniir_amd import comm, retrieval
     key = (cand_index_path, os.path.getmtime(cand_index_path))
@@ -108,6 +113,8 @@ def search_index_with_batch(query_embeddings_batch, shards, num_cand_to_retrieve
         dev = sh.emb.device
         with torch.cuda.device(dev):
             q = torch.as_tensor(query_embeddings_batch).to(dev)      # host fp16 rows or a device tensor
+            if sh.emb.dtype == torch.float16 and q.dtype != torch.float16:
+                q = q.half()               # fp32 rows (an extraction under UNIIR_POOL_FP32) into an fp16 index: stored precision
             outs.append(retrieval.search_shard(sh, q, num_cand_to_retrieve))
     dev0 = shards[0].emb.device
     with torch.cuda.device(dev0):
@@ -118,7 +125,8 @@ def search_index_with_batch(query_embeddings_batch, shards, num_cand_to_retrieve
 
 
 def search_embeddings(queries, cand_index_path, batch_size=10, num_cand_to_retrieve=10):
-    """exact top-k of fp16 query rows (host array or device tensor) over the cached shards of an index file ->
+    """exact top-k of fp16 query rows (host array or device tensor; fp32 rows too when the index holds fp32 rows) over the cached
+    shards of an index file ->
     (scores f32 [n, k], hashed dids int64 [n, k]) as numpy, on every rank.  Under torch.distributed rank r searches the
     contiguous slice r of the queries and the slices are all-gathered; a query's result does not depend on its batch."""
     from uniir_amd import comm
@@ -138,7 +146,11 @@ def search_embeddings(queries, cand_index_path, batch_size=10, num_cand_to_retri
 
 
 def search_index(query_embed_path, cand_index_path, batch_size=10, num_cand_to_retrieve=10):
-    queries = np.load(query_embed_path).astype(np.float16)   # stored fp16; normalised on the device in fp32
+    queries = np.load(query_embed_path)
+    # stored fp16; normalised on the device in fp32.  An fp32 index takes fp32 query rows as they are (fp16 rows are cast up on the
+    # device, which is exact); an fp16 index takes fp16 rows, as it always did
+    if not (queries.dtype == np.float32 and _device_shards(cand_index_path)[0].emb.dtype == torch.float32):
+        queries = queries.astype(np.float16)
     print(f"Retriever: loaded query embeddings from {query_embed_path} with shape: {queries.shape}")
     return search_embeddings(queries, cand_index_path, batch_size, num_cand_to_retrieve)
 
