@@ -39,7 +39,8 @@ const char* uniir_strerror(int code);
  * _rel_bwd_long; uniir_attention_one_fwd / _one_bwd, and the value 2 of uniir_clip_tower.pool_last_block; uniir_layernorm_fwd_f16,
  * uniir_patchify_f16, uniir_vit_assemble_f16: no layout changes; 7: uniir_attn_rel_fwd_f16, uniir_attn_rel_fwd_long_f16 and
  * uniir_rmsnorm_fwd_f16 -- new entry points only, a caller that needs them asks for >= 7; still 7, a new entry point only:
- * uniir_attn_f32_rel_fwd, which a caller finds by its symbol). */
+ * uniir_attn_f32_rel_fwd, which a caller finds by its symbol; still 7, new entry points and a new struct of their own only:
+ * uniir_grad_guard*, uniir_adamw_step_guarded and uniir_grad_ctl, found by their symbols). */
 int uniir_abi_version(void);
 /* Reproducible reductions (round 6).  Bias, LayerNorm-weight and token-embedding gradients are sums over every row of a batch taken by
  * many workgroups; added with fp32 atomics they depend on the arrival order, and two runs of one training step differ in their last
@@ -588,6 +589,51 @@ int uniir_attention_f32_fwd(const float* q, int64_t q_ld, const float* k, const 
 int uniir_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                      void* param_bf16, int64_t count, float lr, float beta1, float beta2, float eps,
                      float weight_decay, int32_t step, float grad_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * [OPT] gradient guard: the part of the reference's scaler.step(optimizer) that is not the loss scale (uniir_clip/engine.py:34-42,
+ * uniir_blip/engine.py:44-52: a step whose gradients hold Inf or NaN is not applied), plus torch's clip_grad_norm_, decided on the
+ * device.  uniir_grad_guard reads the AdamW ranges of one step (host arrays of device pointers and counts) and fills a control
+ * block; uniir_adamw_step_guarded is uniir_adamw_step behind that block.  Nothing here reads device memory on the host.
+ *   x = fl32(g * grad_scale) per element (what AdamW consumes); sumsq = sum of the exact fp64 squares of the finite x, in one fixed
+ *   order: chunks of uniir_grad_guard_chunk() elements per range (a compile-time constant, independent of grid, chip and stream),
+ *   one workgroup and one fp64 partial per chunk, the partials of all ranges added in index order by a fixed tree.  No atomics:
+ *   same input, same bits.  Any order of n exact non-negative terms is within n * 2^-53 * sumsq of the exact sum.
+ *   norm = fl32(sqrt(sumsq)) (the f64 root); nonfinite = a non-finite x anywhere, or norm == Inf; skip = nonfinite && skip_nonfinite;
+ *   coef = 0 when skip; else min(1, max_norm / (norm + 1e-6)) in fp32 when max_norm > 0 and !nonfinite (clip_grad_norm_); else 1.
+ *   first_bad_range / first_bad_chunk / first_bad_index: the lowest (range, element) that was non-finite -- its range, its chunk in
+ *   the range and its element offset in the range; -1 without one.  steps_seen += 1 and steps_skipped += skip on the device: the
+ *   caller zeroes (or restores) the block once and never writes it again.
+ * uniir_grad_guard: one launch per non-empty range plus the finish; max_norm <= 0: no clipping; no ranges or all counts 0: norm 0,
+ * coef 1, skip 0.  UNIIR_EINVAL: a NULL operand (grads[r] may be NULL where counts[r] == 0; workspace may be NULL where it needs no
+ * bytes), a negative count or one of 2^40 and more, more than 2^20 ranges, a NaN or negative grad_scale, a NaN max_norm, a workspace
+ * below uniir_grad_guard_workspace_bytes (which returns -1 for counts it refuses); UNIIR_EALIGN: a range pointer or the control block
+ * not 16-byte aligned, a workspace not 256-byte aligned.  All of it before anything is launched: a refused call writes nothing.
+ * uniir_adamw_step_guarded: skip != 0 -- no thread touches param, the moments or the shadow; otherwise g' = fl32(fl32(g * grad_scale)
+ * * coef), so coef == 1 gives uniir_adamw_step's bits.  `step` is the caller's count of APPLIED steps (+1): a caller that learns of
+ * a skip takes its count back by one, as torch does when scaler.step() leaves optimizer.step() out.  Errors as uniir_adamw_step,
+ * plus a NULL (UNIIR_EINVAL) or misaligned (UNIIR_EALIGN) control block.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct uniir_grad_ctl {      /* 64 bytes, 16-byte aligned, device memory */
+    double sumsq;
+    float norm;
+    float coef;
+    int32_t nonfinite;
+    int32_t skip;
+    int32_t first_bad_range;
+    int32_t first_bad_chunk;
+    int64_t first_bad_index;
+    int64_t steps_seen;
+    int64_t steps_skipped;
+    int64_t reserved;
+} uniir_grad_ctl;
+int64_t uniir_grad_guard_chunk(void);
+int64_t uniir_grad_guard_workspace_bytes(const int64_t* counts, int32_t nranges);
+int uniir_grad_guard(const float* const* grads, const int64_t* counts, int32_t nranges, float grad_scale, float max_norm,
+                     int32_t skip_nonfinite, uniir_grad_ctl* ctl_dev, void* workspace, int64_t workspace_bytes, void* stream);
+int uniir_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* param_bf16,
+                             int64_t count, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+                             float grad_scale, const uniir_grad_ctl* ctl_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * [BLIP] extra pieces of the BLIP_FF path (src/models/uniir_blip): tanh pooler (backbone/med.py:499-511), momentum

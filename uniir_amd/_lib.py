@@ -86,6 +86,13 @@ class ImageAugInfo(C.Structure):
                 ("launches_preprocess", c_int), ("reserved", c_int)]
 
 
+class GradCtl(C.Structure):
+    """uniir_grad_ctl (include/uniir_hip.h [OPT]): the gradient guard's device control block, 64 bytes"""
+    _fields_ = [("sumsq", C.c_double), ("norm", c_float), ("coef", c_float), ("nonfinite", c_int), ("skip", c_int),
+                ("first_bad_range", c_int), ("first_bad_chunk", c_int), ("first_bad_index", c_i64),
+                ("steps_seen", c_i64), ("steps_skipped", c_i64), ("reserved", c_i64)]
+
+
 # name -> (restype, argtypes); P = device pointer, S = stream
 P, S = c_void_p, c_void_p
 SIGNATURES = {
@@ -160,6 +167,11 @@ SIGNATURES = {
     "uniir_sgemm": (c_int, [P, c_i64, c_i64, P, c_i64, c_i64, P, c_i64, c_int, c_int, c_int, c_float, S]),
     "uniir_adamw_step": (c_int, [P, P, P, P, P, c_i64, c_float, c_float, c_float, c_float, c_float, c_int,
                                  c_float, S]),
+    "uniir_grad_guard_chunk": (c_i64, []),
+    "uniir_grad_guard_workspace_bytes": (c_i64, [C.POINTER(c_i64), c_int]),
+    "uniir_grad_guard": (c_int, [C.POINTER(c_void_p), C.POINTER(c_i64), c_int, c_float, c_float, c_int, P, P, c_i64, S]),
+    "uniir_adamw_step_guarded": (c_int, [P, P, P, P, P, c_i64, c_float, c_float, c_float, c_float, c_float, c_int,
+                                         c_float, P, S]),
     "uniir_rmsnorm_fwd": (c_int, [P, c_i64, P, P, P, c_int, c_int, c_float, S]),
     "uniir_rmsnorm_bwd": (c_int, [P, c_i64, P, P, c_int, P, P, c_i64, P, P, c_int, c_int, c_float, S]),
     "uniir_attention_rel_fwd": (c_int, [P, P, P, P, P, c_int, c_float, c_int, c_int, c_int, c_float, C.c_uint32, S]),

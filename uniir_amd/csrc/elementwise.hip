@@ -1110,6 +1110,250 @@ extern "C" int uniir_adamw_step(float* param, const float* grad, float* exp_avg,
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Gradient guard (uniir_hip.h [OPT]): the global norm of the scaled gradient in one fixed summation order, a non-finite scan, and the
+// clip / skip decision in a device control block that adamw_guarded_kernel reads.  The reference's scaler.step(optimizer) does not
+// apply a step whose gradients hold Inf or NaN (uniir_clip/engine.py:34-42); this is that half of it, with clip_grad_norm_ on top.
+//
+// Summation order.  A range is cut into chunks of GUARD_CHUNK elements, one workgroup per chunk, whatever the grid or the chip.
+// Thread t of the chunk takes the 16-byte groups t, t + 256, t + 512, ... in that order, component e of every group into its
+// accumulator e (fp64: x * x of an fp32 x is exact in 53 bits, so each fma rounds once, like an add of the exact term); thread r < 3
+// then takes tail element r of a range whose count is no multiple of 4.  (a0 + a1) + (a2 + a3), the xor-shuffle tree 32, 16, .. 1
+// over the wave, the four waves in wave order through LDS: one fp64 partial per chunk.  guard_finish_kernel adds the partials of
+// every range in index order the same way.  No atomics: same input, same bits, on any stream.
+#define GUARD_CHUNK 65536
+#define GUARD_VEC (GUARD_CHUNK / 4 / 256)          // 16-byte groups per thread of a full chunk
+static_assert(GUARD_CHUNK % 1024 == 0, "a chunk is whole 16-byte groups for every thread");
+#define GUARD_NONE 0x7fffffffffffffffLL            // the key of a chunk that saw only finite values
+
+DEVINL double guard_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+DEVINL long guard_wave_min(long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const long w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    return v;
+}
+DEVINL bool guard_bad(float x) { return !(__builtin_fabsf(x) <= 3.402823466e+38f); }          // Inf or NaN
+
+// one 16-byte group at group index `q` of the chunk: scale, scan, accumulate
+DEVINL void guard_take4(f32x4_t gg, float gscale, unsigned q, double (&acc)[4], unsigned& bad) {
+    float x[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = __fmul_rn(gg[e], gscale);
+    if (guard_bad(x[0]) | guard_bad(x[1]) | guard_bad(x[2]) | guard_bad(x[3])) {          // rare: a non-finite x adds nothing
+#pragma unroll
+        for (int e = 3; e >= 0; --e)
+            if (guard_bad(x[e])) {
+                x[e] = 0.0f;
+                bad = min(bad, 4u * q + (unsigned)e);
+            }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = __builtin_fma((double)x[e], (double)x[e], acc[e]);
+}
+
+// grid = chunks of the range.  part[chunk] = sum of squares; key[chunk] = (range << 40 | offset of the first non-finite element in
+// the range), GUARD_NONE without one.
+__global__ __launch_bounds__(256) void guard_sumsq_kernel(const float* __restrict__ g, long n, float gscale, long range,
+                                                         double* __restrict__ part, long* __restrict__ key) {
+    __shared__ double s_sum[4];
+    __shared__ long s_key[4];
+    const long base = (long)blockIdx.x * GUARD_CHUNK;
+    const long rest = n - base;                                 // >= 1 elements of the range from this chunk on
+    const f32x4_t* __restrict__ g4 = reinterpret_cast<const f32x4_t*>(g + base);
+    const unsigned t = threadIdx.x;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    unsigned bad = 0xffffffffu;                                 // offset in the chunk of this thread's first non-finite element
+    if (rest >= GUARD_CHUNK) {
+#pragma unroll 8
+        for (int k = 0; k < GUARD_VEC; ++k) guard_take4(g4[t + 256u * k], gscale, t + 256u * k, acc, bad);
+    } else {
+        // the length is taken from `rest` inside this branch only: a min(GUARD_CHUNK, rest) shared with the test above compiled to a
+        // scalar select on a condition code that the 64-bit vector compare never set, and the partial chunk read a full one
+        const unsigned len = (unsigned)rest;
+        const unsigned nv = len >> 2;
+        for (unsigned q = t; q < nv; q += 256u) guard_take4(g4[q], gscale, q, acc, bad);
+        if (t < (unsigned)(len & 3)) {                          // the last 1..3 elements of the range
+            const unsigned o = 4u * nv + t;
+            float x = __fmul_rn(g[base + o], gscale);
+            if (guard_bad(x)) {
+                x = 0.0f;
+                bad = min(bad, o);
+            }
+            acc[0] = __builtin_fma((double)x, (double)x, acc[0]);
+        }
+    }
+    const double s = guard_wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
+    const long kk = guard_wave_min(bad == 0xffffffffu ? GUARD_NONE : ((range << 40) | (base + (long)bad)));
+    if ((t & 63) == 0) {
+        s_sum[t >> 6] = s;
+        s_key[t >> 6] = kk;
+    }
+    __syncthreads();
+    if (t == 0) {
+        part[blockIdx.x] = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+        long m = s_key[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) m = s_key[w] < m ? s_key[w] : m;
+        key[blockIdx.x] = m;
+    }
+}
+
+// one workgroup: the partials of all ranges in index order (thread t takes t, t + 1024, ...; shuffle tree; the 16 waves in wave
+// order), then the control block
+__global__ __launch_bounds__(1024) void guard_finish_kernel(const double* __restrict__ part, const long* __restrict__ key,
+                                                           long nchunks, float max_norm, int skip_nonfinite,
+                                                           uniir_grad_ctl* __restrict__ ctl) {
+    __shared__ double s_sum[16];
+    __shared__ long s_key[16];
+    const unsigned t = threadIdx.x;
+    double acc = 0.0;
+    long kmin = GUARD_NONE;
+    for (long i = t; i < nchunks; i += 1024) {
+        acc += part[i];
+        const long k = key[i];
+        kmin = k < kmin ? k : kmin;
+    }
+    acc = guard_wave_sum(acc);
+    kmin = guard_wave_min(kmin);
+    if ((t & 63) == 0) {
+        s_sum[t >> 6] = acc;
+        s_key[t >> 6] = kmin;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    double sumsq = s_sum[0];
+    long m = s_key[0];
+    for (int w = 1; w < 16; ++w) {
+        sumsq += s_sum[w];
+        m = s_key[w] < m ? s_key[w] : m;
+    }
+    const float norm = (float)sqrt(sumsq);                       // the f64 root, then one rounding to fp32
+    const int nonfinite = (m != GUARD_NONE) || guard_bad(norm);
+    const int skip = nonfinite && skip_nonfinite;
+    float coef = 1.0f;
+    if (skip) coef = 0.0f;
+    else if (max_norm > 0.0f && !nonfinite) coef = fminf(1.0f, __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f)));
+    ctl->sumsq = sumsq;
+    ctl->norm = norm;
+    ctl->coef = coef;
+    ctl->nonfinite = nonfinite;
+    ctl->skip = skip;
+    ctl->first_bad_range = m == GUARD_NONE ? -1 : (int32_t)(m >> 40);
+    ctl->first_bad_chunk = m == GUARD_NONE ? -1 : (int32_t)((m & ((1L << 40) - 1)) / GUARD_CHUNK);
+    ctl->first_bad_index = m == GUARD_NONE ? -1 : (m & ((1L << 40) - 1));
+    ctl->steps_seen += 1;
+    ctl->steps_skipped += skip;
+}
+
+extern "C" int64_t uniir_grad_guard_chunk(void) { return GUARD_CHUNK; }
+static int64_t guard_chunks(int64_t count) { return (count + GUARD_CHUNK - 1) / GUARD_CHUNK; }
+extern "C" int64_t uniir_grad_guard_workspace_bytes(const int64_t* counts, int32_t nranges) {
+    if (nranges < 0 || nranges > (1 << 20) || (nranges > 0 && !counts)) return -1;          // the key keeps 23 bits for the range
+    int64_t chunks = 0;
+    for (int32_t r = 0; r < nranges; ++r) {
+        if (counts[r] < 0 || counts[r] >= (1LL << 40)) return -1;
+        chunks += guard_chunks(counts[r]);
+    }
+    return (chunks * 16 + 255) / 256 * 256;          // an fp64 partial and a 64-bit key per chunk
+}
+extern "C" int uniir_grad_guard(const float* const* grads, const int64_t* counts, int32_t nranges, float grad_scale,
+                                float max_norm, int32_t skip_nonfinite, uniir_grad_ctl* ctl_dev, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+    if (nranges < 0 || (nranges > 0 && (!grads || !counts)) || !ctl_dev) return UNIIR_EINVAL;
+    if (!(grad_scale >= 0.0f) || max_norm != max_norm) return UNIIR_EINVAL;          // a NaN grad_scale fails the first test
+    for (int32_t r = 0; r < nranges; ++r)
+        if (counts[r] < 0 || (counts[r] > 0 && !grads[r])) return UNIIR_EINVAL;
+    const int64_t need = uniir_grad_guard_workspace_bytes(counts, nranges);
+    if (need < 0 || workspace_bytes < need || (need > 0 && !workspace)) return UNIIR_EINVAL;
+    for (int32_t r = 0; r < nranges; ++r)
+        if (counts[r] > 0 && ((uintptr_t)grads[r] & 15)) return UNIIR_EALIGN;
+    if (((uintptr_t)ctl_dev & 15) || ((uintptr_t)workspace & 255)) return UNIIR_EALIGN;
+    int64_t total = 0;
+    for (int32_t r = 0; r < nranges; ++r) total += guard_chunks(counts[r]);
+    double* part = (double*)workspace;
+    long* key = (long*)(part + total);
+    int64_t at = 0;
+    for (int32_t r = 0; r < nranges; ++r) {
+        if (counts[r] == 0) continue;
+        const int64_t c = guard_chunks(counts[r]);
+        hipLaunchKernelGGL(guard_sumsq_kernel, dim3((unsigned)c), dim3(256), 0, (hipStream_t)stream, grads[r], (long)counts[r],
+                           grad_scale, (long)r, part + at, key + at);
+        HIP_LAUNCH_CHECK();
+        at += c;
+    }
+    hipLaunchKernelGGL(guard_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, part, key, (long)total, max_norm,
+                       skip_nonfinite != 0, ctl_dev);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+// adamw_kernel line for line, behind the control block: skip != 0 returns before anything is touched, otherwise the gradient is
+// (g * gscale) * coef -- coef == 1 gives adamw_kernel's bits.  The two loads have a wave-uniform address: one scalar load each.
+__global__ __launch_bounds__(256) void adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v,
+                                                            unsigned short* __restrict__ pb, long n, float lr, float b1,
+                                                            float b2, float eps, float wd, float bc1, float bc2s,
+                                                            float gscale, const uniir_grad_ctl* __restrict__ ctl) {
+    if (ctl->skip != 0) return;
+    const float coef = ctl->coef;
+    const long nv = n >> 2;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+        f32x4_t pp = *reinterpret_cast<f32x4_t*>(p + 4 * i);
+        const f32x4_t gg = (*reinterpret_cast<const f32x4_t*>(g + 4 * i) * gscale) * coef;
+        f32x4_t mm = *reinterpret_cast<f32x4_t*>(m + 4 * i);
+        f32x4_t vv = *reinterpret_cast<f32x4_t*>(v + 4 * i);
+        pp = pp * (1.0f - lr * wd);
+        mm = mm * b1 + gg * (1.0f - b1);
+        vv = vv * b2 + gg * gg * (1.0f - b2);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float denom = sqrtf(vv[e]) / bc2s + eps;
+            pp[e] -= (lr / bc1) * (mm[e] / denom);
+        }
+        *reinterpret_cast<f32x4_t*>(p + 4 * i) = pp;
+        *reinterpret_cast<f32x4_t*>(m + 4 * i) = mm;
+        *reinterpret_cast<f32x4_t*>(v + 4 * i) = vv;
+        if (pb) {
+            u32x2_t o = {pack_bf16x2(pp[0], pp[1]), pack_bf16x2(pp[2], pp[3])};
+            *reinterpret_cast<u32x2_t*>(pb + 4 * i) = o;
+        }
+    }
+    // tail (count % 4)
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (nv << 2) + threadIdx.x;
+        float pp = p[i] * (1.0f - lr * wd);
+        const float gg = (g[i] * gscale) * coef;
+        const float mm = m[i] * b1 + gg * (1.0f - b1);
+        const float vv = v[i] * b2 + gg * gg * (1.0f - b2);
+        pp -= (lr / bc1) * (mm / (sqrtf(vv) / bc2s + eps));
+        p[i] = pp; m[i] = mm; v[i] = vv;
+        if (pb) pb[i] = f32_to_bf16(pp);
+    }
+}
+extern "C" int uniir_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* param_bf16,
+                                        int64_t count, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                        int32_t step, float grad_scale, const uniir_grad_ctl* ctl_dev, void* stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !ctl_dev || count < 0 || step < 1) return UNIIR_EINVAL;
+    if (count == 0) return UNIIR_OK;
+    if (((uintptr_t)param & 15) || ((uintptr_t)grad & 15) || ((uintptr_t)exp_avg & 15) ||
+        ((uintptr_t)exp_avg_sq & 15) || ((uintptr_t)param_bf16 & 7) || ((uintptr_t)ctl_dev & 15))
+        return UNIIR_EALIGN;
+    const float bc1 = 1.0f - powf(beta1, (float)step);
+    const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+    hipLaunchKernelGGL(adamw_guarded_kernel, dim3(grid_for(count / 4 + 1, 256, 16384)), dim3(256), 0,
+                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, (unsigned short*)param_bf16,
+                       (long)count, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, ctl_dev);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // BLIP pieces (uniir_blip): tanh pooler (med.py:499-511), momentum EMA (blip_ff.py:288-292) and the soft-target
 // contrastive loss over [in-batch | queue] similarities (blip_ff.py:219-231).
 __global__ __launch_bounds__(256) void tanh_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long n) {

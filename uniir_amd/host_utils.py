@@ -358,14 +358,28 @@ class DevicePrefetcher:
             yield batch
 
 
+def scaler_state(optimizer):
+    """the "scaler" entry of a checkpoint: {} as ever, or the gradient guard's counters where the optimizer has one
+    (trainer.GradGuard: the part of the reference's GradScaler that survives without a loss scale)"""
+    if getattr(optimizer, "guard", None) is None:
+        return {}
+    sd = optimizer.state_dict()
+    return {"steps_seen": sd["steps_seen"], "steps_skipped": sd["steps_skipped"]}
+
+
 def run_train_epoch(model, data_loader, optimizer, scheduler, config, gpu_id, epoch, step_fn):
     """forward, loss / accumulation_steps, backward, optimizer + scheduler step every accumulation_steps micro-batches;
-    the logged lr is read after scheduler.step() and the logged loss is un-scaled, like the reference"""
+    the logged lr is read after scheduler.step() and the logged loss is un-scaled, like the reference.  With a gradient guard
+    (trainer.GradGuard) a grad_norm meter joins the log and every skipped step prints one line; without one the log is unchanged."""
     model.train()
     log = MetricLogger(delimiter="  ")
     log.add_meter("lr", SmoothedValue(window_size=1, fmt="{value:.6f}"))
     log.add_meter("loss", SmoothedValue(window_size=1, fmt="{value:.4f}"))
     log.add_meter("inbatch_accuracy", SmoothedValue(window_size=1, fmt="{value:.4f}"))
+    guarded = getattr(optimizer, "guard", None) is not None
+    if guarded:
+        log.add_meter("grad_norm", SmoothedValue(window_size=1, fmt="{value:.4f}"))
+    stepped = False
     accum = config.trainer_config.gradient_accumulation_steps
     pending, n = 0, len(data_loader)
     feed = DevicePrefetcher(data_loader, gpu_id)
@@ -381,9 +395,17 @@ def run_train_epoch(model, data_loader, optimizer, scheduler, config, gpu_id, ep
             model.zero_grad()
             scheduler.step()
             pending = 0
+            stepped = True
         log.update(loss=scaled.item() * accum)                 # host sync, as in the reference's loop
         log.update(lr=optimizer.param_groups[0]["lr"])
         log.update(inbatch_accuracy=outputs["accuracy"].item())
+        if guarded and stepped:                                # after the .item() above: the step's launches have finished
+            stepped = False
+            stats = optimizer.grad_stats()
+            log.update(grad_norm=stats["norm"])                # over the finite elements of the scaled gradient, before clipping
+            if stats["skipped"]:
+                print(f"step skipped: non-finite gradient in {stats['first_bad'] or 'the global norm'} "
+                      f"({stats['steps_skipped']} of {stats['steps_seen']} steps skipped)")
     log.synchronize_between_processes()
     print("Averaged stats:", log.global_avg())
     return {k: meter.global_avg for k, meter in log.meters.items()}

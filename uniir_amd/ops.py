@@ -517,6 +517,31 @@ def dropout_bf16_(x, p, seed, *, rowscale=None, rows_per_scale=0, row_map=None):
                                          int(rows_per_scale), _stream()), "dropout_bf16")
 
 
+def grad_guard_chunk():
+    """elements per partial sum of the gradient guard (a compile-time constant of the library)"""
+    return int(_lib.load().uniir_grad_guard_chunk())
+
+
+class GradGuardPlan:
+    """the host arrays of one uniir_grad_guard call over fixed ranges: [(flat fp32 tensor, lo, hi)] -> pointers, counts and the
+    workspace size; built once per layout, launched every step (launch())"""
+
+    def __init__(self, ranges):
+        n = len(ranges)
+        self.key = tuple((t.data_ptr(), lo, hi) for t, lo, hi in ranges)
+        self.ptrs = (C.c_void_p * max(1, n))(*[t.data_ptr() + 4 * lo for t, lo, _ in ranges])
+        self.counts = (C.c_int64 * max(1, n))(*[hi - lo for _, lo, hi in ranges])
+        self.n = n
+        self.workspace_bytes = int(_lib.load().uniir_grad_guard_workspace_bytes(self.counts, n))
+        if self.workspace_bytes < 0:
+            raise RuntimeError("uniir_grad_guard: ranges refused (a count below 0 or of 2^40 elements and more)")
+
+    def launch(self, grad_scale, max_norm, skip_nonfinite, ctl, workspace):
+        check(_lib.load().uniir_grad_guard(self.ptrs, self.counts, self.n, float(grad_scale), float(max_norm), int(skip_nonfinite),
+                                           _p(ctl), _p(workspace), workspace.numel() if workspace is not None else 0, _stream()),
+              "grad_guard")
+
+
 def call(name, *args):
     """Generic checked call: tensors are converted to device pointers, the stream is appended."""
     conv = [(_p(a) if isinstance(a, torch.Tensor) else a) for a in args]

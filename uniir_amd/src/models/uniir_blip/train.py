@@ -24,8 +24,8 @@ from models.uniir_blip.backbone.blip import load_checkpoint
 from models.uniir_blip.blip_featurefusion.blip_ff import blip_ff
 from models.uniir_blip.blip_scorefusion.blip_sf import blip_sf
 from models.uniir_blip.engine import eval_engine, train_one_epoch
-from uniir_amd.host_utils import load_checkpoint_file
-from uniir_amd.trainer import CosineLR, NativeAdamW
+from uniir_amd.host_utils import load_checkpoint_file, scaler_state
+from uniir_amd.trainer import CosineLR, NativeAdamW, guard_settings
 
 logger = logging.getLogger()
 
@@ -54,7 +54,7 @@ def save_checkpoint(model, optimizer, scheduler, epoch, scaler, config):
     path = os.path.join(config.uniir_dir, ckpt.ckpt_dir, f"{config.model.short_name.lower()}_epoch_{epoch}.pth")
     os.makedirs(os.path.dirname(path), exist_ok=True)
     torch.save({"model": model.state_dict(), "optimizer": optimizer.state_dict(), "scheduler": scheduler.state_dict(),
-                "config": config.to_dict(), "epoch": epoch, "scaler": {}}, path)
+                "config": config.to_dict(), "epoch": epoch, "scaler": scaler_state(optimizer)}, path)
     print(f"Saved checkpoint to {path}")
 
 
@@ -86,7 +86,9 @@ def main(config):
     if distributed:          # the reference wraps in DDP here (train.py:217-218): rank 0's parameters and buffers to every replica
         from uniir_amd import comm
         comm.sync_replicas(model)
-    optimizer = NativeAdamW(model, lr=tc.init_lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=tc.weight_decay)
+    max_grad_norm, skip_nonfinite = guard_settings(trainer_config=tc)          # optional keys, absent = off
+    optimizer = NativeAdamW(model, lr=tc.init_lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=tc.weight_decay,
+                            max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     # UNIIR_BLIP_RANDAUGMENT=1: the reference's RandomAugment(2, 5) in the train transform (blip_transform.py:11-40); off by default
     randaugment = (2, 5) if os.environ.get("UNIIR_BLIP_RANDAUGMENT") == "1" else None
     train_ds, collate = build_dataset(config, model.get_tokenizer(), model.get_img_preprocess_fn(randaugment=randaugment), train=True)

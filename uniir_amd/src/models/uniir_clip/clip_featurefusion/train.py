@@ -23,8 +23,8 @@ from common.config import OmegaConf
 from data.mbeir_dataset import MBEIRMainCollator, MBEIRMainDataset, Mode
 from models.uniir_clip.clip_featurefusion.clip_ff import CLIPFeatureFusion
 from models.uniir_clip.engine import eval_engine, train_one_epoch
-from uniir_amd.host_utils import load_checkpoint_file
-from uniir_amd.trainer import CosineLR, NativeAdamW
+from uniir_amd.host_utils import load_checkpoint_file, scaler_state
+from uniir_amd.trainer import CosineLR, NativeAdamW, guard_settings
 
 logger = logging.getLogger()
 
@@ -53,7 +53,7 @@ def save_checkpoint(model, optimizer, scheduler, epoch, scaler, config):
     path = os.path.join(config.uniir_dir, ckpt.ckpt_dir, f"{config.model.short_name.lower()}_epoch_{epoch}.pth")
     os.makedirs(os.path.dirname(path), exist_ok=True)
     torch.save({"model": model.state_dict(), "optimizer": optimizer.state_dict(), "scheduler": scheduler.state_dict(),
-                "config": config.to_dict(), "epoch": epoch, "scaler": {}}, path)
+                "config": config.to_dict(), "epoch": epoch, "scaler": scaler_state(optimizer)}, path)
     print(f"Saved checkpoint to {path}")
 
 
@@ -81,9 +81,11 @@ def main(config):
         comm.sync_replicas(model)
     # three groups like clip_featurefusion/train.py:52-66,200-208: CLIP gains/biases (wd 0), CLIP rest (wd 0.2), every T5
     # parameter (wd 0.2, its own learning rate trainer_config.t5_learning_rate)
+    max_grad_norm, skip_nonfinite = guard_settings(trainer_config=config.trainer_config)          # optional keys, absent = off
     optimizer = NativeAdamW(model.clip_model, lr=config.trainer_config.learning_rate, betas=(0.9, 0.98), eps=1.0e-6,
                             weight_decay=0.2,
-                            extra=[model.t5_optimizer_group(lr=config.trainer_config.t5_learning_rate, weight_decay=0.2)])
+                            extra=[model.t5_optimizer_group(lr=config.trainer_config.t5_learning_rate, weight_decay=0.2)],
+                            max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     train_ds, collate = build_dataset(config, model.get_tokenizer(), model.get_img_preprocess_fn(), train=True)
     sampler = DistributedSampler(train_ds, num_replicas=utils.get_world_size(), rank=utils.get_rank(), shuffle=True)
     loader = DataLoader(train_ds, batch_size=config.dataloader_config.train_batch_size,

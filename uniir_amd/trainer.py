@@ -4,17 +4,113 @@ Mirrors UniIR src/models/uniir_clip/engine.py:19-50 (forward, loss / accumulatio
 accumulation_steps, scheduler.step) and clip_scorefusion/train.py:52-61,195-199,281-284 (AdamW lr 1e-5 betas
 (0.9,0.98) eps 1e-6, weight decay 0 for gains / biases / logit_scale and 0.2 for the rest,
 CosineAnnealingLR(T_max, eta_min=0)).  Differences, all result-preserving:
-  * bf16 MFMA compute needs no GradScaler (the reference's fp16 autocast does);
+  * bf16 MFMA compute needs no GradScaler's loss scale (the reference's fp16 autocast does); the other half of scaler.step() -- a step
+    whose gradients hold Inf / NaN is not applied -- is the opt-in GradGuard below, with clip_grad_norm_ on top;
   * gradients live in one flat fp32 buffer: DDP's bucketed all-reduce(mean) becomes RCCL all-reduce(sum) of ranges of
     that buffer, launched per finished residual block while backward still runs (comm.GradReducer; one blocking
     all-reduce of the remainder at step()), with the 1/world factor folded into the fused AdamW kernel;
   * AdamW is one fused kernel per weight-decay group and refreshes the bf16 weight shadow in the same pass.
 """
+import bisect
 import math
+import os
 
 import torch
 
-from . import comm, ops
+from . import _lib, comm, ops
+
+
+def guard_settings(max_grad_norm=None, skip_nonfinite=False, trainer_config=None):
+    """-> (max_grad_norm or None, skip_nonfinite) of the gradient guard, both off unless something asks: an explicit argument, else
+    the optional YAML keys trainer_config.max_grad_norm / trainer_config.skip_nonfinite_steps (absent in every reference YAML), else the
+    environment, UNIIR_MAX_GRAD_NORM=<float> / UNIIR_SKIP_NONFINITE=1.  A norm of 0 or below means no clipping."""
+    def cfg(key):
+        if trainer_config is None:
+            return None
+        return trainer_config.get(key, None) if hasattr(trainer_config, "get") else getattr(trainer_config, key, None)
+
+    if max_grad_norm is None:
+        max_grad_norm = cfg("max_grad_norm")
+    if max_grad_norm is None and os.environ.get("UNIIR_MAX_GRAD_NORM", "") != "":
+        max_grad_norm = os.environ["UNIIR_MAX_GRAD_NORM"]
+    if max_grad_norm is not None:
+        max_grad_norm = float(max_grad_norm)
+        if math.isnan(max_grad_norm):
+            raise ValueError("max_grad_norm is NaN")
+        if max_grad_norm <= 0:
+            max_grad_norm = None
+    if not skip_nonfinite:
+        skip_nonfinite = cfg("skip_nonfinite_steps")
+        if skip_nonfinite is None:
+            skip_nonfinite = os.environ.get("UNIIR_SKIP_NONFINITE", "0") not in ("", "0")
+    return max_grad_norm, bool(skip_nonfinite)
+
+
+class GradGuard:
+    """The device-side guard around the optimizer step (include/uniir_hip.h [OPT] gradient guard): one uniir_grad_guard call per step
+    over the AdamW ranges of every store fills a 64-byte control block on the device -- the global norm of the gradient AdamW will
+    consume, the clip_grad_norm_ coefficient, and whether the step is skipped because a gradient is Inf / NaN -- and the guarded AdamW
+    launches read it there.  The host never reads device memory inside step(): the block is copied to a pinned mirror behind the
+    step's launches and read one step later (resolve())."""
+
+    def __init__(self, max_grad_norm=None, skip_nonfinite=False):
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.steps_seen = self.steps_skipped = 0      # as of the last resolved step (or the checkpoint)
+        self.ctl = self.mirror = self.event = self.workspace = self.plan = None
+        self.pending = False
+        self.stats = None                             # of the last resolved step
+        self._where = []                              # (store, lo) of every range of the pending step
+
+    def _device_state(self, dev):
+        if self.ctl is None or self.ctl.device != dev:
+            host = torch.zeros(8, dtype=torch.int64)
+            host[5], host[6] = self.steps_seen, self.steps_skipped
+            self.ctl = host.to(dev)                   # the allocator's blocks are 512-byte aligned
+            self.mirror = torch.zeros(8, dtype=torch.int64).pin_memory()
+            self.event = torch.cuda.Event()
+            self.workspace = None
+
+    def measure(self, ranges, grad_scale):
+        """ranges: [(FlatStore, lo, hi)], every AdamW range of the step.  Launches the norm / scan kernels and the finish."""
+        dev = ranges[0][0].dev
+        self._device_state(dev)
+        key = tuple((st.g32.data_ptr(), lo, hi) for st, lo, hi in ranges)
+        if self.plan is None or self.plan.key != key:
+            self.plan = ops.GradGuardPlan([(st.g32, lo, hi) for st, lo, hi in ranges])
+        if self.workspace is None or self.workspace.numel() < self.plan.workspace_bytes:
+            self.workspace = torch.empty(max(256, self.plan.workspace_bytes), dtype=torch.uint8, device=dev)
+        self._where = [(st, lo) for st, lo, _ in ranges]
+        self.plan.launch(grad_scale, self.max_grad_norm or 0.0, self.skip_nonfinite, self.ctl, self.workspace)
+
+    def publish(self):
+        """behind the step's launches: control block -> pinned mirror, asynchronously, and an event"""
+        self.mirror.copy_(self.ctl, non_blocking=True)
+        self.event.record()
+        self.pending = True
+
+    def resolve(self):
+        """wait for the last published step and read its outcome; -> True when that step was skipped and not yet reported"""
+        if not self.pending:
+            return False
+        self.event.synchronize()
+        self.pending = False
+        c = _lib.GradCtl.from_buffer_copy(self.mirror.numpy().tobytes())
+        first_bad = None
+        if c.first_bad_range >= 0:
+            st, lo = self._where[c.first_bad_range]
+            names, offs = list(st.off), list(st.off.values())
+            first_bad = names[bisect.bisect_right(offs, lo + c.first_bad_index) - 1]
+        self.steps_seen, self.steps_skipped = int(c.steps_seen), int(c.steps_skipped)
+        self.stats = {"norm": float(c.norm), "coef": float(c.coef), "skipped": bool(c.skip), "nonfinite": bool(c.nonfinite),
+                      "sumsq": float(c.sumsq), "steps_seen": self.steps_seen, "steps_skipped": self.steps_skipped,
+                      "first_bad": first_bad}
+        return bool(c.skip)
+
+    def load_counters(self, seen, skipped):
+        self.steps_seen, self.steps_skipped = int(seen), int(skipped)
+        if self.ctl is not None:
+            self.ctl[5:7] = torch.tensor([self.steps_seen, self.steps_skipped], dtype=torch.int64)
 
 
 class NativeAdamW(torch.optim.Optimizer):
@@ -24,13 +120,19 @@ class NativeAdamW(torch.optim.Optimizer):
     (param_groups / lr schedulers / state_dict work)."""
 
     def __init__(self, clip_model, lr=1e-5, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2, allreduce=True, extra=None,
-                 overlap=True, bucket_bytes=64 << 20):
+                 overlap=True, bucket_bytes=64 << 20, max_grad_norm=None, skip_nonfinite=False):
         """clip_model: the model that owns the main store (CLIP, BLIPFeatureFusion): _ensure_flat() -> its FlatStore,
         optimizer_groups() -> (no-decay params, decay params), adamw_group(name) -> 0 / 1, or None for a tensor that is not
         stepped (BLIP_SF's frozen cross-attention).
         extra: further flat parameter stores, each one param group of its own -- objects with .params (list of nn.Parameter),
         .store() (-> FlatStore), .weight_decay and .lr (CLIP_FF's T5 stack: clip_featurefusion/train.py:52-61 gives it weight
-        decay 0.2 on everything and its own learning rate)"""
+        decay 0.2 on everything and its own learning rate)
+        max_grad_norm / skip_nonfinite: the gradient guard (GradGuard), off by default and then absent: step() issues the plain
+        AdamW launches and nothing else.  max_grad_norm clips the global norm over every store like clip_grad_norm_; skip_nonfinite
+        leaves a step out whose gradients hold Inf or NaN, as the reference's scaler.step(optimizer) does.  The environment
+        (UNIIR_MAX_GRAD_NORM, UNIIR_SKIP_NONFINITE) is read here where the arguments are left at their defaults."""
+        max_grad_norm, skip_nonfinite = guard_settings(max_grad_norm, skip_nonfinite)
+        self.guard = GradGuard(max_grad_norm, skip_nonfinite) if (max_grad_norm is not None or skip_nonfinite) else None
         self.clip = clip_model
         self.extra = list(extra or [])
         nd, d = clip_model.optimizer_groups()
@@ -78,6 +180,8 @@ class NativeAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         main = self._buffers()
+        if self.guard is not None:
+            self._resolve_guard()          # the outcome of the step before this one: a skipped step does not count
         world = comm.world() if self.allreduce else 1
         reduced = set()                    # gradient buffers already all-reduced in this step
         if world > 1:
@@ -87,6 +191,8 @@ class NativeAdamW(torch.optim.Optimizer):
                 reduced.add(main.g32.data_ptr())
         self.clip._grad_reducer = None
         self.opt_step += 1
+        if self.guard is not None:
+            return self._step_guarded(main, world, reduced)
         for i, (store, group_of) in enumerate(self.sources):
             st = main if i == 0 else store()
             m, v = self._moments(i, st)
@@ -104,6 +210,46 @@ class NativeAdamW(torch.optim.Optimizer):
             if i == 0:
                 self.clip._refresh_conv()      # the padded bf16 patch-embedding weights are not part of the shadow
 
+    def _step_guarded(self, main, world, reduced):
+        """the rest of step() behind the gradient guard: the all-reduce of every store first, then ONE norm / scan over the AdamW
+        ranges of all stores (a global norm, as clip_grad_norm_(model.parameters()) takes it; frozen tensors are in no range), then
+        the guarded AdamW launches, which read the decision on the device"""
+        work = []
+        for i, (store, group_of) in enumerate(self.sources):
+            st = main if i == 0 else store()
+            m, v = self._moments(i, st)
+            if world > 1 and st.g32.data_ptr() not in reduced:
+                comm.allreduce_sum_(st.g32)
+                self.last_collectives += 1
+            if self._ranges[i][0] is not st:
+                self._ranges[i] = (st, st.ranges(group_of))
+            work.append((st, m, v, self._ranges[i][1]))
+        self.guard.measure([(st, lo, hi) for st, _, _, rs in work for lo, hi, _ in rs], 1.0 / world)
+        for i, (st, m, v, rs) in enumerate(work):
+            for lo, hi, gi in rs:
+                group = self.param_groups[gi]
+                b1, b2 = group["betas"]
+                ops.call("uniir_adamw_step_guarded", st.p32[lo:hi], st.g32[lo:hi], m[lo:hi], v[lo:hi], st.w16_buf[lo:hi], hi - lo,
+                         float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], self.opt_step, 1.0 / world,
+                         self.guard.ctl)
+            st.mark_half_stale()
+            if i == 0:
+                self.clip._refresh_conv()
+        self.guard.publish()
+
+    def _resolve_guard(self):
+        if self.guard.resolve():           # that step was skipped: bias correction counts applied steps only, as torch's does when
+            self.opt_step -= 1             # scaler.step() leaves optimizer.step() out
+
+    def grad_stats(self):
+        """the guard's view of the last step(): {"norm", "coef", "skipped", "nonfinite", "sumsq", "steps_seen", "steps_skipped",
+        "first_bad"}; first_bad is the name of the tensor (FlatStore.off) that holds the first non-finite gradient, None without one.
+        Waits for that step's launches.  None without a guard or before the first step."""
+        if self.guard is None:
+            return None
+        self._resolve_guard()
+        return self.guard.stats
+
     def zero_grad(self, set_to_none=False):
         self.clip._ensure_flat()
         self.clip.zero_grad()
@@ -111,9 +257,15 @@ class NativeAdamW(torch.optim.Optimizer):
             e.store().g32.zero_()
 
     def state_dict(self):
+        if self.guard is not None:
+            self._resolve_guard()          # opt_step below counts applied steps
         exp_avg, exp_avg_sq = self.mv[0] or (None, None)
-        return {"opt_step": self.opt_step, "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq, "extra": self.mv[1:],
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+        sd = {"opt_step": self.opt_step, "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq, "extra": self.mv[1:],
+              "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+        if self.guard is not None:
+            sd.update(steps_seen=self.guard.steps_seen, steps_skipped=self.guard.steps_skipped,
+                      max_grad_norm=self.guard.max_grad_norm, skip_nonfinite=self.guard.skip_nonfinite)
+        return sd
 
     def load_state_dict(self, sd):
         self.opt_step = sd["opt_step"]
@@ -121,6 +273,9 @@ class NativeAdamW(torch.optim.Optimizer):
         self.mv = [main] + list(sd.get("extra", self.mv[1:]))
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update(s)
+        if self.guard is not None:         # the counters travel; the settings are this run's own (a checkpoint without them: zeros)
+            self.guard.pending = False
+            self.guard.load_counters(sd.get("steps_seen", 0), sd.get("steps_skipped", 0))
 
 
 class CosineLR:
@@ -146,11 +301,12 @@ class CosineLR:
 
 class NativeTrainer:
     def __init__(self, model, lr=1e-5, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2, t_total=1000,
-                 accumulation_steps=1):
+                 accumulation_steps=1, max_grad_norm=None, skip_nonfinite=False):
         self.model = model
         self.clip = model.clip_model
         extra = [model.t5_optimizer_group(lr=lr, weight_decay=weight_decay)] if hasattr(model, "t5_optimizer_group") else None
-        self.opt = NativeAdamW(self.clip, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, extra=extra)
+        self.opt = NativeAdamW(self.clip, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, extra=extra,
+                               max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         self.sched = CosineLR(self.opt, t_total)
         self.accum = accumulation_steps
         self.micro = 0
