@@ -761,11 +761,22 @@ int uniir_meanpool_bwd(const float* dout, float* dx, int32_t n, int32_t tokens, 
  *   uniir_topk_coarse:    MFMA fp16 scan; per query a shortlist of uniir_topk_ncand(nq, kc) pool rows that is
  *                         guaranteed to contain the kc best by approximate score; kc >= k, kc <= 64.
  *   uniir_topk_rescore:   exact fp32 re-score of a shortlist in the oracle's summation order, sort by
- *                         (score desc, id asc), keep k.  exact_ws: nq*ncand floats of scratch.
- * Layouts: pool fp16 [n][dim] (dim % 64 == 0), queries fp16 [nq][dim] as stored by the embedder
- * (un-normalised), ids int64 [n].  Outputs: cand_idx int32 [nq][ncand] pool-row indices (-1 = empty),
+ *                         (score desc, id asc), keep k.  exact_ws: nq*ncand floats of scratch.  A row may
+ *                         appear at most once in a query's shortlist.
+ * Layouts: pool fp16 [n][dim], queries fp16 [nq][dim] as stored by the embedder (un-normalised), ids
+ * int64 [n].  dim % 32 == 0 for uniir_topk_coarse, dim % 8 == 0 for uniir_topk_rescore, dim % 64 == 0 for
+ * uniir_topk_ip; n * dim * 2 < 2 GiB for the scans (UNIIR_ESHAPE otherwise); pool, queries and inverse norms
+ * 16-byte aligned (UNIIR_EALIGN).  Outputs: cand_idx int32 [nq][ncand] pool-row indices (-1 = empty),
  * out_scores f32 [nq][k] descending, out_ids int64 [nq][k] (-1 padded like FAISS).
- * workspace: uniir_topk_workspace_bytes(nq, kc) bytes.
+ * workspace: uniir_topk_workspace_bytes(nq, kc, rows) bytes, 16-byte aligned.
+ * MASS TIES.  The scans keep one maximum per group of 16 rows and the selection keeps at most 2 (k + 8)
+ * groups per query.  When more groups than that tie EXACTLY at the k-th best score (a zero query, whose
+ * scores are all 0; a pool of identical rows), the tied groups kept are those of the lowest row index, so
+ * the ids returned are the smallest among the rows of the kept groups, not the smallest of the whole pool
+ * as an exhaustive (score desc, id asc) sort gives them.  The answer is still a valid one: the scores are
+ * those of the exhaustive search at every rank, bit for bit, every (score, id) returned is the exact score
+ * of that row, ids are distinct and ascend among equal scores.  Near-ties (scores that differ) and fewer
+ * tied groups than 2 (k + 8) are ordered exactly (tests/topk_cases.py, tests/test_topk_paths_gpu.py).
  * ---------------------------------------------------------------------------------------------- */
 int uniir_pool_inv_norms(const void* x_f16, int64_t n, int32_t dim, float* inv_norm, void* stream);
 int64_t uniir_topk_workspace_bytes(int32_t nq, int32_t kc, int64_t rows);
@@ -782,7 +793,9 @@ int uniir_topk_rescore(const void* pool_f16, const float* pool_inv_norm, const i
  * (mbeir_retriever.py:188-232 search_index: faiss.normalize_L2(queries); index.search(queries, k)):
  * per chunk of <= 1024 queries one sweep of the shard (MFMA group-max scan: queries in registers and the pool streamed once for
  * <= 256 queries, GEMM-shaped above), then a fused group selection + query norm + exact re-score launch and the final sort.
- * k <= 56.  Same results as coarse + rescore, bit for bit.
+ * k <= 56.  Candidates: behind the streaming / ping-pong scans every group whose maximum lies within the proven rounding bound of
+ * the k-th best group maximum (GselBound, csrc/topk_select.h; at most 2 (k + 8) groups), not the fixed k + 8 groups of
+ * uniir_topk_coarse -- the results are those of the exhaustive search either way (MASS TIES above excepted), bit for bit.
  * rows * dim * 2 must stay below 2 GiB (UNIIR_ESHAPE otherwise: the shard is addressed through 31-bit buffer offsets); a larger
  * resident shard -- the whole 5.6 M x 768 M-BEIR pool on one GPU -- is searched as equal row ranges and merged with
  * uniir_topk_merge (uniir_amd/retrieval.py subshard_bounds), which is the search of the whole shard.

@@ -224,7 +224,8 @@ extern "C" int uniir_topk_rescore(const void* pool_f16, const float* pool_inv_no
         !out_ids)
         return UNIIR_EINVAL;
     if (rows <= 0 || nq <= 0 || ncand <= 0 || k <= 0) return UNIIR_EINVAL;
-    if (dim % 8) return UNIIR_ESHAPE;
+    if (dim <= 0 || dim % 8) return UNIIR_ESHAPE;
+    if (((uintptr_t)pool_f16 & 15) || ((uintptr_t)queries_f16 & 15)) return UNIIR_EALIGN;      // both kernels read rows 16 bytes at a time
     hipStream_t st = (hipStream_t)stream;
     const long pairs = (long)nq * ncand;
     if (dim % 64 == 0)
