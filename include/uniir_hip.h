@@ -161,6 +161,22 @@ int uniir_layernorm_bwd_ex(const float* x, int64_t x_stride, const float* gamma,
                            int32_t dy_is_f32, const float* dres, float* dx_f32, int64_t dx_stride,
                            void* dx_bf16, float* dgamma, float* dbeta, float* dx_colsum, const float* branch_scale,
                            int32_t rows, int32_t width, float eps, void* stream);
+/* A weight gradient (uniir_gemm of `d`) and an INDEPENDENT LayerNorm backward (the arguments of uniir_layernorm_bwd_ex) as one launch
+ * of one workgroup per compute unit: `side_cus` of the 256 run the LayerNorm rows, the others the product as fp32 split-K slabs in
+ * d->splitk_ws (added to C in K order afterwards).  The product is bound by the matrix pipes and the LayerNorm by HBM, so each runs
+ * in the other's shadow.  Results: dx_f32 / dx_bf16 are bitwise those of uniir_layernorm_bwd_ex; dgamma / dbeta / dx_colsum and C are
+ * fixed-order sums (the same bits in every run; C bitwise uniir_gemm's at the same split count).  The fused launch needs a bf16
+ * product with both operands K-major and the accumulating epilogue on 256 x 256 tiles, bf16 dy, a width of 512 / 768 / 1024, a chunk
+ * plan (uniir_gemm_wgrad_side_plan > 0) and a workspace that holds its slabs; whenever one of these fails the call IS uniir_gemm
+ * followed by uniir_layernorm_bwd_ex, so callers never branch.  side_cus <= 0: always the two launches. */
+int uniir_gemm_wgrad_ln_bwd(const uniir_gemm_desc* d, const float* x, int64_t x_stride, const float* gamma, const void* dy,
+                            int32_t dy_is_f32, const float* dres, float* dx_f32, int64_t dx_stride, void* dx_bf16,
+                            float* dgamma, float* dbeta, float* dx_colsum, const float* branch_scale, int32_t rows,
+                            int32_t width, float eps, int32_t side_cus, void* stream);
+/* the split count of that launch for a weight gradient over `rows` rows with `tiles` 256 x 256 output tiles when `side_cus` compute
+ * units are given to the side rows: the smallest count with tiles * splits a multiple of 256 - side_cus and >= 16 K steps of 64 rows
+ * in every split; 0 = no such count (host arithmetic) */
+int32_t uniir_gemm_wgrad_side_plan(int32_t rows, int32_t tiles, int32_t side_cus);
 
 /* ------------------------------------------------------------------------------------------------
  * [ENC] building block 3: fused multi-head attention, head_dim 64.
@@ -482,7 +498,18 @@ typedef struct {
     float *g_class, *g_pos, *g_ln_pre_w, *g_ln_pre_b, *g_token, *g_ln_post_w, *g_ln_post_b, *g_proj;
     void* splitk_ws;                          /* optional scratch for the weight-gradient GEMMs' split-K slabs */
     int64_t splitk_ws_bytes;
-    int32_t stash_act;                        /* with save_for_backward: 0 = the MLP's act(f) lives in one scratch buffer and the
+    int32_t ln_bwd_side;                      /* 1 = in uniir_clip_tower_bwd_blocks the backward of ln_2 runs inside the launch of
+                                                 the c_fc weight gradient and the backward of ln_1 inside that of the in_proj weight
+                                                 gradient (uniir_gemm_wgrad_ln_bwd: a few compute units stream the LayerNorm rows while the
+                                                 others feed the matrix pipes); each of the two activation-gradient GEMMs then runs before
+                                                 its layer's weight gradient.  Same activation gradients bit for bit; those two weight
+                                                 gradients are summed over more split-K slabs (needs splitk_ws: 7 x 4W x W and 13 x 3W x W
+                                                 floats at ViT-L/14 x 1024 images), the LayerNorm parameter gradients over other row
+                                                 groups -- other valid fp32 orders, the same bits in every run.  Pairs without a chunk
+                                                 plan or slab room run as the two launches they replace.  0 = the separate launches.
+                                                 This field sits in front of the four flags below, which stay the struct's last
+                                                 fields.  Any other value is UNIIR_EINVAL */
+    int32_t stash_act;                       /* with save_for_backward: 0 = the MLP's act(f) lives in one scratch buffer and the
                                                  backward re-materialises it from the stashed pre-activation f inside the c_proj dgrad
                                                  epilogue; 1 = act(f) is stashed per layer next to f (round 4: +2 bytes x rows x 4 width
                                                  per layer of workspace; that epilogue loses its second output: 3.31 -> 2.99 ms at ViT-L/14 x

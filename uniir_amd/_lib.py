@@ -45,7 +45,7 @@ class ClipTower(C.Structure):
         ("token_emb", c_void_p), ("ln_post_w", c_void_p), ("ln_post_b", c_void_p), ("proj16", c_void_p),
         ("g_conv", c_void_p), ("g_class", c_void_p), ("g_pos", c_void_p), ("g_ln_pre_w", c_void_p), ("g_ln_pre_b", c_void_p),
         ("g_token", c_void_p), ("g_ln_post_w", c_void_p), ("g_ln_post_b", c_void_p), ("g_proj", c_void_p),
-        ("splitk_ws", c_void_p), ("splitk_ws_bytes", c_i64),
+        ("splitk_ws", c_void_p), ("splitk_ws_bytes", c_i64), ("ln_bwd_side", c_int),
         ("stash_act", c_int), ("dtype16", c_int), ("pool_last_block", c_int),
         ("recompute", c_int),
     ]
@@ -102,6 +102,9 @@ SIGNATURES = {
     "uniir_reduce_stats": (c_int, [C.POINTER(c_i64), C.POINTER(c_i64), c_int]),
     "uniir_gemm": (c_int, [C.POINTER(GemmDesc), S]),
     "uniir_gemm_wgrad_splits": (c_int, [c_int, c_int]),
+    "uniir_gemm_wgrad_side_plan": (c_int, [c_int, c_int, c_int]),
+    "uniir_gemm_wgrad_ln_bwd": (c_int, [C.POINTER(GemmDesc), P, c_i64, P, P, c_int, P, P, c_i64, P, P, P, P, P, c_int, c_int, c_float,
+                                        c_int, S]),
     "uniir_gemm_timing": (c_int, [c_int]),
     "uniir_gemm_timing_on": (c_int, [c_int, c_void_p]),
     "uniir_gemm_timing_read": (c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(c_int)]),

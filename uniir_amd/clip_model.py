@@ -175,6 +175,11 @@ class CLIP(nn.Module):
         # backward kernel), so it is off by default: UNIIR_POOL_LAST_BLOCK_LONG=1 switches it on at construction.  Without
         # pool_last_block it does nothing; at 512 tokens and below it changes nothing.  Must be the same on every rank.
         self.pool_last_block_long = env_flag("UNIIR_POOL_LAST_BLOCK_LONG")
+        # The backward of ln_2 / ln_1 inside the launch of the c_fc / in_proj weight gradient (uniir_clip_tower.ln_bwd_side,
+        # csrc/gemm.hip gemm_wgrad_side_kernel): the LayerNorm rows stream through a few compute units while the others feed the matrix
+        # pipes.  Same activation gradients bit for bit; the two weight gradients and the LayerNorm parameter gradients are other
+        # fixed-order fp32 sums.  UNIIR_LN_BWD_SIDE=0 runs the separate launches (A/B, tests).  Must be the same on every rank.
+        self.ln_bwd_side = os.environ.get("UNIIR_LN_BWD_SIDE", "1") != "0"
         # Activation recomputation in the C towers (uniir_clip_tower.recompute, csrc/tower.hip): the training forward keeps only the
         # fp32 residual stream that enters each block (4 of the 28 - 36 stashed bytes per row x width element per layer) and the
         # backward rebuilds each block's intermediates from it, with the forward's own launches, right before that block's backward.
@@ -337,7 +342,8 @@ class CLIP(nn.Module):
         t.is_text, t.layers, t.width, t.embed_dim = int(not image), L, W, cfg["embed_dim"]
         t.blocks = C.cast(blocks, C.POINTER(ClipBlock))
         # split-K slabs: one scratch buffer PER TOWER (the two towers may run on two streams at the same time)
-        skw = ops._splitk_workspace(st.dev, 128 << 20, tag=which)
+        # (ln_bwd_side: the c_fc gradient beside ln_2's backward is 13 slabs of 4W x W floats -- 218 MB at W = 1024)
+        skw = ops._splitk_workspace(st.dev, max(128 << 20, 4 * 13 * 4 * W * W if self.ln_bwd_side else 0), tag=which)
         t.splitk_ws, t.splitk_ws_bytes = skw.data_ptr(), skw.numel()
         if image:
             P = cfg["vision_patch_size"]
@@ -692,6 +698,7 @@ class _TowerFn(torch.autograd.Function):
         desc.stash_act = st["stash_act"]        # part of the workspace layout: the value the forward ran with
         desc.pool_last_block = st["pool_last"]
         desc.recompute = st["recompute"]
+        desc.ln_bwd_side = int(bool(model.ln_bwd_side))      # (not part of the workspace layout)
         ws, inp, stream = st["ws"], st["inp"], ops._stream()
         demb = demb.contiguous().float()
         need = ws.numel()

@@ -18,4 +18,6 @@ extern "C" const char* uniir_strerror(int code) {
 // 5: new entry points uniir_image_batch_plan, uniir_image_preprocess_batch (uniir_image_desc / _plan / _batch_info)
 // 6: new entry points uniir_attention_fwd_long, uniir_attention_bwd_long
 // 7: new entry points uniir_attn_rel_fwd_f16, uniir_attn_rel_fwd_long_f16, uniir_rmsnorm_fwd_f16; still 7: uniir_attn_f32_rel_fwd
+// still 7: uniir_clip_tower grew ln_bwd_side (after splitk_ws_bytes, in front of the flags that end the struct); new entry points
+// uniir_gemm_wgrad_ln_bwd, uniir_gemm_wgrad_side_plan -- a binding of this header fails to load an older library on those symbols
 extern "C" int uniir_abi_version(void) { return 7; }

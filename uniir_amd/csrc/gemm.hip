@@ -4,6 +4,7 @@
 #include "gemm_core.h"
 #include "gemm_core256.h"
 #include "gemm_core_pp.h"
+#include "ln_row.h"
 #include "../../include/uniir_hip.h"
 #include "timing_filter.h"
 #include <stdlib.h>
@@ -809,6 +810,58 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
 }
 
+// ---- a weight gradient with LayerNorm-backward side rows (uniir_gemm_wgrad_ln_bwd) ------------------------------------------------
+// One launch of one workgroup per compute unit with two roles, a function of blockIdx alone:
+//   [0, G)        the bf16 product dW = A^T B (both operands K-major) of gemm_glds_kernel<.., 2 / 3>: workgroup b owns the `per_wg`
+//                 chunks c * G + xcd_remap(b, G), c < per_wg; chunk id = (split, tile) exactly as a split-K launch numbers its blocks,
+//                 and writes that block's fp32 slab -- splitk_reduce_kernel adds the slabs in K order afterwards, as after any split
+//   [G, gridDim)  rows of a LayerNorm backward (ln_row.h), one row per wave in a fixed assignment, column partials per workgroup
+// The product is bound by the matrix pipes and barely uses HBM, the LayerNorm is bound by HBM and uses no matrix pipe, and neither
+// depends on the other.  Two launches cannot share the chip that way: a 256 x 256 workgroup takes a CU's whole LDS and register file.
+// No workgroup waits for another one, so any subset of the grid may be resident at a time.
+struct SideLnArgs {
+    LnBwdArgs ln;
+    float *dgamma, *dbeta, *dx_colsum, *part;
+    int nc;          // width = 256 * nc, nc in {2, 3, 4}
+};
+template <bool ROWSUM>
+__global__ __launch_bounds__(512, 2) void gemm_wgrad_side_kernel(GemmKArgs p, SideLnArgs s, int G, int per_wg) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    if ((int)blockIdx.x >= G) {
+        const int sb = blockIdx.x - G, nsb = gridDim.x - G;
+        if (s.nc == 4) ln_bwd_side_rows<4>(s.ln, sb, nsb, (float*)lds, s.part, s.dgamma, s.dbeta, s.dx_colsum);
+        else if (s.nc == 3) ln_bwd_side_rows<3>(s.ln, sb, nsb, (float*)lds, s.part, s.dgamma, s.dbeta, s.dx_colsum);
+        else ln_bwd_side_rows<2>(s.ln, sb, nsb, (float*)lds, s.part, s.dgamma, s.dbeta, s.dx_colsum);
+        return;
+    }
+    const int tiles = p.tiles_m * p.tiles_n;
+    const int ksteps = p.K / 64, per = (ksteps + p.k_splits - 1) / p.k_splits;
+    const int b = xcd_remap(blockIdx.x, G);
+    for (int c = 0; c < per_wg; ++c) {
+        if (c) __syncthreads();           // the copy-out of the previous chunk has read the LDS image this chunk's prologue overwrites
+        int id = c * G + b;
+        const int split = id / tiles;
+        id -= split * tiles;
+        const int mt = id / p.tiles_n, nt = id - mt * p.tiles_n;
+        const int m0 = mt * 256, n0 = nt * 256;
+        const int kbeg = split * per * 64, kend = min(p.K, (split + 1) * per * 64);
+        f32x4_t acc[8][4];
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        glds_mainloop_pp<ElemBF16, true, true, ROWSUM>(p.A, p.lda, p.M, p.B, p.ldb, p.N, m0, n0, kbeg, kend, lds, acc,
+                                                       (ROWSUM && p.rowsum_part) ? p.rowsum_part + (long)(split * p.tiles_n + nt) * p.M
+                                                                                 : p.a_rowsum,
+                                                       nt, p.tiles_n, ROWSUM && p.rowsum_part != nullptr);
+        GemmKArgs q = p;
+        q.C = p.slab + (long)split * p.M * p.N;
+        q.ldc = p.N;
+        q.bias = nullptr;
+        epilogue256_staged<true, false>(q, acc, m0, n0, 0, 0, lds, UNIIR_EPI_F32);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ the host side
 // uniir_gemm = gemm_check (every refusal) -> head + tail split (P6) -> gemm_plan (every dispatch decision, each made once) ->
 // gemm_run (the launches, which only read the plan).  DESIGN.md section 3 has the table of the paths.
@@ -1227,4 +1280,99 @@ extern "C" int uniir_gemm(const uniir_gemm_desc* d, void* stream) {
         g_gt.n = i + 1;
     }
     return rc;
+}
+
+// ---- uniir_gemm_wgrad_ln_bwd: a weight gradient and an independent LayerNorm backward in one launch (gemm_wgrad_side_kernel) --------
+// The chunk arithmetic of that launch.  `side_cus` of the 256 compute units run LayerNorm rows, G = 256 - side_cus the product; the
+// product's `tiles` output tiles are cut into `splits` K ranges each (the split-K rule of uniir_gemm: ceil(K steps / splits) steps per
+// range), and every product workgroup owns tiles * splits / G chunks.  Returns the smallest `splits` with
+//   tiles * splits a multiple of G   (every product workgroup does the same work: no tail round),
+//   >= 16 K steps of 64 rows in every range, the last one included,
+// or 0 when there is none (the caller then runs the two launches one after the other).  Whether the slab workspace holds
+// `splits` slabs is the third condition; it needs the descriptor and is checked by uniir_gemm_wgrad_ln_bwd.  Pure arithmetic.
+extern "C" int32_t uniir_gemm_wgrad_side_plan(int32_t rows, int32_t tiles, int32_t side_cus) {
+    const int ncu = 256;
+    if (rows < 64 * 16 || tiles < 1 || side_cus < 1 || side_cus >= ncu) return 0;
+    const int G = ncu - side_cus, ksteps = rows / 64;
+    for (int s = 1; s <= 64 && s * 16 <= ksteps; ++s) {
+        if (((int64_t)tiles * s) % G) continue;
+        const int per = (ksteps + s - 1) / s;
+        if ((ksteps + per - 1) / per != s) continue;          // the rule would clamp s: a range would be empty
+        if (ksteps - per * (s - 1) < 16) continue;
+        return s;
+    }
+    return 0;
+}
+
+template <auto Kernel>
+static int side_launch(const GemmKArgs& a, const SideLnArgs& s, int G, int per_wg, hipStream_t st) {
+    static PerDeviceOnce attr_set;
+    if (attr_set.first()) (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Glds::LDS_BYTES);
+    hipLaunchKernelGGL(Kernel, dim3(256), dim3(Glds::T), Glds::LDS_BYTES, st, a, s, G, per_wg);
+    HIP_LAUNCH_CHECK();
+    return UNIIR_OK;
+}
+
+extern "C" int uniir_gemm_wgrad_ln_bwd(const uniir_gemm_desc* d, const float* x, int64_t x_stride, const float* gamma, const void* dy,
+                                       int32_t dy_is_f32, const float* dres, float* dx_f32, int64_t dx_stride, void* dx_bf16,
+                                       float* dgamma, float* dbeta, float* dx_colsum, const float* branch_scale, int32_t rows,
+                                       int32_t width, float eps, int32_t side_cus, void* stream) {
+    if (!d) return UNIIR_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    // the fused launch takes: a bf16 weight gradient of the 256-tile ping-pong kernel, accumulating, with a slab workspace; a LayerNorm
+    // of a production width (256 * NC) over bf16 dy.  Everything else -- and every refusal -- is the two entry points one after the other.
+    uniir_gemm_desc head = *d, tail;
+    const bool has_tail = gemm_head_tail(d, &head, &tail);
+    bool fused = d->a_tmaj && d->b_tmaj && d->dtype == UNIIR_DT_BF16 && d->epilogue == UNIIR_EPI_ATOMIC_F32 && d->M > 0 && d->N > 0 &&
+                 head.K > 0 && gemm_shape(d->M, d->N, head.K) == 1 && gemm_check(&head, 1) == UNIIR_OK && d->alpha == 1.0f &&
+                 !dy_is_f32 && rows > 0 && (width == 512 || width == 768 || width == 1024) && x && gamma && dy && dx_f32 && dgamma && dbeta &&
+                 !(x_stride % 4) && !(dx_stride % 4);
+    int splits = 0;
+    GemmPlan p = {};
+    if (fused) {
+        const int tiles = ((d->M + 255) / 256) * ((d->N + 255) / 256);
+        splits = uniir_gemm_wgrad_side_plan(head.K, tiles, side_cus);
+        head.k_splits = splits;
+        if (splits > 0) p = gemm_plan(&head, 1);      // splits, slabs and the row-sum side output as uniir_gemm plans them for this split count
+        fused = splits > 0 && p.splits == splits && p.slab && p.path >= GEMM_P3 && p.rowsum != SIDE_PASS;
+    }
+    if (!fused) {
+        const int rc = uniir_gemm(d, stream);
+        if (rc) return rc;
+        return uniir_layernorm_bwd_ex(x, x_stride, gamma, dy, dy_is_f32, dres, dx_f32, dx_stride, dx_bf16, dgamma, dbeta, dx_colsum,
+                                      branch_scale, rows, width, eps, stream);
+    }
+    const int G = 256 - side_cus;
+    GemmKArgs a = gemm_args(&head, p);
+    a.raster_gm = 0;
+    SideLnArgs s = {};
+    s.ln.x = x; s.ln.x_stride = x_stride; s.ln.gamma = gamma; s.ln.dy = dy; s.ln.dres = dres; s.ln.dx = dx_f32; s.ln.dx_stride = dx_stride;
+    s.ln.dx_bf16 = (unsigned short*)dx_bf16; s.ln.bscale = branch_scale; s.ln.rows = rows; s.ln.width = width; s.ln.eps = eps;
+    s.ln.rms = 0; s.ln.colsum = dx_colsum != nullptr;
+    s.dgamma = dgamma; s.dbeta = dbeta; s.dx_colsum = dx_colsum; s.nc = width / 256;
+    // ONE request of the stream's scratch: the side workgroups' column partials, then the product's row partials (a_rowsum)
+    const int64_t ln_bytes = ((int64_t)side_cus * 3 * width * 4 + 255) / 256 * 256;
+    float* part = reduce_scratch(st, ln_bytes + p.row_bytes);
+    if (part) {
+        s.part = part;
+        if (p.row_bytes) a.rowsum_part = (float*)((char*)part + ln_bytes);
+    }
+    int rc;
+    if (p.rowsum == SIDE_FUSED) rc = side_launch<gemm_wgrad_side_kernel<true>>(a, s, G, a.tiles_m * a.tiles_n * splits / G, st);
+    else rc = side_launch<gemm_wgrad_side_kernel<false>>(a, s, G, a.tiles_m * a.tiles_n * splits / G, st);
+    if (rc) return rc;
+    if (s.part) {
+        rc = reduce_partials(s.part, side_cus, 3L * width, width, dgamma, dbeta, dx_colsum, width, st);
+        if (rc) return rc;
+    }
+    if (a.rowsum_part) {
+        rc = reduce_partials(a.rowsum_part, splits * a.tiles_n, d->M, d->M, d->a_rowsum, nullptr, nullptr, 0, st);
+        if (rc) return rc;
+    }
+    const long mn = (long)d->M * d->N;
+    long g = (mn / 4 + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, st, a.slab, splits, mn, d->N, (float*)d->C, (long)d->ldc);
+    HIP_LAUNCH_CHECK();
+    return has_tail ? gemm_one(&tail, st) : UNIIR_OK;
 }

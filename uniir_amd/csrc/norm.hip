@@ -5,15 +5,8 @@
 #include "../../include/uniir_hip.h"
 
 #define LN_MAXC 8  // float4 chunks per lane -> width <= 64*4*8 = 2048 (kernels are instantiated for NC = 2,3,4,8)
-// the row operands are read exactly once per launch: nt policy (-DUNIIR_LN_NT=0 for the A/B build)
-#ifndef UNIIR_LN_NT
-#define UNIIR_LN_NT 0
-#endif
-#if UNIIR_LN_NT
-#define LN_LD(p) __builtin_nontemporal_load(p)
-#else
-#define LN_LD(p) (*(p))
-#endif
+// LN_LD (the nt policy of the row operands) and the backward's per-row body: ln_row.h
+#include "ln_row.h"
 
 template <int NC, bool EXACT>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, long x_stride,
@@ -100,91 +93,13 @@ __global__ __launch_bounds__(256, (EXACT && NC <= 4) ? 3 : 1) void ln_bwd_kernel
         ab[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         ac[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     }
-    for (long row = (long)blockIdx.x * 4 + w; row < rows; row += (long)gridDim.x * 4) {
-        const float* xr = x + row * x_stride;
-        f32x4_t v[NC], d[NC], rs[NC];
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NC; ++i) {
-            const int c = lane + 64 * i;
-            if (EXACT || c < nchunk) {
-                v[i] = LN_LD(reinterpret_cast<const f32x4_t*>(xr + 4 * c));
-                if (dres) rs[i] = LN_LD(reinterpret_cast<const f32x4_t*>(dres + row * dx_stride + 4 * c));
-                s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-                if (DY_F32) {
-                    d[i] = LN_LD(reinterpret_cast<const f32x4_t*>((const float*)dy_ + row * width + 4 * c));
-                } else {
-                    const u32x2_t pk =
-                        LN_LD(reinterpret_cast<const u32x2_t*>((const unsigned short*)dy_ + row * width + 4 * c));
-                    d[i] = f32x4_t{__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
-                                   __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
-                }
-            }
-        }
-        const float mean = rms ? 0.f : wave_sum(s) * inv_w;
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < NC; ++i) {
-            const int c = lane + 64 * i;
-            if (EXACT || c < nchunk) {
-                v[i] = v[i] - mean;
-                q += (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
-            }
-        }
-        const float rstd = rsqrtf(wave_sum(q) * inv_w + eps);
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < NC; ++i) {
-            const int c = lane + 64 * i;
-            if (EXACT || c < nchunk) {
-                v[i] = v[i] * rstd;  // xhat
-                const f32x4_t g = d[i] * *reinterpret_cast<const f32x4_t*>(gamma + 4 * c);
-                ag[i] += d[i] * v[i];
-                ab[i] += d[i];
-                d[i] = g;
-                s1 += (g[0] + g[1]) + (g[2] + g[3]);
-                s2 += (g[0] * v[i][0] + g[1] * v[i][1]) + (g[2] * v[i][2] + g[3] * v[i][3]);
-            }
-        }
-        const float c1 = rms ? 0.f : wave_sum(s1) * inv_w, c2 = wave_sum(s2) * inv_w;
-        // bscale: the row's DropPath factor of the residual BRANCH this gradient enters next (its last linear layer's bias
-        // gradient and 16-bit operand see bscale * dx; the fp32 residual gradient itself stays unscaled)
-        const float bs = bscale ? bscale[row] : 1.0f;
-#pragma unroll
-        for (int i = 0; i < NC; ++i) {
-            const int c = lane + 64 * i;
-            if (EXACT || c < nchunk) {
-                f32x4_t o = (d[i] - c1 - v[i] * c2) * rstd;
-                if (dres) o += rs[i];
-                *reinterpret_cast<f32x4_t*>(dx + row * dx_stride + 4 * c) = o;
-                if (bscale) o = o * bs;
-                if (dx_colsum) ac[i] += o;
-                if (dx_bf16) {
-                    u32x2_t pk = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
-                    *reinterpret_cast<u32x2_t*>(dx_bf16 + row * width + 4 * c) = pk;
-                }
-            }
-        }
-    }
-    // block reduction of the per-wave column partials, then one atomic per column per block
-    float* mine = &red[w][0];
-    for (int pass = 0; pass < (dx_colsum ? 3 : 2); ++pass) {
-        if (pass == 1 && rms) continue;      // no beta
-#pragma unroll
-        for (int i = 0; i < NC; ++i) {
-            const int c = lane + 64 * i;
-            if (EXACT || c < nchunk) *reinterpret_cast<f32x4_t*>(mine + 4 * c) = pass == 0 ? ag[i] : (pass == 1 ? ab[i] : ac[i]);
-        }
-        __syncthreads();
-        float* dst = pass == 0 ? dgamma : (pass == 1 ? dbeta : dx_colsum);
-        for (int col = threadIdx.x; col < width; col += 256) {
-            const float t = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
-            // part: this workgroup's three column partials [block][pass][width]; a fixed-order reduction follows (common.h)
-            if (part) part[((long)blockIdx.x * 3 + pass) * width + col] = t;
-            else unsafeAtomicAdd(dst + col, t);
-        }
-        __syncthreads();
-    }
+    for (long row = (long)blockIdx.x * 4 + w; row < rows; row += (long)gridDim.x * 4)
+        ln_bwd_row<NC, DY_F32, EXACT>(x, x_stride, gamma, dy_, dres, dx, dx_stride, dx_bf16, dx_colsum, width, eps, rms, bscale, row, lane,
+                                      nchunk, inv_w, ag, ab, ac);
+    // block reduction of the per-wave column partials, then one partial (or one atomic) per column per block
+    LnBwdArgs a = {};
+    a.width = width; a.rms = rms; a.colsum = dx_colsum != nullptr;
+    ln_bwd_col_partials<NC, EXACT, 4>(a, &red[0][0], lane, w, blockIdx.x, part, dgamma, dbeta, dx_colsum, ag, ab, ac);
 }
 
 template <int NC>

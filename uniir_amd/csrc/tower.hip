@@ -133,6 +133,7 @@ int check_tower(const uniir_clip_tower* t, int batch) {
     if (!t || !t->blocks || batch < 0) return UNIIR_EINVAL;
     if (t->layers <= 0 || t->width <= 0 || t->heads <= 0 || t->tokens < 2 || t->embed_dim <= 0) return UNIIR_EINVAL;
     if (t->recompute != 0 && t->recompute != 1) return UNIIR_EINVAL;
+    if (t->ln_bwd_side != 0 && t->ln_bwd_side != 1) return UNIIR_EINVAL;
     // (a vision tower's plain attention streams up to 1024 tokens, attention_long.hip; the causal / packed text forms hold a head in LDS)
     if (t->width != t->heads * 64 || t->width % 64 || t->embed_dim % 8) return UNIIR_ESHAPE;
     if (t->tokens > (t->is_text ? ATT_SEQ_MAX : ATT_LONG_SEQ_MAX)) return UNIIR_ESHAPE;
@@ -147,6 +148,13 @@ int check_tower(const uniir_clip_tower* t, int batch) {
     }
     return UNIIR_OK;
 }
+
+// compute units given to the LayerNorm rows of a fused pair (uniir_clip_tower.ln_bwd_side), chosen from the step times measured at
+// ViT-L/14 x 1024 images over every count that has a chunk plan (profiles/r07_wgrad_ln_side.txt): c_fc's 4W x W gradient (64 tiles)
+// runs as 13 slabs on 208 units, in_proj's 3W x W (48 tiles) as 4 slabs on 192.  The side rows sustain 46 - 50 GB/s per unit, so
+// fewer units than these leave the LayerNorm rows running alone behind the product.  Shapes without a plan at these values run the
+// two launches (uniir_gemm_wgrad_side_plan).
+constexpr int SIDE_CUS_FC = 48, SIDE_CUS_QKV = 64;
 
 #define TRY(call)                 \
     do {                          \
@@ -192,8 +200,18 @@ int linear_dgrad(const void* dy, const void* w, void* out, int M, int N, int K, 
 // dbias (optional): += column sums of dy, from the same pass over dy
 // The slab workspace is offered only when it holds the split count ASKED for, which is stricter than uniir_gemm's own rule when the
 // library clamps the splits (520 K steps at 32 splits run as 31): such products keep their atomics.
+// ln (uniir_clip_tower.ln_bwd_side): a LayerNorm backward that depends on nothing this product writes and writes nothing it reads,
+// run by ln->side_cus compute units of the SAME launch (uniir_gemm_wgrad_ln_bwd: the product is bound by the matrix pipes, the LayerNorm
+// by HBM).  That entry point decides by itself whether the pair runs as one launch or as the two it replaces.
+struct SideLn {
+    const float *x, *gamma, *dres;
+    const void* dy;
+    float *dx, *dgamma, *dbeta, *dx_colsum;
+    void* dxb;
+    int rows, width, side_cus;
+};
 int linear_wgrad(const uniir_clip_tower* t, const void* dy, const void* x, float* dw, int M, int N, int K, void* st,
-                 float* dbias = nullptr, int64_t lddy = 0) {
+                 float* dbias = nullptr, int64_t lddy = 0, const SideLn* ln = nullptr) {
     uniir_gemm_desc d;
     base_desc(d);
     d.A = dy; d.B = x; d.C = dw; d.a_rowsum = dbias;
@@ -204,7 +222,16 @@ int linear_wgrad(const uniir_clip_tower* t, const void* dy, const void* x, float
         d.splitk_ws = t->splitk_ws;
         d.splitk_ws_bytes = t->splitk_ws_bytes;
     }
-    return uniir_gemm(&d, st);
+    if (ln && t->splitk_ws) {      // the side launch has its own (larger) slab count; where it has none the descriptor stays as above
+        const int s = uniir_gemm_wgrad_side_plan(M, ((N + 255) / 256) * ((K + 255) / 256), ln->side_cus);
+        if (s > 0 && t->splitk_ws_bytes >= (int64_t)4 * s * N * K) {
+            d.splitk_ws = t->splitk_ws;
+            d.splitk_ws_bytes = t->splitk_ws_bytes;
+        }
+    }
+    if (!ln) return uniir_gemm(&d, st);
+    return uniir_gemm_wgrad_ln_bwd(&d, ln->x, ln->width, ln->gamma, ln->dy, 0, ln->dres, ln->dx, ln->width, ln->dxb, ln->dgamma, ln->dbeta,
+                                   ln->dx_colsum, nullptr, ln->rows, ln->width, 1e-5f, ln->side_cus, st);
 }
 
 struct Lay {
@@ -509,17 +536,32 @@ int tower_bwd_blocks(const uniir_clip_tower* t, int32_t batch, const int32_t* ro
         // (stash_act: l.g holds act(f) since the forward -- the epilogue writes no second output)
         TRY(linear_dgrad(dxb, b.wproj16, df, R, W, 4 * W, l.f, p.stash_act ? nullptr : g, b.g_bfc, stream));
         TRY(linear_wgrad(t, dxb, p.stash_act ? l.g : g, b.g_wproj, R, W, 4 * W, stream));
-        TRY(linear_wgrad(t, df, l.h2, b.g_wfc, R, 4 * W, W, stream));
-        TRY(linear_dgrad(df, b.wfc16, dh, R, 4 * W, W, nullptr, nullptr, nullptr, stream));            // d ln_2 out
-        TRY(uniir_layernorm_bwd(l.x2, W, b.ln2_w, dh, 0, dx, dx2, W, dxb, b.g_ln2_w, b.g_ln2_b, b.g_bo, R, W, 1e-5f, stream));
+        if (t->ln_bwd_side) {
+            // the two LayerNorm backwards ride the weight gradient that is due next to them: dW_fc (reads df, h2) beside ln_2's backward
+            // (reads x2, dh, dx; writes dx2, dxb), dW_qkv (reads dqkv, h1) beside ln_1's (reads x, dh, dx2; writes dx, dxb).  Each
+            // activation-gradient GEMM therefore runs BEFORE the weight gradient of its layer here; no buffer of a pair is shared.
+            TRY(linear_dgrad(df, b.wfc16, dh, R, 4 * W, W, nullptr, nullptr, nullptr, stream));        // d ln_2 out
+            const SideLn ln2 = {l.x2, b.ln2_w, dx, dh, dx2, b.g_ln2_w, b.g_ln2_b, b.g_bo, dxb, R, W, SIDE_CUS_FC};
+            TRY(linear_wgrad(t, df, l.h2, b.g_wfc, R, 4 * W, W, stream, nullptr, 0, &ln2));
+        } else {
+            TRY(linear_wgrad(t, df, l.h2, b.g_wfc, R, 4 * W, W, stream));
+            TRY(linear_dgrad(df, b.wfc16, dh, R, 4 * W, W, nullptr, nullptr, nullptr, stream));        // d ln_2 out
+            TRY(uniir_layernorm_bwd(l.x2, W, b.ln2_w, dh, 0, dx, dx2, W, dxb, b.g_ln2_w, b.g_ln2_b, b.g_bo, R, W, 1e-5f, stream));
+        }
         TRY(linear_wgrad(t, dxb, l.ao, b.g_wo, R, W, W, stream));
         TRY(linear_dgrad(dxb, b.wo16, dh, R, W, W, nullptr, nullptr, nullptr, stream));                // d attention out
         if (row_off) TRY(uniir_attention_bwd_packed(l.qkv, l.ao, dh, l.lse, dqkv, row_off, p.M, p.T, p.H, t->is_text ? 1 : 0, stream));
         else TRY(uniir_attention_bwd(l.qkv, l.ao, dh, l.lse, dqkv, p.M, p.T, p.H, t->is_text ? 1 : 0, stream));
-        TRY(linear_wgrad(t, dqkv, l.h1, b.g_wqkv, R, 3 * W, W, stream, b.g_bqkv));       // + the in_proj bias gradient
-        TRY(linear_dgrad(dqkv, b.wqkv16, dh, R, 3 * W, W, nullptr, nullptr, nullptr, stream));         // d ln_1 out
-        TRY(uniir_layernorm_bwd(l.x, W, b.ln1_w, dh, 0, dx2, dx, W, dxb, b.g_ln1_w, b.g_ln1_b,
-                                i > 0 ? t->blocks[i - 1].g_bproj : nullptr, R, W, 1e-5f, stream));
+        float* dbproj = i > 0 ? t->blocks[i - 1].g_bproj : nullptr;
+        if (t->ln_bwd_side) {
+            TRY(linear_dgrad(dqkv, b.wqkv16, dh, R, 3 * W, W, nullptr, nullptr, nullptr, stream));     // d ln_1 out
+            const SideLn ln1 = {l.x, b.ln1_w, dx2, dh, dx, b.g_ln1_w, b.g_ln1_b, dbproj, dxb, R, W, SIDE_CUS_QKV};
+            TRY(linear_wgrad(t, dqkv, l.h1, b.g_wqkv, R, 3 * W, W, stream, b.g_bqkv, 0, &ln1));        // + the in_proj bias gradient
+        } else {
+            TRY(linear_wgrad(t, dqkv, l.h1, b.g_wqkv, R, 3 * W, W, stream, b.g_bqkv));   // + the in_proj bias gradient
+            TRY(linear_dgrad(dqkv, b.wqkv16, dh, R, 3 * W, W, nullptr, nullptr, nullptr, stream));     // d ln_1 out
+            TRY(uniir_layernorm_bwd(l.x, W, b.ln1_w, dh, 0, dx2, dx, W, dxb, b.g_ln1_w, b.g_ln1_b, dbproj, R, W, 1e-5f, stream));
+        }
     }
     return UNIIR_OK;
 }
