@@ -823,6 +823,7 @@ int uniir_topk_rescore(const void* pool_f16, const float* pool_inv_norm, const i
  * k <= 56.  Candidates: behind the streaming / ping-pong scans every group whose maximum lies within the proven rounding bound of
  * the k-th best group maximum (GselBound, csrc/topk_select.h; at most 2 (k + 8) groups), not the fixed k + 8 groups of
  * uniir_topk_coarse -- the results are those of the exhaustive search either way (MASS TIES above excepted), bit for bit.
+ * Which kernels a shape gets: the table of DESIGN.md "Top-k host layer"; uniir_topk_plan below answers for one shape.
  * rows * dim * 2 must stay below 2 GiB (UNIIR_ESHAPE otherwise: the shard is addressed through 31-bit buffer offsets); a larger
  * resident shard -- the whole 5.6 M x 768 M-BEIR pool on one GPU -- is searched as equal row ranges and merged with
  * uniir_topk_merge (uniir_amd/retrieval.py subshard_bounds), which is the search of the whole shard.
@@ -847,6 +848,43 @@ int uniir_topk_ip_multi(const void* pool_f16, const float* pool_inv_norm, const 
  * small inputs, and for tuning.  Process-wide host setting.  uniir_topk_ip_sweep_queries: the value a search of this shape uses. */
 int uniir_topk_set_chunk(int32_t queries_per_sweep);
 int32_t uniir_topk_ip_sweep_queries(int32_t dim, int64_t rows);
+/* What a uniir_topk_ip / uniir_topk_ip_multi search of (rows, dim, nq, k) launches on a device with ncu compute units, and the
+ * scratch it uses: the library's own plan (csrc/topk.h TkPlan; the dispatch table it implements is DESIGN.md "Top-k host layer"),
+ * read-only, no device needed.  New entry point only, found by its symbol.  A search runs full sweeps of sweep_queries queries and,
+ * when nq is no multiple, one remainder sweep of rem_queries (0: none); a shard of >= 2 GiB runs them per sub-shard (the fields
+ * then describe a FULL sub-shard; ask again with last_rows for the shorter last one) or, batched == 1, with one tail, one sort and
+ * one merge launch per sweep for all sub-shards.  UNIIR_EINVAL: null / non-positive argument; UNIIR_ESHAPE: k > 56, dim % 64,
+ * rows >= 2^31 (what the searches refuse). */
+enum {                              /* scan: the group-max scan of a sweep */
+    UNIIR_TK_SCAN_STREAM = 0,       /* topk_stream_kernel<dim / 32>: <= 64 queries in LDS, dim 768 | 512, small shards */
+    UNIIR_TK_SCAN_STREAM2 = 1,      /* topk_stream2_kernel<dim / 32, 2>: <= 64 queries in registers, >= 2048 groups */
+    UNIIR_TK_SCAN_SHARED2 = 2,      /* topk_stream5_kernel<2, 2>: 65 .. 128 queries, dim 768, >= 2048 groups */
+    UNIIR_TK_SCAN_SHARED4 = 3,      /* topk_stream5_kernel<4, 2>: 129 .. 256 */
+    UNIIR_TK_SCAN_PP_HALF = 4,      /* topk_gmax_pp_kernel<true, 2>: 65 .. 128 queries, dim % 64 == 0, dim >= 192 */
+    UNIIR_TK_SCAN_PP_NT = 5,        /* topk_gmax_pp_kernel<false, 2>: 129 .. 256 */
+    UNIIR_TK_SCAN_PP = 6,           /* topk_gmax_pp_kernel<false, 0>: 257 .. 1024 */
+    UNIIR_TK_SCAN_GMAX = 7,         /* topk_gmax_kernel<2>: everything else */
+    UNIIR_TK_SCAN_COARSE = 8        /* topk_coarse_kernel: uniir_topk_coarse with more than 1024 queries (never inside a search) */
+};
+enum { UNIIR_TK_TAIL_UNFUSED = 0,   /* tail: stand-alone selection (select = UNIIR_TK_SEL_*), query norms, uniir_topk_rescore */
+       UNIIR_TK_TAIL_FUSED = 1 };   /* topk_tail_select_rescore_kernel<select, ..> (select = 4 | 2 | 1 workgroups per query) + sort */
+enum {
+    UNIIR_TK_SEL_1024_REG = 0,      /* topk_gsel_kernel<1024, true>: an even number of groups, <= 49 152 */
+    UNIIR_TK_SEL_1024 = 1,          /* topk_gsel_kernel<1024, false>: <= 64 queries */
+    UNIIR_TK_SEL_256 = 2,           /* topk_gsel_kernel<256> */
+    UNIIR_TK_SEL_MERGE_PARTIAL = 3  /* topk_merge_partial_kernel, behind UNIIR_TK_SCAN_COARSE */
+};
+typedef struct {
+    int64_t scan, waves, tail, select;                                  /* a full sweep; waves: wave maxima written by the scan (0: none) */
+    int64_t rem_queries, rem_scan, rem_waves, rem_tail, rem_select;     /* the remainder sweep */
+    int64_t sweep_queries, ncand;                                       /* ncand: shortlist entries per query */
+    int64_t nsub, batched, subshard_rows, last_rows;
+    int64_t workspace_bytes;                                            /* = uniir_topk_ip_multi_workspace_bytes */
+    /* regions (batched: of all sub-shards): group [+ wave] maxima, wave maxima where they have a region of their own, query
+     * inverse norms, candidate rows, exact scores, the sub-shards' k-lists (scores and ids) */
+    int64_t gmax_bytes, wmax_bytes, qinv_bytes, cand_bytes, exact_bytes, lists_bytes;
+} uniir_topk_plan_t;
+int uniir_topk_plan(int64_t rows, int32_t dim, int32_t nq, int32_t k, int32_t ncu, uniir_topk_plan_t* out);
 /* The same search over an fp32 pool (an extraction with use_fp16 = False kept as fp32 rows: UNIIR_POOL_FP32).  New entry points only,
  * found by their symbols.  The arithmetic is that of uniir_topk_ip with fp32 inputs where it converts fp16 to fp32: inverse norms
  * (float)(1.0 / (double)sqrtf(s)), s the sequential fp32 sum of squares without fma, 0 when s is not > 0; query and row elements

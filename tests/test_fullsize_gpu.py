@@ -365,6 +365,8 @@ def test_topk_ip_multi_equals_the_merge_of_sub_shard_searches(n, d):
     odd number of 16-row groups, which the batched tail does not take: the entry point's per-sub-shard fallback loop runs instead.
     2.2 M x 512 (the CLIP base models' width, 3 sub-shards): batched at 64 queries, the fallback loop at 300 (no shared-ring scan at
     this width)."""
+    from torch.profiler import ProfilerActivity, profile
+    import topk_cases as T
     from uniir_amd import _lib, retrieval
     k = 10
     lib = _lib.load()
@@ -386,7 +388,20 @@ def test_topk_ip_multi_equals_the_merge_of_sub_shard_searches(n, d):
         where = torch.randperm(n, device=DEV, generator=g)[:nq]
         pool[where] = (queries.float() * 2.0).half()
         shard = retrieval.PoolShard(pool, ids)
-        s, i = retrieval.search_shard(shard, queries, k)
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            s, i = retrieval.search_shard(shard, queries, k)
+            torch.cuda.synchronize()
+        seen = [e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+        tails = sum("topk_tail_select_rescore_kernel" in x or "topk_gsel_kernel" in x for x in seen)     # fused | stand-alone selection
+        merges = sum("merge_rank_kernel" in x or "merge_shards_kernel" in x for x in seen)
+        sweeps = -(-nq // min(nq, T.sweep_queries(d, per)))
+        batched = T.multi_batched(n, d, nq, k)
+        print(f"LAUNCHES {n}x{d} nq={nq} batched={batched} sweeps={sweeps} tails={tails} merges={merges}")
+        assert batched == ((n, d, nq) in ((1_500_032, 768, 64), (1_500_032, 768, 300), (2_200_000, 512, 64)))
+        if tails:               # (a profiler that records nothing checks nothing, as in test_topk_paths_gpu.py)
+            # batched: ONE tail and one merge launch per sweep for all sub-shards; the loop: a tail per sub-shard and sweep, one merge
+            assert (tails, merges) == ((sweeps, sweeps) if batched else (sweeps * len(bounds), 1)), (nq, tails, merges)
         parts = [retrieval.search_shard(retrieval._shard_view(shard, lo, hi), queries, k) for lo, hi in bounds]
         ms, mi = retrieval.merge_shards(torch.stack([p[0] for p in parts]), torch.stack([p[1] for p in parts]))
         assert torch.equal(s, ms) and torch.equal(i, mi), nq

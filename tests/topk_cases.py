@@ -2,8 +2,13 @@
 restatement of the host dispatch of csrc/topk.hip and csrc/topk_tail.hip, the cases with the kernel instantiations each is meant to
 reach, the numpy generators of their inputs and the references.
 
+The authoritative dispatch table is DESIGN.md "Top-k host layer" (the library's tk_plan implements it); what follows is this
+module's own restatement, line for line the rows of that table, which tests/test_topk_refusals_host.py compares with the library's
+plan (uniir_topk_plan) for every case here and for shapes too large to run.  It is kept independent on purpose: nothing below
+calls the library.
+
 Dispatch restated (one sweep of n <= 1024 queries; ngroups = ceil(rows / 16), kc = k + 8, gcap = 2 kc):
-  scan  launch_gmax_scan     n <= 64, dim 768 | 512, rows * dim * 2 < 2^31, ngroups >= 2048   topk_stream2_kernel<dim / 32,2>
+  scan  tk_plan_sweep        n <= 64, dim 768 | 512, rows * dim * 2 < 2^31, ngroups >= 2048   topk_stream2_kernel<dim / 32,2>
                              n <= 64, dim 768 | 512 otherwise                                 topk_stream_kernel<dim / 32>
                              stream_shared_ok: 65 .. 256, dim 768, ngroups >= 2048            topk_stream5_kernel<2 | 4,2> (<= 128 | more)
                              n > 64, dim % 64 == 0, dim >= 192                                topk_gmax_pp_kernel<n <= 128, 2 | 2 | 0>
@@ -12,11 +17,15 @@ Dispatch restated (one sweep of n <= 1024 queries; ngroups = ceil(rows / 16), kc
   tail  fused_tail_ok: dim % 64 == 0, dim <= 4096, ngroups even and <= 49152, gcap * 16 <= 2048, behind every scan but the last:
                              topk_tail_select_rescore_kernel<4,3,4 | 2,5,2 | 1,5,2> (n <= 64 | <= 128 | more) + topk_tail_sort_kernel,
                              selection gsel_hier on the wave maxima where the scan left them, else gsel_body<1024,true>
-        otherwise topk_select_after_scan: topk_gsel_kernel<1024,true> (ngroups even, <= 49152), <1024,false> (n <= 64), <256>;
+        otherwise launch_select: topk_gsel_kernel<1024,true> (ngroups even, <= 49152), <1024,false> (n <= 64), <256>;
                              uniir_topk_rescore: rescore_coalesced_kernel (dim % 64 == 0) | rescore_kernel, final_sort_kernel by
                              ncand = 32 kc: rank count (<= 1024), registers (<= 2048), re-read loop (more)
   uniir_topk_coarse with more than 1024 queries: topk_coarse_kernel + topk_merge_partial_kernel, ncand = kc
   launch_merge: merge_rank_kernel up to 4096 entries per query, merge_shards_kernel above
+  uniir_topk_ip_multi (rows * dim * 2 >= 2^31): equal sub-shards on 32-row boundaries (subshard_rows); batched (multi_batched: one
+                             tail, sort and merge launch per sweep for all sub-shards, multi_sweep_path) when every sub-shard, the
+                             shorter last one included, is on a register streaming scan and the fused tail in sweeps of <= 256
+                             queries and there are <= 64 of them; else one uniir_topk_ip search per sub-shard and one merge
 Two branches are taken by the DATA, not the shape; the cases that force them name them as well:
   "gsel_hier bail-out"        more than 128 candidate waves or 1024 groups reach the threshold: gsel_body runs instead
   "gsel_body extraction loop" more than 1024 groups reach the threshold: one extraction per round
@@ -94,7 +103,7 @@ def wave_maxima(ngroups, ncu):
 
 
 def scan_path(rows, dim, n, ncu):
-    """launch_gmax_scan -> (kernel, its return value, per-wave maxima written)"""
+    """the scan of a sweep -> (kernel, 1 where a 1024-thread selection or the fused tail may follow else 0, per-wave maxima written)"""
     ng = cdiv(rows, TK_G)
     big = dim in (768, 512) and rows * dim * 2 < 2 ** 31 and ng >= 2048
     if n <= 64 and big:
@@ -115,8 +124,74 @@ def fused_tail_ok(rows, dim, kc):
     return rows * dim * 2 < 2 ** 31
 
 
+# uniir_topk_ip_multi: a resident shard of >= 2 GiB as equal logical sub-shards
+def subshard_rows(rows, dim):
+    """uniir_topk_subshard_rows"""
+    if rows <= 0 or dim <= 0:
+        return 0
+    if rows * dim * 2 < 2 ** 31:
+        return rows
+    cap = min(((2 ** 31 - 1) // (dim * 2)) // 32 * 32, 1024 * 2 * TK_SELREG * TK_G)
+    return cdiv(cdiv(rows, cdiv(rows, cap)), 32) * 32
+
+
+def subshards(rows, dim):
+    """-> (rows of a full sub-shard, sub-shards, rows of the last one)"""
+    per = subshard_rows(rows, dim)
+    nsub = cdiv(rows, per)
+    return per, nsub, rows - (nsub - 1) * per
+
+
+def align256(x):
+    return (x + 255) // 256 * 256
+
+
+def multi_workspace_bytes(nq, k, rows, dim, chunk=0):
+    """uniir_topk_ip_multi_workspace_bytes: the larger of the batched layout (per sub-shard: group maxima, wave maxima, candidates,
+    exact scores, two k-lists of a sweep) and the per-sub-shard loop's (one uniir_topk_ip workspace + two k-lists of ALL queries per
+    sub-shard)"""
+    if nq <= 0 or k <= 0 or rows <= 0 or dim <= 0:
+        return 0
+    if rows * dim * 2 < 2 ** 31:
+        return ip_workspace_bytes(nq, k, rows, dim, chunk)
+    per, nsub, _ = subshards(rows, dim)
+    c = min(nq, sweep_queries(dim, per, chunk))
+    g = align256(c * cdiv(per, TK_G) * 4)
+    w = align256(max(c if c <= 256 else 64, 64) * 1024 * 4 + 256)
+    cb = align256(c * ncand(c, k + 8) * 4)
+    o = align256(c * k * 8)
+    batched = nsub * (g + w + 2 * cb + 2 * o)
+    loop = align256(ip_workspace_bytes(nq, k, per, dim, chunk)) + 2 * nsub * align256(nq * k * 8)
+    return max(batched, loop) + 256
+
+
+def multi_batched(rows, dim, nq, k, chunk=0):
+    """does uniir_topk_ip_multi run ONE tail, sort and merge launch per sweep for all sub-shards (else: one uniir_topk_ip per
+    sub-shard, one merge)?  Every sub-shard on a register streaming scan and the fused tail, sweeps of <= 256 queries, <= 64 sub-shards"""
+    if rows * dim * 2 < 2 ** 31:
+        return False
+    per, nsub, last = subshards(rows, dim)
+    c = min(nq, sweep_queries(dim, per, chunk))
+    lg = cdiv(last, TK_G)
+    return (dim in (768, 512) and lg >= 2048 and lg % 2 == 0 and c <= 256 and nsub <= 64
+            and (c <= 64 or (stream_shared_ok(dim, per, c) and stream_shared_ok(dim, last, c)))
+            and fused_tail_ok(per, dim, k + 8) and fused_tail_ok(last, dim, k + 8))
+
+
+def multi_sweep_path(rows, dim, n, k, ncu):
+    """one BATCHED sweep of n queries: the scan of every sub-shard, then one tail for all of them (a workgroup per query, part and
+    sub-shard; the hierarchical selection only where every sub-shard's scan leaves wave maxima), one sort, one merge"""
+    per, nsub, last = subshards(rows, dim)
+    scan, _, _ = scan_path(per, dim, n, ncu)
+    assert scan == scan_path(last, dim, n, ncu)[0]
+    wm = wave_maxima(cdiv(per, TK_G), ncu) and wave_maxima(cdiv(last, TK_G), ncu)
+    parts = "4,3,4" if n * nsub <= 64 else "2,5,2" if n * nsub <= 128 else "1,5,2"
+    return (scan, f"topk_tail_select_rescore_kernel<{parts}>", "gsel_hier" if wm else "gsel_body<1024,true>", "topk_tail_sort_kernel",
+            "merge_rank_kernel" if nsub * k <= MERGE_CAP else "merge_shards_kernel")
+
+
 def select_path(sel, rows, n):
-    """topk_select_after_scan"""
+    """the stand-alone selection behind a scan (sel: scan_path's second value)"""
     ng = cdiv(rows, TK_G)
     if sel == 1 and ng % 2 == 0 and ng <= 1024 * 2 * TK_SELREG:
         return "topk_gsel_kernel<1024,true>"

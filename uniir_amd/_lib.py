@@ -241,7 +241,23 @@ SIGNATURES = {
     "uniir_topk_subshard_rows": (c_i64, [c_i64, c_int]),
     "uniir_topk_ip_multi_workspace_bytes": (c_i64, [c_int, c_int, c_i64, c_int]),
     "uniir_topk_ip_multi": (c_int, [P, P, P, c_i64, c_int, P, c_int, c_int, P, P, P, c_i64, S]),
+    "uniir_topk_plan": (c_int, [c_i64, c_int, c_int, c_int, c_int, P]),
 }
+
+
+class TopkPlan(C.Structure):
+    """uniir_topk_plan_t (include/uniir_hip.h): what a search of a shape launches and where its scratch lies"""
+    _fields_ = [(n, c_i64) for n in (
+        "scan", "waves", "tail", "select", "rem_queries", "rem_scan", "rem_waves", "rem_tail", "rem_select", "sweep_queries", "ncand",
+        "nsub", "batched", "subshard_rows", "last_rows", "workspace_bytes",
+        "gmax_bytes", "wmax_bytes", "qinv_bytes", "cand_bytes", "exact_bytes", "lists_bytes")]
+
+
+def topk_plan(rows, dim, nq, k, ncu):
+    """the library's plan of a uniir_topk_ip / uniir_topk_ip_multi search on a device with ncu compute units (no device needed)"""
+    p = TopkPlan()
+    check(load().uniir_topk_plan(rows, dim, nq, k, ncu, C.byref(p)), "uniir_topk_plan")
+    return p
 
 _lib = None
 

@@ -329,22 +329,6 @@ __global__ __launch_bounds__(BS) void topk_gsel_kernel(const float* __restrict__
     gsel_body<BS, REG>(gmax + (long)q * ngroups, ngroups, rows, kc, gcap, cand_idx + (long)q * gcap * TK_G, [] {});
 }
 
-static void coarse_plan(int nq, long rows, int* nqt, int* nslices, long* rows_per_slice) {
-    *nqt = (nq + TK_QT - 1) / TK_QT;
-    long tiles = (rows + TK_CT - 1) / TK_CT;
-    long want = (768 + *nqt - 1) / *nqt;        // aim at ~768 workgroups (3 per CU)
-    if (want < 1) want = 1;
-    if (want > tiles) want = tiles;
-    long tps = (tiles + want - 1) / want;       // candidate tiles per slice
-    if (tps < 1) tps = 1;
-    *rows_per_slice = tps * TK_CT;
-    *nslices = (int)((rows + *rows_per_slice - 1) / *rows_per_slice);
-}
-
-extern "C" int32_t uniir_topk_ncand(int32_t nq, int32_t kc) {
-    return nq <= TK_GPATH_MAXQ ? TK_GMULT * kc * TK_G : kc;
-}
-
 struct ElemF16Direct {   // operands in the order the main loop hands them over (B fragment, A fragment) -> mfma(A, B)
     static DEVINL f32x4_t mfma(u32x4_t b, u32x4_t a, f32x4_t c) {
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
@@ -1082,212 +1066,84 @@ __global__ __launch_bounds__(64 * QW, 1) void topk_stream5_kernel(const unsigned
     tkr_wait_vm<0>();                                              // the trailing dummies (and the last stores)
 }
 
-// The group-max scan of <= 1024 queries over the shard: gmax[q][group] = best approximate score of the 16 rows of the group.
-// Returns 1 when a 1024-thread selection is the matching follow-up (streaming / ping-pong scans), 0 for the 256-thread one,
-// negative on error.
-// wmax / nw_out (optional): room for [nq][1024] per-wave maxima; *nw_out = the number of waves when the scan wrote them, else 0.
-// does the shared-ring streaming scan (topk_stream5_kernel<2 / 4>) take a sweep of nq (65 .. 256) queries over this shard?
-static bool stream_shared_ok(int dim, int64_t rows, int nq) {
-    const long ngroups = (rows + TK_G - 1) / TK_G;
-    return nq > 64 && nq <= 256 && dim == 768 && rows * 1536 < (1L << 31) && ngroups >= 2048;
-}
-static int tk_cu_count() {
-    static int ncu = 0;
-    if (!ncu) {
-        int d = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&d) != hipSuccess || hipGetDeviceProperties(&prop, d) != hipSuccess) return -1;
-        ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return ncu;
-}
-template <int QW>
-static void launch_stream5(int nv, hipStream_t st0, const void* pool_f16, const float* pool_inv_norm, long rows,
-                           const void* queries_f16, int nq, float* gmax, long ngroups, float* wm) {
-    static PerDeviceOnce attr;
-    if (attr.first())
-        (void)hipFuncSetAttribute((const void*)topk_stream5_kernel<QW, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, Tk5<QW>::LDS);
-    hipLaunchKernelGGL((topk_stream5_kernel<QW, 2>), dim3(nv / QW), dim3(64 * QW), Tk5<QW>::LDS, st0, (const unsigned short*)pool_f16,
-                       pool_inv_norm, rows, (const unsigned short*)queries_f16, nq, gmax, ngroups, wm);
-}
-// The scan of a sweep, by shape (every pool stream is read with the nt policy where a row is read exactly once per sweep:
-// measured 0.2729 -> 0.2466 ms per 64-query search):
-//   <= 64 queries, dim 768 / 512, a shard the 31-bit buffer bound addresses, >= 2048 groups : topk_stream2_kernel<dim / 32>
-//   <= 64 queries, dim 768 / 512 otherwise (small shards)                                    : topk_stream_kernel (queries in LDS)
-//   65 .. 256 queries where the first line's conditions hold                           : topk_stream5_kernel<2 / 4>
-//   more queries or other shapes, dim a multiple of 64 and >= 192                      : topk_gmax_pp_kernel (ping-pong GEMM core)
-//   anything else                                                                      : topk_gmax_kernel
-static int launch_gmax_scan(const void* pool_f16, const float* pool_inv_norm, int64_t rows, int32_t dim,
-                            const void* queries_f16, int32_t nq, float* gmax, hipStream_t st0, float* wmax = nullptr,
-                            int* nw_out = nullptr) {
-    if (nw_out) *nw_out = 0;
-    const long ngroups = (rows + TK_G - 1) / TK_G;
-    int nqt, nsl; long rps;
-    coarse_plan(nq, rows, &nqt, &nsl, &rps);
-    const bool big_stream = (dim == 768 || dim == 512) && rows * dim * 2 < (1L << 31) && ngroups >= 2048;
-    if (nq <= 64 && big_stream) {
-        const int ncu = tk_cu_count();
-        if (ncu < 0) return UNIIR_ELAUNCH;
-        // the per-wave maxima feed the hierarchical selection of the fused tail
-        float* wm = (wmax && nw_out && ncu * 4 <= 1024 && (ngroups + ncu * 4 - 1) / (ncu * 4) <= 64) ? wmax : nullptr;
-        if (wm) *nw_out = ncu * 4;
-#define TKS2_LAUNCH(NK)                                                                                                             \
-    do {                                                                                                                            \
-        static PerDeviceOnce attr_s2;                                                                                               \
-        if (attr_s2.first())                                                                                                        \
-            (void)hipFuncSetAttribute((const void*)topk_stream2_kernel<NK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,          \
-                                      4 * Tkr<NK>::WAVE_LDS);                                                                       \
-        hipLaunchKernelGGL((topk_stream2_kernel<NK, 2>), dim3(ncu), dim3(256), 4 * Tkr<NK>::WAVE_LDS, st0,                          \
-                           (const unsigned short*)pool_f16, pool_inv_norm, (long)rows, (const unsigned short*)queries_f16, nq, gmax, \
-                           ngroups, wm);                                                                                            \
-    } while (0)
-        if (dim == 768) TKS2_LAUNCH(24);
-        else TKS2_LAUNCH(16);
-#undef TKS2_LAUNCH
-        HIP_LAUNCH_CHECK();
-        return 1;
-    }
-    if (nq <= 64 && (dim == 768 || dim == 512)) {
-        const long nchunks = (ngroups + TKS_CH - 1) / TKS_CH;
-        const size_t sms = 64 * (dim * 2 + 16) + 8 * 64 * TKS_CH * 4;
-        int grid = 256;
-        if (nchunks < (long)grid * 8) grid = (int)((nchunks + 7) / 8);
-        if (dim == 768) {
-            (void)hipFuncSetAttribute((const void*)topk_stream_kernel<24>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sms);
-            hipLaunchKernelGGL(topk_stream_kernel<24>, dim3(grid), dim3(512), sms, st0, (const unsigned short*)pool_f16,
-                               pool_inv_norm, (long)rows, (const unsigned short*)queries_f16, nq, gmax, ngroups, nchunks);
-        } else {
-            (void)hipFuncSetAttribute((const void*)topk_stream_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sms);
-            hipLaunchKernelGGL(topk_stream_kernel<16>, dim3(grid), dim3(512), sms, st0, (const unsigned short*)pool_f16,
-                               pool_inv_norm, (long)rows, (const unsigned short*)queries_f16, nq, gmax, ngroups, nchunks);
-        }
-        HIP_LAUNCH_CHECK();
-        return 1;
-    }
-    // 65 .. 256 queries, dim 768: the shared-ring streaming scan (queries in registers, 64 per wave)
-    // MEASURED (round 3, 700 k rows, whole search): 128 queries 0.224-0.239 ms vs 0.280-0.291 (ping-pong GEMM scan), 256 queries
-    // 0.318-0.345 vs 0.376
-    if (stream_shared_ok(dim, rows, nq)) {
-        const int ncu = tk_cu_count();
-        if (ncu < 0) return UNIIR_ELAUNCH;
-        const int nv = ncu * 4;
-        float* wm = (wmax && nw_out && nv <= 1024 && (ngroups + nv - 1) / nv <= 64) ? wmax : nullptr;
-        if (wm) *nw_out = nv;
-        if (nq <= 128) launch_stream5<2>(nv, st0, pool_f16, pool_inv_norm, (long)rows, queries_f16, nq, gmax, ngroups, wm);
-        else launch_stream5<4>(nv, st0, pool_f16, pool_inv_norm, (long)rows, queries_f16, nq, gmax, ngroups, wm);
-        HIP_LAUNCH_CHECK();
-        return 1;
-    }
-    if (nq > 64 && dim % 64 == 0 && dim >= 192) {
-        const int tiles_q = (nq + 255) / 256;
-        const long tiles_c = (rows + 255) / 256;
-        const bool halfn = nq <= 128;         // half-width query tile
-        const bool nt = nq <= 256;            // one query tile: every pool row is read exactly once
-#define TKPP_LAUNCH(H, A)                                                                                                      \
-    do {                                                                                                                       \
-        static PerDeviceOnce attr;                                                                                             \
-        if (attr.first())                                                                                                      \
-            (void)hipFuncSetAttribute((const void*)topk_gmax_pp_kernel<H, A>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072); \
-        hipLaunchKernelGGL((topk_gmax_pp_kernel<H, A>), dim3((unsigned)(tiles_c * tiles_q)), dim3(512), 131072, st0,          \
-                           (const unsigned short*)pool_f16, pool_inv_norm, (long)rows, dim, (const unsigned short*)queries_f16, \
-                           nq, gmax, ngroups, tiles_q);                                                                        \
-    } while (0)
-        if (halfn) TKPP_LAUNCH(true, 2);
-        else if (nt) TKPP_LAUNCH(false, 2);
-        else TKPP_LAUNCH(false, 0);
-#undef TKPP_LAUNCH
-        HIP_LAUNCH_CHECK();
-        return 1;
-    }
-    const long ct = 256;
-    long tiles = (rows + ct - 1) / ct;
-    long want = (768 + nqt - 1) / nqt;
-    if (want > tiles) want = tiles;
+// =============================================================================================================================
+// Host layer.  One plan per search, computed before the first launch (tk_plan); one launcher (tk_launch, topk.h); one argument
+// check (tk_check).  The table the plan implements is DESIGN.md "Top-k host layer"; tests/topk_cases.py restates it on its own
+// and the host suite compares the two through uniir_topk_plan.  Nothing below launches first and decides afterwards.
+// =============================================================================================================================
+static void coarse_plan(int nq, long rows, int* nqt, int* nslices, long* rows_per_slice) {
+    *nqt = (nq + TK_QT - 1) / TK_QT;
+    long tiles = (rows + TK_CT - 1) / TK_CT;
+    long want = (768 + *nqt - 1) / *nqt;        // aim at ~768 workgroups (3 per CU)
     if (want < 1) want = 1;
-    const long tps = (tiles + want - 1) / want;
-    rps = tps * ct;
-    nsl = (int)((rows + rps - 1) / rps);
-    const size_t smg = GldsShape<2, 2, 32>::LDS_BYTES;
-    (void)hipFuncSetAttribute((const void*)topk_gmax_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smg);
-    hipLaunchKernelGGL(topk_gmax_kernel<2>, dim3(nsl, nqt), dim3(256), smg, st0, (const unsigned short*)pool_f16,
-                       pool_inv_norm, (long)rows, dim, (const unsigned short*)queries_f16, nq, rps, gmax, ngroups);
-    HIP_LAUNCH_CHECK();
-    return 0;
+    if (want > tiles) want = tiles;
+    long tps = (tiles + want - 1) / want;       // candidate tiles per slice
+    if (tps < 1) tps = 1;
+    *rows_per_slice = tps * TK_CT;
+    *nslices = (int)((rows + *rows_per_slice - 1) / *rows_per_slice);
 }
 
-// the stand-alone group selection behind a scan (`sel` = launch_gmax_scan's return value)
-static int topk_select_after_scan(int sel, const float* gmax, int64_t rows, int32_t nq, int32_t kc, int32_t* cand_idx,
-                                  hipStream_t st0) {
-    const long ngroups = (rows + TK_G - 1) / TK_G;
-    if (sel == 1 && ngroups % 2 == 0 && ngroups <= 1024L * 2 * TK_SELREG)       // register-resident selection
-        hipLaunchKernelGGL((topk_gsel_kernel<1024, true>), dim3(nq), dim3(1024), 0, st0, gmax, ngroups, (long)rows, nq,
-                           kc, TK_GMULT * kc, cand_idx);
-    else if (sel == 1 && nq <= 64)
-        hipLaunchKernelGGL((topk_gsel_kernel<1024, false>), dim3(nq), dim3(1024), 0, st0, gmax, ngroups, (long)rows, nq,
-                           kc, TK_GMULT * kc, cand_idx);
-    else
-        hipLaunchKernelGGL(topk_gsel_kernel<256>, dim3(nq), dim3(256), 0, st0, gmax, ngroups, (long)rows, nq, kc,
-                           TK_GMULT * kc, cand_idx);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
+extern "C" int32_t uniir_topk_ncand(int32_t nq, int32_t kc) {
+    return nq <= TK_GPATH_MAXQ ? TK_GMULT * kc * TK_G : kc;
 }
 
-#define TK_WMAX_BYTES(nq) ((int64_t)((nq) < 64 ? 64 : (nq)) * 1024 * 4 + 256)     // per-wave maxima of the streaming scans: [nq][<= 1024 waves] fp32
-extern "C" int64_t uniir_topk_workspace_bytes(int32_t nq, int32_t kc, int64_t rows) {
-    if (nq <= 0 || kc <= 0 || rows <= 0) return 0;
-    if (nq <= TK_GPATH_MAXQ) {
-        const int64_t ngroups = (rows + TK_G - 1) / TK_G;
-        const int64_t dense = (int64_t)nq * ngroups * 4 + 256 + TK_WMAX_BYTES(nq <= 256 ? nq : 64);
-        return dense;
+// ---- the shape rules, each once ------------------------------------------------------------------------------------------------
+// the register streaming scans (topk_stream2_kernel, topk_stream5_kernel): a width they are built for, a shard the 31-bit buffer
+// bound addresses, >= 2048 groups
+static bool big_stream(int64_t rows, int32_t dim) {
+    return (dim == 768 || dim == 512) && tk_fits31(rows, dim, 2) && tk_groups(rows) >= 2048;
+}
+// does the shared-ring streaming scan (topk_stream5_kernel<2 / 4>, dim 768 only) take a sweep of nq (65 .. 256) queries over this shard?
+static bool stream_shared_ok(int dim, int64_t rows, int nq) { return nq > 64 && nq <= 256 && dim == 768 && big_stream(rows, dim); }
+// do the 4 ncu waves of a register streaming scan leave their maxima ([nq][<= 1024 waves], each over <= 64 groups) beside the
+// group maxima?  They feed the hierarchical selection of the fused tail.
+static bool waves_ok(int64_t rows, int ncu) { return ncu > 0 && ncu * 4 <= 1024 && (tk_groups(rows) + ncu * 4 - 1) / (ncu * 4) <= 64; }
+// can the fused tail (selection + query norm + exact re-score | sort) serve this search?  (the last term: the gather's buffer bound)
+static bool fused_tail_ok(int64_t rows, int32_t dim, int32_t kc) {
+    const int gcap = TK_GMULT * kc;
+    return dim % 64 == 0 && dim <= 4096 && tk_sel_reg_ok(rows) && gcap * TK_G <= TKT_SORTCAP && gcap <= 2 * TK_MAXKC && tk_fits31(rows, dim, 2);
+}
+
+// ---- one sweep -----------------------------------------------------------------------------------------------------------------
+// The scan of a sweep, by shape (every pool stream is read with the nt policy where a row is read exactly once per sweep: measured
+// 0.2729 -> 0.2466 ms per 64-query search); the whole table with the tails: DESIGN.md "Top-k host layer".
+// MEASURED (round 3, 700 k rows, whole search), shared-ring scan against the ping-pong GEMM scan: 128 queries 0.224-0.239 ms vs
+// 0.280-0.291, 256 queries 0.318-0.345 vs 0.376.
+// (A single fused select + re-score + sort launch per query was measured and dropped: with 64 queries the tail is latency-bound and
+// one 1024-thread workgroup per query serialises what the launches spread over the whole chip: 98 us instead of 80 us behind the
+// 217-us scan; at 1024 queries it made no difference.)
+TkSweep tk_plan_sweep(int64_t rows, int32_t dim, int32_t n, int32_t kc, int ncu) {
+    TkSweep s = {};
+    s.n = n;
+    s.ncu = ncu;
+    s.ncand = uniir_topk_ncand(n, kc);
+    if (n > TK_GPATH_MAXQ) {                     // uniir_topk_coarse only: threshold-select scan, shortlist of kc rows
+        s.scan = UNIIR_TK_SCAN_COARSE;
+        s.sel = UNIIR_TK_SEL_MERGE_PARTIAL;
+        return s;
     }
-    int nqt, nsl; long rps;
-    coarse_plan(nq, rows, &nqt, &nsl, &rps);
-    return (int64_t)nqt * nsl * TK_QT * TK_CAP * (int64_t)sizeof(TkEntry) + (int64_t)nsl * nq * kc * (int64_t)sizeof(TkEntry) + 256;
+    if (n <= 64 && big_stream(rows, dim)) s.scan = UNIIR_TK_SCAN_STREAM2;
+    else if (n <= 64 && (dim == 768 || dim == 512)) s.scan = UNIIR_TK_SCAN_STREAM;
+    else if (stream_shared_ok(dim, rows, n)) s.scan = n <= 128 ? UNIIR_TK_SCAN_SHARED2 : UNIIR_TK_SCAN_SHARED4;
+    else if (n > 64 && dim % 64 == 0 && dim >= 192)      // half-width query tile | one query tile, every row read once (nt) | more
+        s.scan = n <= 128 ? UNIIR_TK_SCAN_PP_HALF : n <= 256 ? UNIIR_TK_SCAN_PP_NT : UNIIR_TK_SCAN_PP;
+    else s.scan = UNIIR_TK_SCAN_GMAX;
+    const bool registers = s.scan == UNIIR_TK_SCAN_STREAM2 || s.scan == UNIIR_TK_SCAN_SHARED2 || s.scan == UNIIR_TK_SCAN_SHARED4;
+    s.nw = registers && waves_ok(rows, ncu) ? ncu * 4 : 0;
+    const bool wide = s.scan != UNIIR_TK_SCAN_GMAX;       // a 1024-thread selection follows every scan but the first-generation one
+    s.sel = wide && tk_sel_reg_ok(rows) ? UNIIR_TK_SEL_1024_REG : wide && n <= 64 ? UNIIR_TK_SEL_1024 : UNIIR_TK_SEL_256;
+    s.fused = wide && fused_tail_ok(rows, dim, kc);
+    // one workgroup per (query, part): the interactive regime spreads a query's re-score over PARTS workgroups
+    s.parts = n <= 64 ? 4 : n <= 128 ? 2 : 1;
+    return s;
+}
+static bool tk_batchable(const TkSweep& s) {     // the batched tail follows register streaming scans on fused-tail shapes
+    return s.n == 0 || (s.fused && (s.scan == UNIIR_TK_SCAN_STREAM2 || s.scan == UNIIR_TK_SCAN_SHARED2 || s.scan == UNIIR_TK_SCAN_SHARED4));
 }
 
-extern "C" int uniir_topk_coarse(const void* pool_f16, const float* pool_inv_norm, int64_t rows, int32_t dim,
-                                 const void* queries_f16, int32_t nq, int32_t kc, int32_t* cand_idx,
-                                 float* cand_score, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (!pool_f16 || !pool_inv_norm || !queries_f16 || !cand_idx || !workspace) return UNIIR_EINVAL;
-    if (rows <= 0 || nq <= 0 || kc <= 0) return UNIIR_EINVAL;
-    if (kc > TK_MAXKC || dim % 32 || dim <= 0 || rows > 0x7fffffffL || rows * (int64_t)dim * 2 >= ((int64_t)1 << 31)) return UNIIR_ESHAPE;
-    if (((uintptr_t)pool_f16 & 15) || ((uintptr_t)queries_f16 & 15) || ((uintptr_t)pool_inv_norm & 15) ||
-        ((uintptr_t)workspace & 15))
-        return UNIIR_EALIGN;
-    if (workspace_bytes < uniir_topk_workspace_bytes(nq, kc, rows)) return UNIIR_EINVAL;
-    int nqt, nsl; long rps;
-    coarse_plan(nq, rows, &nqt, &nsl, &rps);
-    hipStream_t st0 = (hipStream_t)stream;
-    if (nq <= TK_GPATH_MAXQ) {
-        const long ngroups = (rows + TK_G - 1) / TK_G;
-        float* gmax = (float*)workspace;
-        const int sel = launch_gmax_scan(pool_f16, pool_inv_norm, rows, dim, queries_f16, nq, gmax, st0);
-        if (sel < 0) return sel;
-        return topk_select_after_scan(sel, gmax, rows, nq, kc, cand_idx, st0);
-    }
-    TkEntry* bufs = (TkEntry*)workspace;
-    TkEntry* partial = bufs + (long)nqt * nsl * TK_QT * TK_CAP;
-    const size_t sm = TkShape::LDS_BYTES + 1024 + 64;
-    static PerDeviceOnce attr;
-    if (attr.first())
-        (void)hipFuncSetAttribute((const void*)topk_coarse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(topk_coarse_kernel, dim3(nsl, nqt), dim3(256), sm, st, (const unsigned short*)pool_f16,
-                       pool_inv_norm, (long)rows, dim, (const unsigned short*)queries_f16, nq, kc, rps, bufs, partial);
-    hipLaunchKernelGGL(topk_merge_partial_kernel, dim3(nq), dim3(256), 0, st, partial, nsl, nq, kc, cand_idx,
-                       cand_score);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
-}
-
-// -------------------------------------------------------------------------------------------------------------
-// uniir_topk_ip: the whole search_index of one pool shard in one call (mbeir_retriever.py:188-232 = normalise the queries,
-// exact inner-product top-k): query inverse norms, then per chunk of <= 1024 queries one sweep of the shard (group-max scan),
-// group selection, exact re-score, sort.  k <= 56 (k + 8 <= TK_MAXKC groups per query); larger k is assembled from slices by
-// the caller.  (A single fused select + re-score + sort launch per query was measured and dropped: with 64 queries the tail is
-// latency-bound and one 1024-thread workgroup per query serialises what the three launches spread over the whole chip:
-// 98 us instead of 80 us behind the 217-us scan; at 1024 queries it made no difference.)
+// ---- one search ----------------------------------------------------------------------------------------------------------------
 #define TKI_CHUNK_MAX 1024
+static_assert(TKI_CHUNK_MAX <= TK_GPATH_MAXQ, "a sweep of the one-call search is a group-max scan, never the coarse kernel");
 static int g_tki_chunk = 0;             // 0 = automatic
 // queries per sweep of uniir_topk_ip.  0 = automatic: 256 where the 4-wave streaming scan applies (dim 768, a shard the buffer
 // bound can address, >= 2048 groups), else 1024 (the most the GEMM-shaped scan takes).  MEASURED (round 3, 700 k rows, same box,
@@ -1295,6 +1151,9 @@ static int g_tki_chunk = 0;             // 0 = automatic
 // 1.380 / 1.303 -- four streaming sweeps re-read the pool three more times (HBM is not the limit there) and still beat one GEMM-
 // shaped sweep.  An explicit value only changes the number of sweeps (tests of the sweep loop; tuning); results never depend on it.
 // Host-side setting, not thread-safe.
+// (One tail per BATCH of sweeps -- the scans of four 256-query sweeps writing their maxima side by side, then one fused tail and
+// one sort for the 1024 queries -- was built and measured in round 4: 1024 queries 1.262 ms vs 1.24-1.27, 100 000 queries 123.8 vs
+// 124.3 ms.  The tail is throughput-bound, not launch-bound; dropped.)
 extern "C" int uniir_topk_set_chunk(int32_t queries_per_sweep) {
     if (queries_per_sweep < 0 || queries_per_sweep > TKI_CHUNK_MAX) return UNIIR_EINVAL;
     g_tki_chunk = queries_per_sweep;
@@ -1305,83 +1164,275 @@ extern "C" int32_t uniir_topk_ip_sweep_queries(int32_t dim, int64_t rows) {
     if (g_tki_chunk) return g_tki_chunk;
     return stream_shared_ok(dim, rows, 256) ? 256 : TKI_CHUNK_MAX;
 }
-static int64_t tki_ws_bytes(int32_t nq, int32_t k, int64_t rows, int chunk_max) {
-    const int chunk = nq < chunk_max ? nq : chunk_max;
-    const int kc = k + 8 < TK_MAXKC ? k + 8 : TK_MAXKC;
-    const int64_t ncand = uniir_topk_ncand(chunk, kc);
-    return uniir_topk_workspace_bytes(chunk, kc, rows) + (int64_t)nq * 4 + 256 + 2 * ((int64_t)chunk * ncand * 4 + 256);
+// per-wave maxima of the streaming scans: [n][<= 1024 waves] fp32, room for 64 queries at least; wider sweeps than 256 write none
+static int64_t tk_wmax_bytes(int n) { return (int64_t)(n < 64 || n > 256 ? 64 : n) * 1024 * 4 + 256; }
+// scratch of one group-max sweep of n <= 1024 queries: group maxima [n][ngroups] | wave maxima
+static int64_t tk_dense_bytes(int n, int64_t rows) { return (int64_t)n * tk_groups(rows) * 4 + 256 + tk_wmax_bytes(n); }
+// The search of one shard below the buffer bound in sweeps of at most chunk_max queries.
+// Workspace: group [+ wave] maxima of one sweep | query inverse norms (unfused tail) | candidate rows | exact scores.
+static void tk_plan_shard(int64_t rows, int32_t dim, int32_t nq, int32_t k, int chunk_max, int ncu, TkShardPlan* p) {
+    p->rows = rows;
+    p->chunk = nq < chunk_max ? nq : chunk_max;
+    p->kc = k + 8 < TK_MAXKC ? k + 8 : TK_MAXKC;          // (a k the entry points refuse still has a size)
+    const int nrem = nq % p->chunk;
+    p->full = tk_plan_sweep(rows, dim, p->chunk, p->kc, ncu);
+    p->rem = nrem ? tk_plan_sweep(rows, dim, nrem, p->kc, ncu) : TkSweep{};
+    // the wave maxima lie behind the group maxima of the sweep that writes them (a narrow remainder sweep under an explicit width
+    // above 256 may write more of them than tk_wmax_bytes(chunk) holds: the rows it does not use are its room)
+    p->full.wmax_off = tk_align256((int64_t)p->chunk * tk_groups(rows) * 4);
+    p->rem.wmax_off = tk_align256((int64_t)nrem * tk_groups(rows) * 4);
+    const int64_t cbytes = (int64_t)p->chunk * p->full.ncand * 4;
+    p->gmax = {0, tk_align256(tk_dense_bytes(p->chunk, rows))};
+    p->qinv = {p->gmax.bytes, tk_align256((int64_t)nq * 4)};
+    p->cand = {p->qinv.off + p->qinv.bytes, tk_align256(cbytes)};
+    p->exact = {p->cand.off + p->cand.bytes, tk_align256(cbytes)};
+    p->bytes = tk_dense_bytes(p->chunk, rows) + (int64_t)nq * 4 + 256 + 2 * (cbytes + 256);       // (the size exported since round 1)
 }
+extern "C" int64_t uniir_topk_subshard_rows(int64_t rows, int32_t dim) {
+    if (rows <= 0 || dim <= 0) return 0;
+    if (tk_fits31(rows, dim, 2)) return rows;
+    const int64_t fused = 1024L * 2 * TK_SELREG * TK_G;                       // the fused tail's register-resident selection
+    int64_t cap = ((((int64_t)1 << 31) - 1) / ((int64_t)dim * 2)) / 32 * 32;
+    if (cap > fused) cap = fused;
+    const int64_t parts = (rows + cap - 1) / cap;
+    return ((rows + parts - 1) / parts + 31) / 32 * 32;
+}
+// The search of one resident shard of any size: equal logical sub-shards (nothing is copied), each below the buffer bound and
+// within the fused tail's rows.  BATCHED when all four sweep shapes -- a full sub-shard and the last one, each at the full sweep
+// width and at the remainder -- are register streaming scans with a fused tail, the two sub-shard shapes agree on the sweep width
+// and there are <= 64 sub-shards (the merge kernel's MERGE_CAP at k <= 56): then the tail, the sort and the merge of ALL sub-shards
+// are one launch each per sweep.  Otherwise (a last sub-shard with an odd number of groups, more than 256 queries per sweep at
+// dim 512, ...) one uniir_topk_ip search per sub-shard and one merge; same results.
+// Round 4 ran that loop from the host: 5 x (27 + 8) us of latency-bound tails behind 5 scans (64 queries: 1.88 ms = 0.571 of 8 TB/s
+// over the 8.6-GB pool); batched, the tails of all sub-shards run side by side.
+void tk_plan(int64_t rows, int32_t dim, int32_t nq, int32_t k, int ncu, TkPlan* p) {
+    *p = {};
+    p->per = uniir_topk_subshard_rows(rows, dim);
+    p->nsub = (int)((rows + p->per - 1) / p->per);
+    p->last_rows = rows - (int64_t)(p->nsub - 1) * p->per;
+    TkShardPlan &a = p->sub[0], &b = p->sub[1];
+    tk_plan_shard(p->per, dim, nq, k, uniir_topk_ip_sweep_queries(dim, p->per), ncu, &a);
+    tk_plan_shard(p->last_rows, dim, nq, k, uniir_topk_ip_sweep_queries(dim, p->last_rows), ncu, &b);
+    p->bytes = a.bytes;
+    if (p->nsub == 1) return;
+    p->batched = a.chunk == b.chunk && tk_batchable(a.full) && tk_batchable(a.rem) && tk_batchable(b.full) && tk_batchable(b.rem) &&
+                 a.full.scan == b.full.scan && a.rem.scan == b.rem.scan && p->nsub <= 64;
+    if (p->batched) {
+        // one tail for all sub-shards: the wave maxima exist only when EVERY sub-shard's scan writes them (the rule depends on the
+        // group count, and the shorter last sub-shard may disagree with the full ones); the sub-shards already fill the chip
+        p->full = a.full;
+        p->rem = a.rem;
+        for (TkSweep* s : {&p->full, &p->rem}) {
+            s->nw = a.full.nw && b.full.nw ? a.full.nw : 0;
+            s->parts = s->n * p->nsub <= 64 ? 4 : s->n * p->nsub <= 128 ? 2 : 1;
+        }
+    }
+    // batched: per sub-shard group maxima | wave maxima | candidates | exact scores | k-lists of a sweep (scores, ids)
+    const int64_t ns = p->nsub;
+    const int64_t g = tk_align256((int64_t)a.chunk * tk_groups(p->per) * 4), w = tk_align256(tk_wmax_bytes(a.chunk));
+    const int64_t c = tk_align256((int64_t)a.chunk * uniir_topk_ncand(a.chunk, k + 8) * 4);      // (k + 8 unclamped: the exported size)
+    const int64_t o = tk_align256((int64_t)a.chunk * k * 8);
+    p->gmax = {0, g};
+    p->wmax = {ns * g, w};
+    p->cand = {p->wmax.off + ns * w, c};
+    p->exact = {p->cand.off + ns * c, c};
+    p->list_s = {p->exact.off + ns * c, o};
+    p->list_i = {p->list_s.off + ns * o, o};
+    // the loop: one uniir_topk_ip workspace (the last sub-shard's need is never larger: with equal sweep widths the size grows with
+    // the rows, and a last sub-shard too short for the 256-query sweeps of the full ones has < 2048 groups against their > 32 768)
+    // | k-lists of ALL queries per sub-shard (scores, ids)
+    const int64_t all = ns * tk_align256((int64_t)nq * k * 8);
+    p->inner = {0, tk_align256(a.bytes)};
+    p->all_s = {p->inner.bytes, all};
+    p->all_i = {p->all_s.off + all, all};
+    const int64_t batched = p->list_i.off + ns * o, loop = p->all_i.off + all;
+    p->bytes = (batched > loop ? batched : loop) + 256;          // (both, whichever runs: the size does not depend on the device)
+}
+
+static int tk_cu_count() {
+    static int ncu = 0;
+    if (!ncu) {
+        int d = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&d) != hipSuccess || hipGetDeviceProperties(&prop, d) != hipSuccess) return -1;
+        ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    return ncu;
+}
+// The group-max scan the plan names: gmax[q][group] = best approximate score of the 16 rows of the group; the register streaming
+// scans also write their per-wave maxima to wmax when s.nw says so.  (UNIIR_TK_SCAN_COARSE has outputs of its own: uniir_topk_coarse.)
+static int launch_scan(const TkSweep& s, const void* pool_f16, const float* pinv, int64_t rows_, int32_t dim, const void* queries_f16,
+                       float* gmax, float* wmax, hipStream_t st) {
+    const unsigned short* pool = (const unsigned short*)pool_f16;
+    const unsigned short* q = (const unsigned short*)queries_f16;
+    const long rows = (long)rows_, ngroups = (long)tk_groups(rows_);
+    const int n = s.n;
+    float* wm = s.nw ? wmax : nullptr;
+    switch (s.scan) {
+    case UNIIR_TK_SCAN_STREAM2:               // queries in registers, wave-private rings: one workgroup per compute unit
+        if (dim == 768) return tk_launch<topk_stream2_kernel<24, 2>>(dim3(s.ncu), dim3(256), 4 * Tkr<24>::WAVE_LDS, st, pool, pinv, rows, q, n, gmax, ngroups, wm);
+        return tk_launch<topk_stream2_kernel<16, 2>>(dim3(s.ncu), dim3(256), 4 * Tkr<16>::WAVE_LDS, st, pool, pinv, rows, q, n, gmax, ngroups, wm);
+    case UNIIR_TK_SCAN_STREAM: {              // queries in LDS (small shards)
+        const long nchunks = (ngroups + TKS_CH - 1) / TKS_CH;
+        const int lds = 64 * (dim * 2 + 16) + 8 * 64 * TKS_CH * 4;
+        int grid = 256;
+        if (nchunks < (long)grid * 8) grid = (int)((nchunks + 7) / 8);
+        if (dim == 768) return tk_launch<topk_stream_kernel<24>>(dim3(grid), dim3(512), lds, st, pool, pinv, rows, q, n, gmax, ngroups, nchunks);
+        return tk_launch<topk_stream_kernel<16>>(dim3(grid), dim3(512), lds, st, pool, pinv, rows, q, n, gmax, ngroups, nchunks);
+    }
+    case UNIIR_TK_SCAN_SHARED2:               // the shared ring: 64 register-resident queries per wave, 2 | 4 waves, 4 ncu waves in all
+        return tk_launch<topk_stream5_kernel<2, 2>>(dim3(s.ncu * 2), dim3(128), Tk5<2>::LDS, st, pool, pinv, rows, q, n, gmax, ngroups, wm);
+    case UNIIR_TK_SCAN_SHARED4:
+        return tk_launch<topk_stream5_kernel<4, 2>>(dim3(s.ncu), dim3(256), Tk5<4>::LDS, st, pool, pinv, rows, q, n, gmax, ngroups, wm);
+    case UNIIR_TK_SCAN_PP_HALF:               // the ping-pong GEMM core
+    case UNIIR_TK_SCAN_PP_NT:
+    case UNIIR_TK_SCAN_PP: {
+        const int tiles_q = (n + 255) / 256;
+        const dim3 grid((unsigned)((rows + 255) / 256 * tiles_q));
+        if (s.scan == UNIIR_TK_SCAN_PP_HALF) return tk_launch<topk_gmax_pp_kernel<true, 2>>(grid, dim3(512), 131072, st, pool, pinv, rows, dim, q, n, gmax, ngroups, tiles_q);
+        if (s.scan == UNIIR_TK_SCAN_PP_NT) return tk_launch<topk_gmax_pp_kernel<false, 2>>(grid, dim3(512), 131072, st, pool, pinv, rows, dim, q, n, gmax, ngroups, tiles_q);
+        return tk_launch<topk_gmax_pp_kernel<false, 0>>(grid, dim3(512), 131072, st, pool, pinv, rows, dim, q, n, gmax, ngroups, tiles_q);
+    }
+    case UNIIR_TK_SCAN_GMAX: {                // the first-generation scan, in the coarse kernel's slices
+        int nqt, nsl; long rps;
+        coarse_plan(n, rows, &nqt, &nsl, &rps);
+        return tk_launch<topk_gmax_kernel<2>>(dim3(nsl, nqt), dim3(256), (int)GldsShape<2, 2, 32>::LDS_BYTES, st, pool, pinv, rows, dim, q, n, rps, gmax, ngroups);
+    }
+    }
+    return UNIIR_EINVAL;                      // (no plan of a group-max sweep names another scan)
+}
+
+// the stand-alone group selection the plan names behind a scan
+static int launch_select(const TkSweep& s, const float* gmax, int64_t rows, int32_t kc, int32_t* cand_idx, hipStream_t st) {
+    const long ngroups = (long)tk_groups(rows);
+    const int gcap = TK_GMULT * kc;
+    if (s.sel == UNIIR_TK_SEL_1024_REG) return tk_launch<topk_gsel_kernel<1024, true>>(dim3(s.n), dim3(1024), 0, st, gmax, ngroups, (long)rows, s.n, kc, gcap, cand_idx);
+    if (s.sel == UNIIR_TK_SEL_1024) return tk_launch<topk_gsel_kernel<1024, false>>(dim3(s.n), dim3(1024), 0, st, gmax, ngroups, (long)rows, s.n, kc, gcap, cand_idx);
+    return tk_launch<topk_gsel_kernel<256>>(dim3(s.n), dim3(256), 0, st, gmax, ngroups, (long)rows, s.n, kc, gcap, cand_idx);
+}
+
+// One check for the searches: the arguments uniir_topk_ip, uniir_topk_ip_multi and uniir_topk_coarse have in common, in the order
+// the refusal table of tests/test_topk_refusals_host.py pins (null pointers and counts, shape, alignment).  out: the entry point's
+// own output pointers (null when one is missing); count: its k or kc as given; kc: the groups it keeps per query; dim_mult /
+// ws_align: 64 / 256 for the one-call searches, 32 / 16 for the op-level scan; bound31: the shard must lie below the buffer bound.
+// A refused call has reached no HIP call.
+static int tk_check(const void* pool_f16, const float* pinv, const void* queries_f16, const void* out, const void* workspace,
+                    int64_t rows, int32_t dim, int32_t nq, int32_t count, int32_t kc, int dim_mult, bool bound31, int ws_align) {
+    if (!pool_f16 || !pinv || !queries_f16 || !out || !workspace) return UNIIR_EINVAL;
+    if (rows <= 0 || nq <= 0 || count <= 0) return UNIIR_EINVAL;
+    if (kc > TK_MAXKC || dim % dim_mult || dim <= 0 || rows > 0x7fffffffL) return UNIIR_ESHAPE;
+    // a shard is addressed through 31-bit buffer offsets: >= 2 GiB of rows is searched as equal sub-shards (uniir_topk_ip_multi:
+    // the 5.6 M x 768 pool on one GPU = 8 logical sub-shards), never silently by a slower path
+    if (bound31 && !tk_fits31(rows, dim, 2)) return UNIIR_ESHAPE;
+    if (((uintptr_t)pool_f16 & 15) || ((uintptr_t)queries_f16 & 15) || ((uintptr_t)pinv & 15) || ((uintptr_t)workspace & (ws_align - 1)))
+        return UNIIR_EALIGN;
+    return UNIIR_OK;
+}
+
+// workspace of uniir_topk_coarse: the scratch of one group-max sweep, or (more than 1024 queries) the coarse kernel's candidate
+// buffers [query tiles][slices][128][TK_CAP] | the slices' partial shortlists [slices][nq][kc]
+static int64_t tk_coarse_bufs(int nqt, int nsl) { return (int64_t)nqt * nsl * TK_QT * TK_CAP; }      // entries
+extern "C" int64_t uniir_topk_workspace_bytes(int32_t nq, int32_t kc, int64_t rows) {
+    if (nq <= 0 || kc <= 0 || rows <= 0) return 0;
+    if (nq <= TK_GPATH_MAXQ) return tk_dense_bytes(nq, rows);
+    int nqt, nsl; long rps;
+    coarse_plan(nq, rows, &nqt, &nsl, &rps);
+    return (tk_coarse_bufs(nqt, nsl) + (int64_t)nsl * nq * kc) * (int64_t)sizeof(TkEntry) + 256;
+}
+
+extern "C" int uniir_topk_coarse(const void* pool_f16, const float* pool_inv_norm, int64_t rows, int32_t dim,
+                                 const void* queries_f16, int32_t nq, int32_t kc, int32_t* cand_idx,
+                                 float* cand_score, void* workspace, int64_t workspace_bytes, void* stream) {
+    int rc = tk_check(pool_f16, pool_inv_norm, queries_f16, cand_idx, workspace, rows, dim, nq, kc, kc, 32, true, 16);
+    if (rc) return rc;
+    if (workspace_bytes < uniir_topk_workspace_bytes(nq, kc, rows)) return UNIIR_EINVAL;
+    const int ncu = tk_cu_count();
+    if (ncu < 0) return UNIIR_ELAUNCH;
+    hipStream_t st = (hipStream_t)stream;
+    TkSweep s = tk_plan_sweep(rows, dim, nq, kc, ncu);
+    if (s.scan != UNIIR_TK_SCAN_COARSE) {
+        s.nw = 0;                             // the op-level selection kernels read the group maxima only
+        float* gmax = (float*)workspace;
+        rc = launch_scan(s, pool_f16, pool_inv_norm, rows, dim, queries_f16, gmax, nullptr, st);
+        return rc ? rc : launch_select(s, gmax, rows, kc, cand_idx, st);
+    }
+    int nqt, nsl; long rps;
+    coarse_plan(nq, rows, &nqt, &nsl, &rps);
+    TkEntry* bufs = (TkEntry*)workspace;
+    TkEntry* partial = bufs + tk_coarse_bufs(nqt, nsl);
+    rc = tk_launch<topk_coarse_kernel>(dim3(nsl, nqt), dim3(256), (int)(TkShape::LDS_BYTES + 1024 + 64), st, (const unsigned short*)pool_f16,
+                                       pool_inv_norm, (long)rows, dim, (const unsigned short*)queries_f16, nq, kc, rps, bufs, partial);
+    return rc ? rc : tk_launch<topk_merge_partial_kernel>(dim3(nq), dim3(256), 0, st, (const TkEntry*)partial, nsl, nq, kc, cand_idx, cand_score);
+}
+
+// -------------------------------------------------------------------------------------------------------------
+// uniir_topk_ip: the whole search_index of one pool shard in one call (mbeir_retriever.py:188-232 = normalise the queries,
+// exact inner-product top-k): per sweep of <= 1024 queries one group-max scan of the shard, then the fused tail (selection + query
+// norm + exact re-score | sort) or, where the plan says so, the stand-alone selection, the query inverse norms (once) and
+// uniir_topk_rescore.  k <= 56 (k + 8 <= TK_MAXKC groups per query); larger k is assembled from slices by the caller.
 extern "C" int64_t uniir_topk_ip_workspace_bytes(int32_t nq, int32_t k, int64_t rows) {
     if (nq <= 0 || k <= 0 || rows <= 0) return 0;
-    if (g_tki_chunk) return tki_ws_bytes(nq, k, rows, g_tki_chunk);
-    const int64_t a = tki_ws_bytes(nq, k, rows, 256), b = tki_ws_bytes(nq, k, rows, TKI_CHUNK_MAX);     // dim is not known here
-    return a > b ? a : b;
+    TkShardPlan a, b;
+    tk_plan_shard(rows, 768, nq, k, g_tki_chunk ? g_tki_chunk : 256, 0, &a);                  // dim is not known here: the larger of
+    tk_plan_shard(rows, 768, nq, k, g_tki_chunk ? g_tki_chunk : TKI_CHUNK_MAX, 0, &b);        // the two automatic sweep widths
+    return a.bytes > b.bytes ? a.bytes : b.bytes;
 }
 // the exact requirement of a search of this shape: the sweep width is a function of (dim, rows), so up to 256 queries on a dim-768
 // shard need a quarter of the group-maxima region the dim-agnostic bound reserves (45 MB instead of 179 MB at 700 k rows)
 extern "C" int64_t uniir_topk_ip_workspace_bytes_ex(int32_t nq, int32_t k, int64_t rows, int32_t dim) {
     if (nq <= 0 || k <= 0 || rows <= 0 || dim <= 0) return 0;
-    return tki_ws_bytes(nq, k, rows, uniir_topk_ip_sweep_queries(dim, rows));
+    TkShardPlan p;
+    tk_plan_shard(rows, dim, nq, k, uniir_topk_ip_sweep_queries(dim, rows), 0, &p);
+    return p.bytes;
 }
-extern "C" int uniir_topk_ip(const void* pool_f16, const float* pool_inv_norm, const int64_t* pool_ids, int64_t rows,
-                             int32_t dim, const void* queries_f16, int32_t nq, int32_t k, float* out_scores,
-                             int64_t* out_ids, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (!pool_f16 || !pool_inv_norm || !queries_f16 || !out_scores || !out_ids || !workspace) return UNIIR_EINVAL;
-    if (rows <= 0 || nq <= 0 || k <= 0) return UNIIR_EINVAL;
-    if (k + 8 > TK_MAXKC || dim % 64 || dim <= 0 || rows > 0x7fffffffL) return UNIIR_ESHAPE;
-    // a shard is addressed through 31-bit buffer offsets: >= 2 GiB of rows is searched as equal sub-shards by the caller
-    // (uniir_topk_ip_multi below: the 5.6 M x 768 pool on one GPU = 8 logical sub-shards), never silently by a slower path
-    if (rows * (int64_t)dim * 2 >= ((int64_t)1 << 31)) return UNIIR_ESHAPE;
-    if (((uintptr_t)pool_f16 & 15) || ((uintptr_t)queries_f16 & 15) || ((uintptr_t)pool_inv_norm & 15) ||
-        ((uintptr_t)workspace & 255))
-        return UNIIR_EALIGN;
-    if (workspace_bytes < uniir_topk_ip_workspace_bytes_ex(nq, k, rows, dim)) return UNIIR_EINVAL;
-    const int chunk_max = uniir_topk_ip_sweep_queries(dim, rows);
-    const int chunk = nq < chunk_max ? nq : chunk_max;
-    const int kc = k + 8;
-    const int ncand = uniir_topk_ncand(chunk, kc);
+// the sweeps of one planned shard search; every shape question was answered by the plan
+static int tk_search_shard(const TkShardPlan& p, const void* pool_f16, const float* pool_inv_norm, const int64_t* pool_ids, int32_t dim,
+                           const void* queries_f16, int32_t nq, int32_t k, float* out_scores, int64_t* out_ids, void* workspace,
+                           void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    float* gmax = (float*)ws;
-    const int64_t gbytes = (uniir_topk_workspace_bytes(chunk, kc, rows) + 255) & ~(int64_t)255;
-    float* qinv = (float*)(ws + gbytes);
-    int32_t* cand = (int32_t*)(ws + gbytes + (((int64_t)nq * 4 + 255) & ~(int64_t)255));
-    float* exact = (float*)((char*)cand + (((int64_t)chunk * ncand * 4 + 255) & ~(int64_t)255));
-    int rc = UNIIR_OK;
+    float* gmax = (float*)(ws + p.gmax.off);
+    float* qinv = (float*)(ws + p.qinv.off);
+    int32_t* cand = (int32_t*)(ws + p.cand.off);
+    float* exact = (float*)(ws + p.exact.off);
     bool have_qinv = false;
-    // (One tail per BATCH of sweeps -- the scans of four 256-query sweeps writing their maxima side by side, then one fused tail and
-    // one sort for the 1024 queries -- was built and measured in round 4: 1024 queries 1.262 ms vs 1.24-1.27, 100 000 queries 123.8 vs
-    // 124.3 ms.  The tail is throughput-bound, not launch-bound; dropped.)
-    for (int lo = 0; lo < nq; lo += chunk) {
-        const int n = nq - lo < chunk ? nq - lo : chunk;
+    for (int lo = 0; lo < nq; lo += p.chunk) {
+        const TkSweep& s = nq - lo < p.chunk ? p.rem : p.full;
         const unsigned short* qp = (const unsigned short*)queries_f16 + (long)lo * dim;
-        if (n <= TK_GPATH_MAXQ) {       // group-max scan, then the fused tail (selection + query norm + exact re-score | sort)
-            // the per-wave maxima live behind the group maxima of this sweep (uniir_topk_workspace_bytes reserves the room)
-            const int64_t ngr = (rows + TK_G - 1) / TK_G;
-            float* wmax = (float*)(((uintptr_t)(gmax + (int64_t)n * ngr) + 255) & ~(uintptr_t)255);
-            int nw = 0;
-            const int sel = launch_gmax_scan(pool_f16, pool_inv_norm, rows, dim, qp, n, gmax, (hipStream_t)stream, wmax, &nw);
-            if (sel < 0) return sel;
-            if (sel >= 1 && launch_fused_tail(pool_f16, pool_inv_norm, pool_ids, rows, dim, qp, n, kc, k, gmax, cand, exact,
-                                              out_scores + (long)lo * k, out_ids + (long)lo * k, (hipStream_t)stream, wmax, nw)) {
-                HIP_LAUNCH_CHECK();
-                continue;
-            }
-            rc = topk_select_after_scan(sel, gmax, rows, n, kc, cand, (hipStream_t)stream);
+        float* os = out_scores + (long)lo * k;
+        int64_t* oi = out_ids + (long)lo * k;
+        float* wmax = (float*)(ws + s.wmax_off);
+        int rc = launch_scan(s, pool_f16, pool_inv_norm, p.rows, dim, qp, gmax, wmax, st);
+        if (rc) return rc;
+        if (s.fused) {
+            rc = launch_fused_tail(s, pool_f16, pool_inv_norm, pool_ids, p.rows, dim, qp, p.kc, k, gmax, wmax, cand, exact, os, oi, st);
             if (rc) return rc;
-        } else {
-            rc = uniir_topk_coarse(pool_f16, pool_inv_norm, rows, dim, qp, n, kc, cand, nullptr, gmax, gbytes, stream);
-            if (rc) return rc;
+            continue;
         }
+        rc = launch_select(s, gmax, p.rows, p.kc, cand, st);
+        if (rc) return rc;
         if (!have_qinv) {               // the unfused tail reads the query norms from a separate pass
             rc = uniir_pool_inv_norms(queries_f16, nq, dim, qinv, stream);
             if (rc) return rc;
             have_qinv = true;
         }
-        rc = uniir_topk_rescore(pool_f16, pool_inv_norm, pool_ids, rows, dim, qp, qinv + lo, n, cand, ncand, k, exact,
-                                out_scores + (long)lo * k, out_ids + (long)lo * k, stream);
+        rc = uniir_topk_rescore(pool_f16, pool_inv_norm, pool_ids, p.rows, dim, qp, qinv + lo, s.n, cand, s.ncand, k, exact, os, oi, stream);
         if (rc) return rc;
     }
     return UNIIR_OK;
+}
+extern "C" int uniir_topk_ip(const void* pool_f16, const float* pool_inv_norm, const int64_t* pool_ids, int64_t rows,
+                             int32_t dim, const void* queries_f16, int32_t nq, int32_t k, float* out_scores,
+                             int64_t* out_ids, void* workspace, int64_t workspace_bytes, void* stream) {
+    const int rc = tk_check(pool_f16, pool_inv_norm, queries_f16, out_scores && out_ids ? out_scores : nullptr, workspace, rows, dim, nq, k,
+                            k + 8, 64, true, 256);
+    if (rc) return rc;
+    if (workspace_bytes < uniir_topk_ip_workspace_bytes_ex(nq, k, rows, dim)) return UNIIR_EINVAL;
+    const int ncu = tk_cu_count();
+    if (ncu < 0) return UNIIR_ELAUNCH;
+    TkShardPlan p;
+    tk_plan_shard(rows, dim, nq, k, uniir_topk_ip_sweep_queries(dim, rows), ncu, &p);
+    return tk_search_shard(p, pool_f16, pool_inv_norm, pool_ids, dim, queries_f16, nq, k, out_scores, out_ids, workspace, stream);
 }
 
 // -------------------------------------------------------------------------------------------------------------
@@ -1393,122 +1444,96 @@ extern "C" int uniir_topk_ip(const void* pool_f16, const float* pool_inv_norm, c
 //   ONE fused tail launch for all sub-shards (workgroup (query, part, sub-shard), TkMulti),
 //   ONE sort launch (a k-list per (sub-shard, query)),
 //   ONE merge launch on (score desc, id asc) -- uniir_topk_merge's kernel; ids are unique, so this IS the search of the whole shard.
-// Round 4 ran the three launches of uniir_topk_ip per sub-shard from the host and merged at the end: 5 x (27 + 8) us of latency-bound
-// tails behind 5 scans (64 queries: 1.88 ms = 0.571 of 8 TB/s over the 8.6-GB pool); here the tails of all sub-shards run side by side.
-// A shape the batched tail does not take (a last sub-shard with an odd number of groups, k + 8 > 64 ...) falls back to exactly that
-// loop -- same results.  A shard below both bounds is one uniir_topk_ip call.
+// or, for a shape the batched tail does not take, one uniir_topk_ip search per sub-shard and one merge at the end (same results).
+// Which of the two a shape gets is the plan's decision (tk_plan), taken before the first launch.  A shard below both bounds is one
+// uniir_topk_ip call.
 // -------------------------------------------------------------------------------------------------------------
-extern "C" int64_t uniir_topk_subshard_rows(int64_t rows, int32_t dim) {
-    if (rows <= 0 || dim <= 0) return 0;
-    if (rows * (int64_t)dim * 2 < ((int64_t)1 << 31)) return rows;
-    const int64_t fused = 1024L * 2 * TK_SELREG * TK_G;                       // the fused tail's register-resident selection
-    int64_t cap = ((((int64_t)1 << 31) - 1) / ((int64_t)dim * 2)) / 32 * 32;
-    if (cap > fused) cap = fused;
-    const int64_t parts = (rows + cap - 1) / cap;
-    return ((rows + parts - 1) / parts + 31) / 32 * 32;
-}
-static int64_t tkm_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
-struct TkmPlan {
-    int64_t per; int nsub; int chunk; int kc; int ncand;
-    int64_t g_bytes, w_bytes, c_bytes, o_bytes, inner_bytes;     // per sub-shard regions (aligned); inner = one uniir_topk_ip call's scratch
-};
-static void tkm_plan(int32_t nq, int32_t k, int64_t rows, int32_t dim, TkmPlan* p) {
-    p->per = uniir_topk_subshard_rows(rows, dim);
-    p->nsub = (int)((rows + p->per - 1) / p->per);
-    const int chunk_max = uniir_topk_ip_sweep_queries(dim, p->per);
-    p->chunk = nq < chunk_max ? nq : chunk_max;
-    p->kc = k + 8;
-    p->ncand = uniir_topk_ncand(p->chunk, p->kc);
-    const int64_t ngr = (p->per + TK_G - 1) / TK_G;
-    p->g_bytes = tkm_align((int64_t)p->chunk * ngr * 4);
-    p->w_bytes = tkm_align(TK_WMAX_BYTES(p->chunk <= 256 ? p->chunk : 64));
-    p->c_bytes = tkm_align((int64_t)p->chunk * p->ncand * 4);
-    p->o_bytes = tkm_align((int64_t)p->chunk * k * 8);
-    p->inner_bytes = tkm_align(uniir_topk_ip_workspace_bytes_ex(nq, k, p->per, dim));
-}
 extern "C" int64_t uniir_topk_ip_multi_workspace_bytes(int32_t nq, int32_t k, int64_t rows, int32_t dim) {
     if (nq <= 0 || k <= 0 || rows <= 0 || dim <= 0) return 0;
-    if (rows * (int64_t)dim * 2 < ((int64_t)1 << 31)) return uniir_topk_ip_workspace_bytes_ex(nq, k, rows, dim);
-    TkmPlan p;
-    tkm_plan(nq, k, rows, dim, &p);
-    const int64_t batched = p.nsub * (p.g_bytes + p.w_bytes + 2 * p.c_bytes + 2 * p.o_bytes);
-    const int64_t fallback = p.inner_bytes + 2 * p.nsub * tkm_align((int64_t)nq * k * 8);       // per-sub-shard lists of all queries
-    return (batched > fallback ? batched : fallback) + 256;
+    TkPlan p;
+    tk_plan(rows, dim, nq, k, 0, &p);
+    return p.bytes;
+}
+// the query for tests and tools: what a uniir_topk_ip / uniir_topk_ip_multi search of this shape launches on a device with ncu
+// compute units, and where its scratch lies
+extern "C" int uniir_topk_plan(int64_t rows, int32_t dim, int32_t nq, int32_t k, int32_t ncu, uniir_topk_plan_t* out) {
+    if (!out || rows <= 0 || dim <= 0 || nq <= 0 || k <= 0 || ncu <= 0) return UNIIR_EINVAL;
+    if (k + 8 > TK_MAXKC || dim % 64 || rows > 0x7fffffffL) return UNIIR_ESHAPE;
+    TkPlan p;
+    tk_plan(rows, dim, nq, k, ncu, &p);
+    const TkShardPlan& a = p.sub[0];
+    const TkSweep& f = p.batched ? p.full : a.full;
+    const TkSweep& r = p.batched ? p.rem : a.rem;
+    *out = {};
+    out->scan = f.scan, out->waves = f.nw, out->tail = f.fused, out->select = f.fused ? f.parts : f.sel;
+    out->rem_queries = r.n, out->rem_scan = r.scan, out->rem_waves = r.nw, out->rem_tail = r.fused, out->rem_select = r.fused ? r.parts : r.sel;
+    out->sweep_queries = a.chunk, out->ncand = f.ncand;
+    out->nsub = p.nsub, out->batched = p.batched, out->subshard_rows = p.per, out->last_rows = p.last_rows;
+    out->workspace_bytes = p.bytes;
+    if (p.batched) {
+        out->gmax_bytes = p.nsub * p.gmax.bytes, out->wmax_bytes = p.nsub * p.wmax.bytes, out->cand_bytes = p.nsub * p.cand.bytes;
+        out->exact_bytes = p.nsub * p.exact.bytes, out->lists_bytes = 2 * p.nsub * p.list_s.bytes;
+    } else {                                  // one uniir_topk_ip search (per sub-shard): the wave maxima lie inside the first region
+        out->gmax_bytes = a.gmax.bytes, out->qinv_bytes = a.qinv.bytes, out->cand_bytes = a.cand.bytes, out->exact_bytes = a.exact.bytes;
+        out->lists_bytes = p.nsub > 1 ? 2 * p.all_s.bytes : 0;
+    }
+    return UNIIR_OK;
 }
 extern "C" int uniir_topk_ip_multi(const void* pool_f16, const float* pool_inv_norm, const int64_t* pool_ids, int64_t rows,
                                    int32_t dim, const void* queries_f16, int32_t nq, int32_t k, float* out_scores,
                                    int64_t* out_ids, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (!pool_f16 || !pool_inv_norm || !queries_f16 || !out_scores || !out_ids || !workspace) return UNIIR_EINVAL;
-    if (rows <= 0 || nq <= 0 || k <= 0) return UNIIR_EINVAL;
-    if (rows * (int64_t)dim * 2 < ((int64_t)1 << 31))
+    int rc = tk_check(pool_f16, pool_inv_norm, queries_f16, out_scores && out_ids ? out_scores : nullptr, workspace, rows, dim, nq, k,
+                      k + 8, 64, false, 256);
+    if (rc) return rc;
+    if (tk_fits31(rows, dim, 2))
         return uniir_topk_ip(pool_f16, pool_inv_norm, pool_ids, rows, dim, queries_f16, nq, k, out_scores, out_ids, workspace,
                              workspace_bytes, stream);
-    if (k + 8 > TK_MAXKC || dim % 64 || dim <= 0 || rows > 0x7fffffffL) return UNIIR_ESHAPE;
-    if (((uintptr_t)pool_f16 & 15) || ((uintptr_t)queries_f16 & 15) || ((uintptr_t)pool_inv_norm & 15) || ((uintptr_t)workspace & 255))
-        return UNIIR_EALIGN;
     if (workspace_bytes < uniir_topk_ip_multi_workspace_bytes(nq, k, rows, dim)) return UNIIR_EINVAL;
-    TkmPlan p;
-    tkm_plan(nq, k, rows, dim, &p);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t last_rows = rows - (int64_t)(p.nsub - 1) * p.per;
-    const int64_t last_groups = (last_rows + TK_G - 1) / TK_G;
-    // the batched tail wants every sub-shard on a streaming scan with wave maxima and on the fused tail (<= 256 queries per sweep)
-    const bool big = (dim == 768 || dim == 512) && last_groups >= 2048 && last_groups % 2 == 0 && p.chunk <= 256 &&
-                     (p.chunk <= 64 || stream_shared_ok(dim, p.per, p.chunk)) && (p.chunk <= 64 || stream_shared_ok(dim, last_rows, p.chunk)) &&
-                     fused_tail_ok(p.per, dim, p.kc) && fused_tail_ok(last_rows, dim, p.kc) && p.nsub <= 64;
     if (!pool_ids) return UNIIR_EINVAL;          // (local row numbers of different sub-shards cannot be merged)
+    const int ncu = tk_cu_count();
+    if (ncu < 0) return UNIIR_ELAUNCH;
+    TkPlan p;
+    tk_plan(rows, dim, nq, k, ncu, &p);
+    hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    // the per-sub-shard loop of round 4, on the device side of the ABI: lists [nsub][nq][k], one merge.  Also the way out when the
-    // batched path refuses a shape (same results: both end in the exact re-score and the same merge rule)
-    auto per_sub_shard = [&]() -> int {
-        float* ls = (float*)(ws + p.inner_bytes);
-        int64_t* li = (int64_t*)(ws + p.inner_bytes + p.nsub * tkm_align((int64_t)nq * k * 8));
+    const unsigned short* pool = (const unsigned short*)pool_f16;
+    if (!p.batched) {                            // one planned uniir_topk_ip search per sub-shard: lists [nsub][nq][k], one merge
+        float* ls = (float*)(ws + p.all_s.off);
+        int64_t* li = (int64_t*)(ws + p.all_i.off);
         for (int z = 0; z < p.nsub; ++z) {
-            const int64_t lo = (int64_t)z * p.per, n = z == p.nsub - 1 ? last_rows : p.per;
-            const int rc = uniir_topk_ip((const unsigned short*)pool_f16 + lo * dim, pool_inv_norm + lo, pool_ids ? pool_ids + lo : nullptr, n,
-                                         dim, queries_f16, nq, k, ls + (int64_t)z * nq * k, li + (int64_t)z * nq * k, ws, p.inner_bytes, stream);
+            const int64_t r0 = (int64_t)z * p.per;
+            rc = tk_search_shard(p.sub[z == p.nsub - 1], pool + r0 * dim, pool_inv_norm + r0, pool_ids + r0, dim, queries_f16, nq, k,
+                                 ls + (int64_t)z * nq * k, li + (int64_t)z * nq * k, ws + p.inner.off, stream);
             if (rc) return rc;
         }
         return uniir_topk_merge(ls, li, p.nsub, nq, k, out_scores, out_ids, stream);
-    };
-    if (!big) return per_sub_shard();
-    // the per-wave maxima (hierarchical selection) exist only when EVERY sub-shard's scan writes them: the rule depends on the
-    // sub-shard's group count and the device's CU count, and the shorter last sub-shard may disagree with the full ones
-    const int ncu = tk_cu_count();
-    if (ncu < 0) return UNIIR_ELAUNCH;
-    auto waves_ok = [&](int64_t r) { const long ng = (r + TK_G - 1) / TK_G; return ncu * 4 <= 1024 && (ng + ncu * 4 - 1) / (ncu * 4) <= 64; };
-    const bool use_wmax = waves_ok(p.per) && waves_ok(last_rows);
-    float* gmax = (float*)ws;
-    float* wmax = (float*)(ws + p.nsub * p.g_bytes);
-    int32_t* cand = (int32_t*)(ws + p.nsub * (p.g_bytes + p.w_bytes));
-    float* exact = (float*)((char*)cand + p.nsub * p.c_bytes);
-    float* ls = (float*)((char*)exact + p.nsub * p.c_bytes);
-    int64_t* li = (int64_t*)((char*)ls + p.nsub * p.o_bytes);
+    }
+    float* gmax = (float*)(ws + p.gmax.off);
+    float* wmax = (float*)(ws + p.wmax.off);
+    int32_t* cand = (int32_t*)(ws + p.cand.off);
+    float* exact = (float*)(ws + p.exact.off);
+    float* ls = (float*)(ws + p.list_s.off);
+    int64_t* li = (int64_t*)(ws + p.list_i.off);
     TkMulti mu;
     mu.per = p.per;
     mu.rows_total = rows;
-    mu.g_stride = p.g_bytes / 4;
-    mu.w_stride = p.w_bytes / 4;
-    mu.c_stride = p.c_bytes / 4;
-    for (int lo = 0; lo < nq; lo += p.chunk) {
-        const int n = nq - lo < p.chunk ? nq - lo : p.chunk;
+    mu.g_stride = p.gmax.bytes / 4;
+    mu.w_stride = p.wmax.bytes / 4;
+    mu.c_stride = p.cand.bytes / 4;
+    const int chunk = p.sub[0].chunk;
+    for (int lo = 0; lo < nq; lo += chunk) {
+        const TkSweep& s = nq - lo < chunk ? p.rem : p.full;       // (the same scan for every sub-shard: that is what batched means)
         const unsigned short* qp = (const unsigned short*)queries_f16 + (long)lo * dim;
-        int nw = 0;
         for (int z = 0; z < p.nsub; ++z) {
-            const int64_t r0 = (int64_t)z * p.per, nr = z == p.nsub - 1 ? last_rows : p.per;
-            int nwz = 0;
-            const int sel = launch_gmax_scan((const unsigned short*)pool_f16 + r0 * dim, pool_inv_norm + r0, nr, dim, qp, n,
-                                             gmax + z * mu.g_stride, st, use_wmax ? wmax + z * mu.w_stride : nullptr, &nwz);
-            if (sel < 0) return sel;
-            if (sel < 1 || (z > 0 && nwz != nw)) return per_sub_shard();       // a scan the batched tail cannot follow: start over
-            if (z == 0) nw = nwz;
+            const int64_t r0 = (int64_t)z * p.per;
+            rc = launch_scan(s, pool + r0 * dim, pool_inv_norm + r0, z == p.nsub - 1 ? p.last_rows : p.per, dim, qp, gmax + z * mu.g_stride,
+                             wmax + z * mu.w_stride, st);
+            if (rc) return rc;
         }
-        mu.o_stride = (long)n * k;
-        if (!launch_fused_tail(pool_f16, pool_inv_norm, pool_ids, p.per, dim, qp, n, p.kc, k, gmax, cand, exact, ls, li, st,
-                               nw > 0 ? wmax : nullptr, nw, &mu, p.nsub))
-            return per_sub_shard();
-        HIP_LAUNCH_CHECK();
-        const int rc = uniir_topk_merge(ls, li, p.nsub, n, k, out_scores + (long)lo * k, out_ids + (long)lo * k, stream);
+        mu.o_stride = (long)s.n * k;
+        rc = launch_fused_tail(s, pool_f16, pool_inv_norm, pool_ids, p.per, dim, qp, p.sub[0].kc, k, gmax, wmax, cand, exact, ls, li, st, &mu, p.nsub);
+        if (rc) return rc;
+        rc = uniir_topk_merge(ls, li, p.nsub, s.n, k, out_scores + (long)lo * k, out_ids + (long)lo * k, stream);
         if (rc) return rc;
     }
     return UNIIR_OK;

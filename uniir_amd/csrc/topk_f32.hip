@@ -274,14 +274,21 @@ static int tkf_chunk_max() {
     const int c = tk_sweep_override();
     return c ? c : TK_GPATH_MAXQ;
 }
-static int64_t tkf_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
+struct TkfLayout { int chunk; int64_t qinv, cand, exact, bytes; };       // sweep width; byte offsets (group maxima at 0); total
+static TkfLayout tkf_layout(int32_t nq, int32_t k, int64_t rows) {
+    TkfLayout l;
+    const int chunk_max = tkf_chunk_max();
+    l.chunk = nq < chunk_max ? nq : chunk_max;
+    const int64_t cbytes = tk_align256((int64_t)l.chunk * TK_GMULT * (k + 8) * TK_G * 4);
+    l.qinv = tk_align256((int64_t)l.chunk * tk_groups(rows) * 4);
+    l.cand = l.qinv + tk_align256((int64_t)nq * 4);
+    l.exact = l.cand + cbytes;
+    l.bytes = l.exact + cbytes + 256;
+    return l;
+}
 extern "C" int64_t uniir_topk_ip_f32_workspace_bytes(int32_t nq, int32_t k, int64_t rows, int32_t dim) {
     if (nq <= 0 || k <= 0 || rows <= 0 || dim <= 0) return 0;
-    const int chunk_max = tkf_chunk_max();
-    const int64_t chunk = nq < chunk_max ? nq : chunk_max;
-    const int64_t ngroups = (rows + TK_G - 1) / TK_G;
-    const int64_t ncand = (int64_t)TK_GMULT * (k + 8) * TK_G;
-    return tkf_align(chunk * ngroups * 4) + tkf_align((int64_t)nq * 4) + 2 * tkf_align(chunk * ncand * 4) + 256;
+    return tkf_layout(nq, k, rows).bytes;
 }
 
 extern "C" int uniir_topk_ip_f32(const float* pool_f32, const float* pool_inv_norm, const int64_t* pool_ids, int64_t rows,
@@ -291,20 +298,20 @@ extern "C" int uniir_topk_ip_f32(const float* pool_f32, const float* pool_inv_no
     if (rows <= 0 || nq <= 0 || k <= 0) return UNIIR_EINVAL;
     if (k + 8 > TK_MAXKC || dim % 64 || dim <= 0 || rows > 0x7fffffffL) return UNIIR_ESHAPE;
     // the same cut as the fp16 search: >= 2 GiB of rows is searched as equal sub-shards by the caller (retrieval.subshard_bounds)
-    if (rows * (int64_t)dim * 4 >= ((int64_t)1 << 31)) return UNIIR_ESHAPE;
+    if (!tk_fits31(rows, dim, 4)) return UNIIR_ESHAPE;
     if (((uintptr_t)pool_f32 & 15) || ((uintptr_t)queries_f32 & 15) || ((uintptr_t)pool_inv_norm & 15) || ((uintptr_t)workspace & 255))
         return UNIIR_EALIGN;
-    if (workspace_bytes < uniir_topk_ip_f32_workspace_bytes(nq, k, rows, dim)) return UNIIR_EINVAL;
+    const TkfLayout l = tkf_layout(nq, k, rows);
+    if (workspace_bytes < l.bytes) return UNIIR_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const int chunk_max = tkf_chunk_max();
-    const int chunk = nq < chunk_max ? nq : chunk_max;
+    const int chunk = l.chunk;
     const int kc = k + 8, gcap = TK_GMULT * kc, ncand = gcap * TK_G;
-    const long ngroups = (rows + TK_G - 1) / TK_G;
+    const long ngroups = (long)tk_groups(rows);
     char* ws = (char*)workspace;
     float* gmax = (float*)ws;
-    float* qinv = (float*)(ws + tkf_align((int64_t)chunk * ngroups * 4));
-    int32_t* cand = (int32_t*)((char*)qinv + tkf_align((int64_t)nq * 4));
-    float* exact = (float*)((char*)cand + tkf_align((int64_t)chunk * ncand * 4));
+    float* qinv = (float*)(ws + l.qinv);
+    int32_t* cand = (int32_t*)(ws + l.cand);
+    float* exact = (float*)(ws + l.exact);
     int rc = uniir_pool_inv_norms_f32(queries_f32, nq, dim, qinv, stream);
     if (rc) return rc;
     const long tiles_c = (rows + 127) / 128;
@@ -325,7 +332,7 @@ extern "C" int uniir_topk_ip_f32(const float* pool_f32, const float* pool_inv_no
             hipLaunchKernelGGL((topk_gmax_f32_kernel<8>), dim3((unsigned)(tiles_c * tiles_q)), dim3(256), 0, st, pool_f32,
                                pool_inv_norm, (long)rows, dim, qp, n, gmax, ngroups, tiles_q);
         }
-        if (ngroups % 2 == 0 && ngroups <= 1024L * 2 * TK_SELREG)
+        if (tk_sel_reg_ok(rows))
             hipLaunchKernelGGL((topk_gsel_f32_kernel<true>), dim3(n), dim3(1024), 0, st, gmax, ngroups, (long)rows, qinv + lo, dim, kc, k,
                                gcap, cand);
         else
@@ -334,8 +341,8 @@ extern "C" int uniir_topk_ip_f32(const float* pool_f32, const float* pool_inv_no
         const long pairs = (long)n * ncand;
         hipLaunchKernelGGL(rescore_f32_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, pool_f32, pool_inv_norm, qp,
                            qinv + lo, n, dim, cand, ncand, exact);
-        launch_tail_sort(exact, cand, pool_ids, n, ncand, k, out_scores + (long)lo * k, out_ids + (long)lo * k, st);
-        HIP_LAUNCH_CHECK();
+        rc = launch_tail_sort(exact, cand, pool_ids, n, ncand, k, out_scores + (long)lo * k, out_ids + (long)lo * k, st);
+        if (rc) return rc;                  // (its launch check covers the sweep's launches)
     }
     return UNIIR_OK;
 }

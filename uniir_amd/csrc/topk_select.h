@@ -55,6 +55,8 @@ struct GselBound {
 };
 #define TK_SELCAP 1024
 #define TK_SELREG 24    // float2 loads per thread of the register-resident variant: ngroups <= 1024 * 2 * 24
+// host: does the register-resident variant (REG) take a query's row of group maxima?  float2 loads, TK_SELREG of them per thread
+static inline bool tk_sel_reg_ok(int64_t rows) { return tk_groups(rows) % 2 == 0 && tk_groups(rows) <= 1024L * 2 * TK_SELREG; }
 // REG (the interactive <= 64-query path, one 1024-thread block per query): the query's group maxima are read ONCE, as
 // back-to-back 8-byte loads that all stay in flight, and both passes (thread maxima, collection above the threshold) run
 // on registers -- the two dependent strided passes over global memory were 40 of the kernel's 62 us at 700 k rows.

@@ -227,19 +227,15 @@ extern "C" int uniir_topk_rescore(const void* pool_f16, const float* pool_inv_no
     if (dim <= 0 || dim % 8) return UNIIR_ESHAPE;
     if (((uintptr_t)pool_f16 & 15) || ((uintptr_t)queries_f16 & 15)) return UNIIR_EALIGN;      // both kernels read rows 16 bytes at a time
     hipStream_t st = (hipStream_t)stream;
-    const long pairs = (long)nq * ncand;
-    if (dim % 64 == 0)
-        hipLaunchKernelGGL(rescore_coalesced_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st,
-                           (const unsigned short*)pool_f16, pool_inv_norm, (const unsigned short*)queries_f16,
-                           query_inv_norm, nq, dim, cand_idx, ncand, exact_ws);
-    else
-        hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st,
-                           (const unsigned short*)pool_f16, pool_inv_norm, (const unsigned short*)queries_f16,
-                           query_inv_norm, nq, dim, cand_idx, ncand, exact_ws);
-    hipLaunchKernelGGL(final_sort_kernel, dim3(nq), dim3(256), 0, st, exact_ws, cand_idx,
-                       (const long long*)pool_ids, nq, ncand, k, out_scores, (long long*)out_ids);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
+    const unsigned short* pool = (const unsigned short*)pool_f16;
+    const unsigned short* q = (const unsigned short*)queries_f16;
+    const dim3 grid((unsigned)(((long)nq * ncand + 255) / 256));
+    // rows of whole 128-byte lines go through the wave's LDS slab
+    const int rc = dim % 64 == 0 ? tk_launch<rescore_coalesced_kernel>(grid, dim3(256), 0, st, pool, pool_inv_norm, q, query_inv_norm, nq, dim, cand_idx, ncand, exact_ws)
+                                 : tk_launch<rescore_kernel>(grid, dim3(256), 0, st, pool, pool_inv_norm, q, query_inv_norm, nq, dim, cand_idx, ncand, exact_ws);
+    if (rc) return rc;
+    return tk_launch<final_sort_kernel>(dim3(nq), dim3(256), 0, st, (const float*)exact_ws, cand_idx, (const long long*)pool_ids, nq, ncand, k, out_scores,
+                                        (long long*)out_ids);
 }
 
 // k-way merge of per-shard final results (score desc, id asc); ids are unique across shards.
@@ -304,30 +300,25 @@ __global__ __launch_bounds__(256) void merge_shards_kernel(const float* __restri
         else { os[(long)q * k + j] = -INFINITY; oi[(long)q * k + j] = -1; last_s = -INFINITY; last_id = 0x7fffffffffffffffLL; }
     }
 }
-static void launch_merge(const float* scores, const int64_t* ids, int nshard, int nq, int kin, int k, float* out_scores,
-                         int64_t* out_ids, hipStream_t st) {
-    if ((long)nshard * kin <= MERGE_CAP)
-        hipLaunchKernelGGL(merge_rank_kernel, dim3(nq), dim3(256), 0, st, scores, (const long long*)ids, nshard, nq, kin, k, out_scores,
-                           (long long*)out_ids);
-    else
-        hipLaunchKernelGGL(merge_shards_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, scores, (const long long*)ids, nshard, nq,
-                           kin, k, out_scores, (long long*)out_ids);
+static int launch_merge(const float* scores, const int64_t* ids, int nshard, int nq, int kin, int k, float* out_scores,
+                        int64_t* out_ids, hipStream_t st) {
+    if ((long)nshard * kin <= MERGE_CAP)          // the entries of a query fit the rank kernel's LDS
+        return tk_launch<merge_rank_kernel>(dim3(nq), dim3(256), 0, st, scores, (const long long*)ids, nshard, nq, kin, k, out_scores,
+                                            (long long*)out_ids);
+    return tk_launch<merge_shards_kernel>(dim3((nq + 255) / 256), dim3(256), 0, st, scores, (const long long*)ids, nshard, nq, kin, k,
+                                          out_scores, (long long*)out_ids);
 }
 extern "C" int uniir_topk_merge(const float* scores, const int64_t* ids, int32_t nshard, int32_t nq, int32_t k,
                                 float* out_scores, int64_t* out_ids, void* stream) {
     if (!scores || !ids || !out_scores || !out_ids || nshard <= 0 || nq <= 0 || k <= 0) return UNIIR_EINVAL;
-    launch_merge(scores, ids, nshard, nq, k, k, out_scores, out_ids, (hipStream_t)stream);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
+    return launch_merge(scores, ids, nshard, nq, k, k, out_scores, out_ids, (hipStream_t)stream);
 }
 // the same with lists of k_in entries per shard merged into the k_out best (k_out may exceed k_in: a large-k search
 // assembled from slices of the pool, uniir_amd/retrieval.py)
 extern "C" int uniir_topk_merge_ex(const float* scores, const int64_t* ids, int32_t nshard, int32_t nq, int32_t k_in,
                                    int32_t k_out, float* out_scores, int64_t* out_ids, void* stream) {
     if (!scores || !ids || !out_scores || !out_ids || nshard <= 0 || nq <= 0 || k_in <= 0 || k_out <= 0) return UNIIR_EINVAL;
-    launch_merge(scores, ids, nshard, nq, k_in, k_out, out_scores, out_ids, (hipStream_t)stream);
-    HIP_LAUNCH_CHECK();
-    return UNIIR_OK;
+    return launch_merge(scores, ids, nshard, nq, k_in, k_out, out_scores, out_ids, (hipStream_t)stream);
 }
 
 // -------------------------------------------------------------------------------------------------------------
@@ -572,7 +563,6 @@ __global__ __launch_bounds__(TKT_THREADS) void topk_tail_select_rescore_kernel(
 // kc-th best and its ties stay empty), then every live entry counts the entries that beat it (score desc, id asc); rank < k is the
 // answer.  1024 threads: one entry per thread, ~n / 16 trips of 16 compares each (the 256-thread, uncompacted form of this kernel
 // took 22 us: 576^2 compares on four waves).
-#define TKT_SORTCAP (2 * TK_MAXKC * TK_G)     // 2048 slots at most (gcap <= 128 groups)
 __global__ __launch_bounds__(1024) void topk_tail_sort_kernel(const float* __restrict__ exact, const int* __restrict__ cand,
                                                              const long long* __restrict__ ids, int ncand, int k,
                                                              float* __restrict__ out_s, long long* __restrict__ out_i, TkMulti mu) {
@@ -643,52 +633,33 @@ __global__ __launch_bounds__(1024) void topk_tail_sort_kernel(const float* __res
     }
 }
 
-void launch_tail_sort(const float* exact, const int32_t* cand, const int64_t* pool_ids, int32_t nq, int32_t ncand, int32_t k,
-                      float* out_scores, int64_t* out_ids, hipStream_t st) {
-    const TkMulti one = {};
-    hipLaunchKernelGGL(topk_tail_sort_kernel, dim3(nq, 1), dim3(1024), 0, st, exact, cand, (const long long*)pool_ids, ncand, k,
-                       out_scores, (long long*)out_ids, one);
+int launch_tail_sort(const float* exact, const int32_t* cand, const int64_t* pool_ids, int32_t nq, int32_t ncand, int32_t k,
+                     float* out_scores, int64_t* out_ids, hipStream_t st) {
+    return tk_launch<topk_tail_sort_kernel>(dim3(nq, 1), dim3(1024), 0, st, exact, (const int*)cand, (const long long*)pool_ids, ncand, k, out_scores,
+                                            (long long*)out_ids, TkMulti{});
 }
-// can the fused tail (selection + query norm + exact re-score | sort) serve this search?
-bool fused_tail_ok(int64_t rows, int32_t dim, int32_t kc) {
-    const long ngroups = (rows + TK_G - 1) / TK_G;
-    const int gcap = TK_GMULT * kc;
-    if (dim % 64 || dim > 4096 || ngroups % 2 || ngroups > 1024L * 2 * TK_SELREG || gcap * TK_G > TKT_SORTCAP || gcap > 2 * TK_MAXKC)
-        return false;
-    return rows * dim * 2 < (1L << 31);                                // the gather's 31-bit buffer bound
+// selection + exact re-score, then the sort, behind a finished scan: what the plan's sweep says (s.fused; the plan checked the
+// shape, the last sub-shard's included).  rows: of the (first) sub-shard -- in a batched tail every sub-shard but the last has this many.
+template <int P, int RW, int DEPTH>          // rings: RW waves x DEPTH slices of 8 KiB
+static int launch_tail_rescore(const TkSweep& s, const void* pool_f16, const float* pinv, int64_t rows, int32_t dim, const void* queries_f16,
+                               int32_t kc, int32_t k, const float* gmax, const float* wmax, int32_t* cand, float* exact, hipStream_t st,
+                               const TkMulti& mu, int nsub) {
+    // one workgroup per (query, part, sub-shard)
+    return tk_launch<topk_tail_select_rescore_kernel<P, RW, DEPTH>>(dim3(s.n, P, nsub), dim3(TKT_THREADS), RW * DEPTH * 8192, st,
+                                                                    (const unsigned short*)pool_f16, pinv, (long)rows, dim,
+                                                                    (const unsigned short*)queries_f16, gmax, (long)tk_groups(rows), kc,
+                                                                    TK_GMULT * kc, cand, exact, s.nw > 0 ? wmax : nullptr, s.nw, mu, k);
 }
-// selection + exact re-score + sort behind a finished scan (dense gmax [+ wave maxima]); false when the shape does not fit the
-// fused kernels
-bool launch_fused_tail(const void* pool_f16, const float* pinv, const int64_t* pool_ids, int64_t rows, int32_t dim,
-                              const void* queries_f16, int32_t nq, int32_t kc, int32_t k, const float* gmax, int32_t* cand,
-                              float* exact, float* out_scores, int64_t* out_ids, hipStream_t st, const float* wmax, int nw,
-                              const TkMulti* mu, int nsub) {
-    // rows: of the (first) sub-shard -- in a batched tail every sub-shard but the last has this many (the caller checked the last one)
-    const long ngroups = (rows + TK_G - 1) / TK_G;
-    const int gcap = TK_GMULT * kc;
-    if (!fused_tail_ok(rows, dim, kc)) return false;
-    TkMulti one = {};
-    if (!mu) { mu = &one; nsub = 1; }
-    // one workgroup per (query, part, sub-shard): the interactive regime spreads a query's re-score over PARTS workgroups; with
-    // several sub-shards in one launch the sub-shards already fill the chip
-    const int parts = nq * nsub <= 64 ? 4 : nq * nsub <= 128 ? 2 : 1;
-    const dim3 g(nq, parts, nsub), b(TKT_THREADS);
-#define TKT_LAUNCH(P, RW, DEPTH)                                                                                       \
-    do {                                                                                                               \
-        static PerDeviceOnce attr;                                                                                     \
-        if (attr.first())                                                                                              \
-            (void)hipFuncSetAttribute((const void*)topk_tail_select_rescore_kernel<P, RW, DEPTH>,                      \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, RW * DEPTH * 8192);                  \
-        hipLaunchKernelGGL((topk_tail_select_rescore_kernel<P, RW, DEPTH>), g, b, RW * DEPTH * 8192, st,               \
-                           (const unsigned short*)pool_f16, pinv, (long)rows, dim, (const unsigned short*)queries_f16, \
-                           gmax, ngroups, kc, gcap, cand, exact, nw > 0 ? wmax : nullptr, nw, *mu, k);                 \
-    } while (0)
-    // rings: 3 waves x 4 slices (the interactive regime: 144 slots per workgroup at k = 10) or 5 waves x 2 slices = 96 / 80 KiB
-    if (parts == 4) TKT_LAUNCH(4, 3, 4);
-    else if (parts == 2) TKT_LAUNCH(2, 5, 2);
-    else TKT_LAUNCH(1, 5, 2);
-#undef TKT_LAUNCH
-    hipLaunchKernelGGL(topk_tail_sort_kernel, dim3(nq, nsub), dim3(1024), 0, st, exact, cand, (const long long*)pool_ids,
-                       gcap * TK_G, k, out_scores, (long long*)out_ids, *mu);
-    return true;
+int launch_fused_tail(const TkSweep& s, const void* pool_f16, const float* pinv, const int64_t* pool_ids, int64_t rows, int32_t dim,
+                      const void* queries_f16, int32_t kc, int32_t k, const float* gmax, const float* wmax, int32_t* cand, float* exact,
+                      float* out_scores, int64_t* out_ids, hipStream_t st, const TkMulti* mu, int nsub) {
+    const TkMulti m = mu ? *mu : TkMulti{};
+    if (!mu) nsub = 1;
+    // 3 waves x 4 slices (the interactive regime: 144 slots per workgroup at k = 10) or 5 waves x 2 slices = 96 / 80 KiB
+    const int rc = s.parts == 4 ? launch_tail_rescore<4, 3, 4>(s, pool_f16, pinv, rows, dim, queries_f16, kc, k, gmax, wmax, cand, exact, st, m, nsub)
+                 : s.parts == 2 ? launch_tail_rescore<2, 5, 2>(s, pool_f16, pinv, rows, dim, queries_f16, kc, k, gmax, wmax, cand, exact, st, m, nsub)
+                                : launch_tail_rescore<1, 5, 2>(s, pool_f16, pinv, rows, dim, queries_f16, kc, k, gmax, wmax, cand, exact, st, m, nsub);
+    if (rc) return rc;
+    return tk_launch<topk_tail_sort_kernel>(dim3(s.n, nsub), dim3(1024), 0, st, (const float*)exact, (const int*)cand, (const long long*)pool_ids,
+                                            TK_GMULT * kc * TK_G, k, out_scores, (long long*)out_ids, m);
 }

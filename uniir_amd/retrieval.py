@@ -58,7 +58,9 @@ def _shard_view(shard, lo, hi):
 
 SUBSHARD_BYTES = 1 << 31     # the streaming scans and the fused tail address a shard's rows through 31-bit buffer offsets
 FUSED_TAIL_ROWS = 1024 * 2 * 24 * 16     # csrc/topk_select.h: the register-resident selection of the fused tail holds 1024 x 2 x
-                                         # TK_SELREG group maxima = 49 152 groups of 16 rows = 786 432 rows
+                                         # TK_SELREG group maxima = 49 152 groups of 16 rows = 786 432 rows.  subshard_bounds below is
+                                         # uniir_topk_subshard_rows in Python (it also serves 4-byte rows and a patched bound); the host
+                                         # suite holds the two together (tests/test_topk_refusals_host.py)
 
 
 def subshard_bounds(n, dim, itemsize=2):
