@@ -74,16 +74,30 @@ def _fakes():
     return fakes
 
 
-def _clip():
-    """what the CLIP launch sequences read of a CLIP module: its config, its store and the padded patch weights"""
+def _padded(st, name, width, P, half):
+    """what a model does to its store before the forward: the patch weight `name` registered for its padded copies and, for an fp16
+    forward, the fp16 copies brought up to date (nothing is launched here, and these calls are no part of a trace)"""
+    from uniir_amd import flat_store, ops
+    st.add_padded(name, width, 3 * P * P, flat_store.patch_kpad(P))
+    if half:
+        real, ops.call = ops.call, lambda *a: None
+        try:
+            st.half_shadow()
+        finally:
+            ops.call = real
+    return st
+
+
+def _clip(patches16, half):
+    """what the CLIP launch sequences read of a CLIP module: its config and its store, which holds the padded patch weights where
+    the case reads them (patches16: the 16-bit vision tower)"""
     from oracle import clip_oracle
     from uniir_amd import clip_model, flat_store
     cfg = clip_oracle.tiny_config(embed_dim=W, transformer_width=W, transformer_heads=HEADS)
     st = flat_store.FlatStore([(n, tuple(p.shape)) for n, p in clip_model.CLIP(cfg).named_parameters()], "cpu")
-    kpad = (3 * cfg["vision_patch_size"] ** 2 + 63) // 64 * 64
-    model = types.SimpleNamespace(cfg=cfg, _flat=st, kpad=kpad, recompute_blocks=False,
-                                  _conv16=torch.zeros(cfg["vision_width"], kpad, dtype=torch.bfloat16),
-                                  _conv16h=torch.zeros(cfg["vision_width"], kpad, dtype=torch.float16))
+    if patches16:
+        _padded(st, clip_model.CONV, cfg["vision_width"], cfg["vision_patch_size"], half)
+    model = types.SimpleNamespace(cfg=cfg, _flat=st, kpad=flat_store.patch_kpad(cfg["vision_patch_size"]), recompute_blocks=False)
     image = torch.zeros(2, 3, cfg["image_resolution"], cfg["image_resolution"])
     return model, st, image, torch.zeros(2, cfg["context_length"], dtype=torch.int32)
 
@@ -102,7 +116,7 @@ def _run(prec, what):
     ids, key_len = torch.zeros(K.M, K.L, dtype=torch.int32), torch.tensor(K.KEY_LEN, dtype=torch.int32)
     images = torch.zeros(2, 3, VIT["img_size"], VIT["img_size"])
     if what.startswith("clip"):
-        model, st, image, text = _clip()
+        model, st, image, text = _clip(what == "clipff-vision" and not f32, prec == "fp16")
         if what == "clip-image":
             return st, lambda: clip_model._encode_fp32(model, "image", image, st.p)
         if what == "clip-text":
@@ -120,8 +134,8 @@ def _run(prec, what):
         st = flat_store.FlatStore([("visual_encoder." + n, s) for n, s in bm.vit_param_shapes(VIT, VIT["img_size"])], "cpu")
         if f32:
             return st, lambda: bm.vit_forward_f32(st, "visual_encoder.", VIT, VIT["img_size"], images)
-        conv16 = torch.zeros(W, 768, dtype=dt)
-        return st, lambda: bm.vit_forward(st, conv16, "visual_encoder.", VIT, VIT["img_size"], images, False, dtype16=dt)
+        _padded(st, "visual_encoder." + bm.CONV, W, VIT["patch_size"], prec == "fp16")
+        return st, lambda: bm.vit_forward(st, "visual_encoder.", VIT, VIT["img_size"], images, False, dtype16=dt)
     if what.startswith("bert"):
         cross, pool = what != "bert-text", what == "bert-cross-pool"
         cfg = {**bm.MED_DEFAULT, **MED}
@@ -134,8 +148,9 @@ def _run(prec, what):
     ones = torch.ones(K.M, dtype=torch.int64)
     if f32:
         return st, lambda: model._encode_sf_f32(st, ids, key_len, images, ones, ones)
-    conv16, pack = torch.zeros(W, 768, dtype=dt), bm.TextPack.build(key_len, K.L)
-    return st, lambda: model._encode_sf(st, conv16, ids, key_len, images, ones, ones, False, pack, dt)
+    pack = bm.TextPack.build(key_len, K.L)
+    _padded(st, "visual_encoder." + bm.CONV, W, VIT["patch_size"], prec == "fp16")
+    return st, lambda: model._encode_sf(st, ids, key_len, images, ones, ones, False, pack, dt)
 
 
 def trace(name):

@@ -222,7 +222,7 @@ def test_guards_and_the_bf16_path_is_untouched(score_fusion):
     txt, img = batch["txt_batched"], batch["image_batched"]
     model = _model(score_fusion, med_cfg, vit_cfg).cuda().eval()
     emb0 = _encode(model, "bf16", txt, img)
-    assert model._online.h16_buf is None and model._conv16h is None          # bf16 users allocate nothing
+    assert model._online.h16_buf is None and model._online.half_bytes() == 0          # bf16 users allocate nothing
     model.precision = "fp16"
     model.train()
     with pytest.raises(RuntimeError, match="eval"):

@@ -196,7 +196,7 @@ def test_384_pixels_577_image_tokens_and_the_gate_tells_fp32_from_fp16(score_fus
         assert model.last_text_rows == (3 * L, 3 * L)          # the dense rows, whatever pack_text says
     assert model._online.h16_buf is not None          # fp16 built its shadow; fp32 reads the masters and builds none:
     fresh = _model(score_fusion, MED_384, VIT_384, embed_dim=32 if score_fusion else None, seed=5).cuda().eval()
-    assert torch.equal(_encode(fresh, "fp32", txt(), img.cuda(), masks), got) and fresh._online.h16_buf is None and fresh._conv16h is None
+    assert torch.equal(_encode(fresh, "fp32", txt(), img.cuda(), masks), got) and fresh._online.h16_buf is None and fresh._online.half_bytes() == 0
 
 
 def test_guards_on_the_device_and_the_bf16_path_is_untouched():

@@ -45,11 +45,11 @@ def test_g7_vit_forward_backward():
     model.zero_grad()
     st = model._online
     x = torch.from_numpy(z["x"]).cuda()
-    tok, T, stash = bm.vit_forward(st, model._conv16, "visual_encoder.", model.vit_cfg, model.image_size, x, True)
+    tok, T, stash = bm.vit_forward(st, "visual_encoder.", model.vit_cfg, model.image_size, x, True)
     y = torch.from_numpy(z["y"])
     assert rel(tok.float().view(y.shape), y) < 2e-2
     w = torch.from_numpy(z["w"]).cuda().view(-1, y.shape[-1]).contiguous()
-    bm.vit_backward(st, model._dconv, "visual_encoder.", model.vit_cfg, w, stash)
+    bm.vit_backward(st, "visual_encoder.", model.vit_cfg, w, stash)
     for k in z.files:
         if k.startswith("grad::"):
             g = st.grad_view("visual_encoder." + k[6:])

@@ -144,7 +144,7 @@ def test_guards_and_the_bf16_path_is_untouched():
     with torch.no_grad():
         emb0 = model.encode_multimodal_input(batch["txt_batched"], x).clone()
     tok0 = model._vit_tokens(x).clone()
-    assert model._online.h16_buf is None and model._conv16h is None          # bf16 users allocate nothing
+    assert model._online.h16_buf is None and model._online.half_bytes() == 0          # bf16 users allocate nothing
     with pytest.raises(RuntimeError, match="unknown precision"):
         model._vit_tokens(x, "fp32")
     model.train()
@@ -156,12 +156,12 @@ def test_guards_and_the_bf16_path_is_untouched():
     assert h.requires_grad is False
     st = model._online
     with pytest.raises(RuntimeError, match="save=True"):          # no fp16 stash: nothing to run a backward from
-        bm.vit_forward(st, model._conv16h, "visual_encoder.", model.vit_cfg, model.image_size, x, True, dtype16=torch.float16)
-    with pytest.raises(ValueError):          # the bf16 patch weight with an fp16 forward
-        bm.vit_forward(st, model._conv16, "visual_encoder.", model.vit_cfg, model.image_size, x, False, dtype16=torch.float16)
+        bm.vit_forward(st, "visual_encoder.", model.vit_cfg, model.image_size, x, True, dtype16=torch.float16)
+    # (an fp16 forward can no longer be handed the bf16 patch weight: vit_forward takes the one of its dtype16 from the store)
+    assert st.padded16h("visual_encoder.patch_embed.proj.weight").dtype == torch.float16 and st.half_bytes() > 2 * st.total
     # after fp16 was used: the bf16 tokens and the model's embeddings are what they were before, bit for bit
     assert torch.equal(model._vit_tokens(x, "bf16"), tok0)
     with torch.no_grad():
         assert torch.equal(model.encode_multimodal_input(batch["txt_batched"], x), emb0)
-    tok, T, _ = bm.vit_forward(st, model._conv16, "visual_encoder.", model.vit_cfg, model.image_size, x, False)
+    tok, T, _ = bm.vit_forward(st, "visual_encoder.", model.vit_cfg, model.image_size, x, False)
     assert torch.equal(tok.view(tok0.shape), tok0)

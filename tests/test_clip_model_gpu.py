@@ -488,3 +488,114 @@ def test_pooled_last_block_at_small_batches(pack_text, items):
         err = float((g_p[n] - g_f[n]).norm() / den)
         linear_bias = n.endswith("bias") and "ln_" not in n
         assert err < (2.0 ** -7 if linear_bias else 1e-5), (items, n, err)
+
+
+# ---- the fp16 copies of the weights (FlatStore.half_shadow) behind the C towers ------------------------------------------------------
+SHADOW_CFG = dict(vision_width=128, vision_layers=3, transformer_width=128, transformer_heads=2, transformer_layers=3)
+
+
+def _fp16(clip, txt, img):
+    """(image, text) embeddings of the C towers at precision "fp16", under no_grad; the attribute goes back to what it was"""
+    was, clip.precision = clip.precision, "fp16"
+    try:
+        with torch.no_grad():
+            return clip.encode_image(img).clone(), (clip.encode_text(txt).clone() if hasattr(clip, "text_projection") else None)
+    finally:
+        clip.precision = was
+
+
+@pytest.mark.parametrize("pack_text", [True, False])
+def test_the_fp16_copies_follow_the_fused_adamw_in_place_edits_and_load_state_dict(pack_text):
+    """CLIP score fusion, as tests/test_clipff_embed_fp16_gpu.py has it for CLIP_FF: fp16 embeddings, one bf16 training step with the
+    project's AdamW (whose kernels write the masters and the bf16 shadow and bump no Parameter._version), fp16 embeddings again:
+    those of a freshly built model that loaded the stepped state_dict, bit for bit, image and text tower -- and again after an
+    in-place edit of one parameter, and after load_state_dict into a model whose fp16 copies already existed.
+    Before the store owned the fp16 copies this failed at the first `same_as_fresh` (run once on that tree: `moved` held, the
+    comparison did not): the towers read the fp32 gains and biases of after the step and the fp16 matrices of before it."""
+    from oracle import clip_oracle as O
+    from uniir_amd.trainer import NativeAdamW
+    cfg = O.tiny_config(**SHADOW_CFG)
+
+    def build(seed):
+        m = _build(cfg, seed=seed)[0].eval()
+        m.clip_model.pack_text = pack_text
+        return m
+
+    model = build(5)
+    clip = model.clip_model
+    batch = O.synthetic_batch(cfg, 2, seed=23)          # 4 items
+    dbatch = {k: (v.cuda() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
+    txt, img = dbatch["txt_batched"], dbatch["image_batched"]
+    before = _fp16(clip, txt, img)          # the fp16 copies exist BEFORE the weights move
+    assert clip._flat.h16_buf is not None
+    opt = NativeAdamW(clip, lr=1e-2, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2, allreduce=False)
+    model.train()
+    opt.zero_grad()
+    model(dbatch)["loss"].backward()
+    proj_before = clip.visual.proj.detach().clone()
+    opt.step()
+    model.eval()
+    assert not torch.equal(clip.visual.proj, proj_before)
+
+    def same_as_fresh(got, seed):
+        fresh = build(seed)
+        fresh.clip_model.load_state_dict(clip.state_dict())
+        want = _fp16(fresh.clip_model, txt, img)
+        return torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+
+    got = _fp16(clip, txt, img)
+    moved = not torch.equal(got[0], before[0]) and not torch.equal(got[1], before[1])
+    assert moved and same_as_fresh(got, 9)
+    with torch.no_grad():          # the patch-embedding weight: its padded fp16 copy is no part of the store's flat shadow
+        clip.visual.conv1.weight.mul_(1.5)
+    got_img = _fp16(clip, txt, img)
+    assert not torch.equal(got_img[0], got[0]) and torch.equal(got_img[1], got[1]) and same_as_fresh(got_img, 10)
+    with torch.no_grad():
+        clip.get_parameter("transformer.resblocks.0.mlp.c_fc.weight").mul_(0.75)
+    got_txt = _fp16(clip, txt, img)
+    assert torch.equal(got_txt[0], got_img[0]) and not torch.equal(got_txt[1], got_img[1]) and same_as_fresh(got_txt, 11)
+    other = build(12)          # its fp16 copies exist, of other weights
+    first = _fp16(other.clip_model, txt, img)
+    assert not torch.equal(first[0], got_txt[0]) and not torch.equal(first[1], got_txt[1])
+    other.clip_model.load_state_dict(clip.state_dict())
+    again = _fp16(other.clip_model, txt, img)
+    assert torch.equal(again[0], got_txt[0]) and torch.equal(again[1], got_txt[1])
+
+
+@pytest.mark.parametrize("pack_text", [True, False])
+@pytest.mark.parametrize("order", ["towers-first", "clipff-first"])
+def test_score_fusion_and_clipff_in_fp16_share_the_fp16_copies_of_one_clip(order, pack_text):
+    """one CLIP run as the score-fusion C tower at fp16 and as the inner model of a CLIP_FF at fp16, in either order: each gives
+    bitwise what it gives on a model of its own, and the C tower's description points into the store's one fp16 buffer.
+    (embed_dim = 128 on top of SHADOW_CFG: CLIP_FF joins the text tokens, of the text width, with the projected image tokens.  The
+    CLIP inside a CLIP_FF has no text_projection, so the C tower run here is the image tower.)"""
+    from oracle import clip_oracle as O
+    from test_clipff_embed_fp16_gpu import SMALL_T5, _encode
+    from test_clipff_gpu import _model
+    cfg = O.tiny_config(embed_dim=128, **SHADOW_CFG)
+    batch = O.synthetic_batch(cfg, 2, seed=23)          # 4 items
+    txt, img = batch["txt_batched"].cuda(), batch["image_batched"].cuda()
+
+    def build():
+        m = _model(cfg, SMALL_T5, seed=5)[0].eval()
+        m.embed_fp16 = False
+        m.clip_model.pack_text = pack_text
+        return m
+
+    towers_alone = _fp16(build().clip_model, txt, img)[0]
+    clipff_alone = _encode(build(), "fp16", txt, img)
+    m = build()
+    if order == "towers-first":
+        towers, clipff = _fp16(m.clip_model, txt, img)[0], _encode(m, "fp16", txt, img)
+    else:
+        clipff, towers = _encode(m, "fp16", txt, img), _fp16(m.clip_model, txt, img)[0]
+    assert torch.equal(towers, towers_alone) and torch.equal(clipff, clipff_alone)
+    st = m.clip_model._flat
+    desc = m.clip_model.tower_desc("image", half=True)
+    lo = st.h16_buf.data_ptr()
+    assert desc.dtype16 == 1 and desc.proj16 == st.ptr(st.h16_buf, "visual.proj")
+    for i in range(cfg["vision_layers"]):
+        b = desc.blocks[i]
+        assert all(lo <= p < lo + 2 * st.total for p in (b.wqkv16, b.wo16, b.wfc16, b.wproj16))
+    assert desc.conv16 == st.padded16h("visual.conv1.weight").data_ptr()
+    assert st.half_bytes() == 2 * (st.total + cfg["vision_width"] * m.clip_model.kpad)          # the store is held in fp16 once

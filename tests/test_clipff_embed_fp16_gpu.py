@@ -181,6 +181,7 @@ def test_guards_and_the_bf16_path_is_untouched():
     txt, img = dbatch["txt_batched"], dbatch["image_batched"]
     emb0 = _encode(m, "bf16", txt, img)
     assert m.clip_model._flat.h16_buf is None and m._t5.h16_buf is None          # bf16 users allocate nothing
+    assert m.clip_model._flat.half_bytes() == 0 and m._t5.half_bytes() == 0          # ... no fp16 padded copy either
     m.precision = "fp16"
     m.train()
     with pytest.raises(RuntimeError, match="eval"), torch.no_grad():

@@ -3,7 +3,9 @@ arguments -- which parameter of the store, which temporary, which column view, w
 (towers without pooling and the T5 stack), the BLIP ViT, the MED BERT and BLIP_SF, and of the 16-bit forward-only passes in bf16 and
 fp16.  The table holds a digest of every entry (and the entries of one case in full): a mismatch prints the first entry that differs
 as it is now.  It was recorded (tests/golden/make_golden_embed_launches.py) before the fp32 launch layer and the precision rule were
-each made one.  CPU only: the recorder of tests/bert_launch_cases.py stands in for every op, so neither a GPU nor the library is
+each made one.  One later edit: the fp16 cases that read the padded patch weight (fp16-vit, fp16-clipff-vision, fp16-sf) lost the entry
+of the store's first-use fp16 cast -- the padded fp16 copy is the store's now and is made with that cast (FlatStore.half_shadow), which
+a model does before its forward and the cases do before their trace; tests/test_half_shadow_host.py pins those calls.  CPU only: the recorder of tests/bert_launch_cases.py stands in for every op, so neither a GPU nor the library is
 needed."""
 import json
 import os

@@ -104,3 +104,61 @@ def test_native_adamw_state_dict_keys():
     opt.load_state_dict(dict(sd, opt_step=7, exp_avg=m, exp_avg_sq=v))
     again = opt.state_dict()
     assert again["opt_step"] == 7 and again["exp_avg"] is m and again["exp_avg_sq"] is v and again["extra"] == []
+
+
+# ---- NativeAdamW and the store's one "a kernel wrote the masters" event --------------------------------------------------------------
+def _recorded_step(monkeypatch, guarded):
+    """a BLIP-shaped pair of stores (the online one is stepped, the momentum one is not) plus an extra store without padded tensors
+    (CLIP_FF's T5 stack), on the CPU with ops.call recorded -> (online, momentum, extra, the calls of one step as (name, store tag))"""
+    from types import SimpleNamespace
+    from uniir_amd import ops
+    from uniir_amd.blip_model import CONV, BLIPScoreFusion
+    from uniir_amd.flat_store import FlatStore, patch_kpad
+    from uniir_amd.trainer import NativeAdamW
+    med = dict(hidden_size=64, intermediate_size=128, max_position_embeddings=16, num_attention_heads=1, num_hidden_layers=2,
+               vocab_size=100)
+    vit = dict(patch_size=16, embed_dim=64, depth=2, num_heads=1, drop_path_rate=0.0, img_size=32)
+    m = BLIPScoreFusion(med_config=med, vit_config=vit, embed_dim=32, queue_size=8)
+    online = FlatStore.adopt(m._online_params(), "cpu", frozen=m._frozen, unversioned=("temp",))
+    mom = FlatStore.adopt(m._momentum_params(), "cpu", with_grad=False)
+    for st in (online, mom):
+        st.add_padded("visual_encoder." + CONV, 64, 768, patch_kpad(16))
+    t5_params = [torch.nn.Parameter(torch.randn(8, 8)), torch.nn.Parameter(torch.randn(8))]
+    extra = FlatStore.adopt([("a", t5_params[0]), ("b", t5_params[1])], "cpu")
+    tag = {online.p32.data_ptr(): "online", mom.p32.data_ptr(): "momentum", extra.p32.data_ptr(): "extra"}
+    calls = []
+
+    def call(name, *a):
+        src = a[0]
+        base = src.untyped_storage().data_ptr()
+        calls.append((name, tag[base]))
+
+    monkeypatch.setattr(ops, "call", call)
+    model = SimpleNamespace(_ensure_flat=lambda: online, optimizer_groups=m.optimizer_groups, adamw_group=m.adamw_group)
+    group = SimpleNamespace(params=t5_params, store=lambda: extra, weight_decay=0.2, lr=1e-3)
+    opt = NativeAdamW(model, lr=1e-3, allreduce=False, extra=[group], max_grad_norm=1.0 if guarded else None, skip_nonfinite=False)
+    assert (opt.guard is not None) == guarded
+    if guarded:          # the guard's own launches need the device: stood in for, in their place in the sequence
+        opt.guard = SimpleNamespace(ctl=None, resolve=lambda: False, publish=lambda: calls.append(("publish", None)),
+                                    measure=lambda ranges, scale: calls.append(("measure", None)))
+    for st in (online, mom, extra):
+        st.half_stale = False          # as if fp16 copies existed and were fresh
+    opt.step()
+    return online, mom, extra, calls
+
+
+@pytest.mark.parametrize("guarded", [False, True])
+def test_native_adamw_tells_every_store_it_stepped_exactly_once(monkeypatch, guarded):
+    """per store: the AdamW launches, then FlatStore.kernel_wrote() -- one pad launch for the online store's one padded tensor, none
+    for the momentum store (the optimizer does not step it) and none for a store without padded tensors; fp16 goes stale where stepped"""
+    online, mom, extra, calls = _recorded_step(monkeypatch, guarded)
+    step = "uniir_adamw_step_guarded" if guarded else "uniir_adamw_step"
+    body = [c for c in calls if c[0] not in ("measure", "publish")]
+    launches = [c for c in body if c[1] == "online" and c[0] == step]
+    assert len(launches) == 2          # trainable | frozen cross-attention (not stepped) | temp: two ranges
+    assert body == launches + [("uniir_cast_pad_rows", "online"), (step, "extra")]
+    assert not any(c[1] == "momentum" for c in calls)
+    if guarded:
+        assert calls[0] == ("measure", None) and calls[-1] == ("publish", None) and len(calls) == len(body) + 2
+    assert online.half_stale is True and extra.half_stale is True and mom.half_stale is False
+    assert online.half_bytes() == 0 and extra.half_bytes() == 0          # and nothing fp16 was allocated by the step

@@ -26,7 +26,7 @@ def _casts(st, name):
 def test_nothing_is_allocated_until_the_fp16_shadow_is_asked_for(store):
     assert store.h16_buf is None
     store.refresh_shadow()
-    store.mark_half_stale()
+    store.kernel_wrote()
     store.w16("a.weight")
     store.p("q.weight", (24, 8))
     assert store.h16_buf is None and not _casts(store, "uniir_cast_f32_to_f16")
@@ -58,7 +58,7 @@ def test_the_shadow_is_cast_on_first_use_and_again_only_once_stale(store):
     assert store.half_stale is True and len(_casts(store, f16)) == 1          # ... and casts nothing by itself
     store.w16h("tail")
     assert len(_casts(store, f16)) == 2 and store.half_stale is False and store.h16_buf is buf          # rebuilt in place
-    store.mark_half_stale()          # a writer that goes past the class (fused AdamW, EMA)
+    store.kernel_wrote()          # a writer that goes past the class (fused AdamW, EMA)
     assert store.half_stale is True
     store.half_shadow()
     store.half_shadow()
@@ -148,3 +148,122 @@ def test_the_fp16_glue_entry_points_keep_the_checks_of_their_bf16_twins(fn, twin
         assert got < 0 or call[count] == 0, (fn, ch, got)          # 0 only for an empty call: nothing here may reach a launch
         codes.add(got)
     assert codes == {0, -1, -2}          # UNIIR_OK for an empty call, UNIIR_EINVAL, UNIIR_ESHAPE: every branch was reached
+
+
+# ---- the padded copies and the two "the masters moved" events: the exact ops.call sequence of every event ----------------------------
+PAD = ("conv.weight", 8, 27, 64)          # an 8 x 27 tensor, rows padded to 64
+
+
+@pytest.fixture
+def padded_store(monkeypatch):
+    """a CPU store with gradients and one padded tensor registered, its device calls recorded"""
+    from uniir_amd import flat_store
+    calls = []
+    monkeypatch.setattr(flat_store.ops, "call", lambda name, *a: calls.append((name,) + a))
+    st = flat_store.FlatStore([("conv.weight", (8, 3, 3, 3))] + SHAPES, "cpu")
+    st.add_padded(*PAD)
+    st.calls = calls
+    return st
+
+
+def _taken(st):
+    """the calls recorded since the last look, as (name, what was written, the scalars); the source is checked here"""
+    out = []
+    for name, src, dst, *rest in st.calls:
+        whole = name in ("uniir_cast_f32_to_bf16", "uniir_cast_f32_to_f16")
+        want = st.p32 if whole else st.p("conv.weight")
+        assert src.data_ptr() == want.data_ptr() and src.dtype == torch.float32 and (src is st.p32) == whole
+        out.append((name, dst, tuple(rest)))
+    del st.calls[:]
+    return out
+
+
+def test_every_event_makes_exactly_its_calls(padded_store):
+    st = padded_store
+    assert st.calls == [] and st.half_bytes() == 0          # construction and registration launch nothing, allocate no fp16
+    b16 = st.padded16("conv.weight")
+    assert b16.dtype == torch.bfloat16 and tuple(b16.shape) == (8, 64)
+    g = st.padded_grad("conv.weight")
+    assert g.dtype == torch.float32 and tuple(g.shape) == (8, 64) and g.data_ptr() != st.g32.data_ptr()
+    pad16 = ("uniir_cast_pad_rows", b16, (8, 27, 64))
+    st.refresh_shadow()
+    assert _taken(st) == [("uniir_cast_f32_to_bf16", st.w16_buf, (st.total,)), pad16]
+    st.kernel_wrote()          # the kernel cast the flat shadow itself: only the padded copy is left to do
+    assert _taken(st) == [pad16]
+    assert st.half_bytes() == 0 and st.h16_buf is None          # neither event touches fp16
+    h = st.half_shadow()          # the first one: allocates, one cast and one fp16 pad
+    h16 = st.padded16h("conv.weight")
+    assert h is st.h16_buf and h16.dtype == torch.float16 and tuple(h16.shape) == (8, 64) and st.half_bytes() == 2 * (st.total + 8 * 64)
+    padh = ("uniir_cast_pad_rows_f16", h16, (8, 27, 64))
+    assert _taken(st) == [("uniir_cast_f32_to_f16", h, (st.total,)), padh]
+    st.half_shadow()          # a second one: nothing
+    st.w16h("a.weight")
+    assert _taken(st) == []
+    for event, calls in ((st.refresh_shadow, [("uniir_cast_f32_to_bf16", st.w16_buf, (st.total,)), pad16]), (st.kernel_wrote, [pad16])):
+        event()
+        assert _taken(st) == calls and st.half_stale is True          # fp16 is marked, not cast
+        assert st.half_shadow() is h and st.padded16h("conv.weight") is h16          # refilled in place: raw pointers stay valid
+        assert _taken(st) == [("uniir_cast_f32_to_f16", h, (st.total,)), padh]
+        st.half_shadow()
+        assert _taken(st) == []
+    assert st.padded16("conv.weight") is b16 and st.padded_grad("conv.weight") is g
+
+
+def test_a_store_without_padded_tensors_makes_no_pad_call_and_one_without_gradients_keeps_no_scratch(store, monkeypatch):
+    from uniir_amd import flat_store
+    store.refresh_shadow()
+    store.kernel_wrote()
+    store.half_shadow()
+    store.kernel_wrote()
+    store.half_shadow()
+    assert [c[0] for c in store.calls] == ["uniir_cast_f32_to_bf16", "uniir_cast_f32_to_f16", "uniir_cast_f32_to_f16"]
+    assert store.half_bytes() == 2 * store.total
+    mom = flat_store.FlatStore([("conv.weight", (8, 3, 3, 3))], "cpu", with_grad=False)          # the BLIP momentum store's kind
+    mom.add_padded(*PAD)
+    assert mom.padded_grad("conv.weight") is None and mom.padded16("conv.weight").shape == (8, 64)
+    with pytest.raises(ValueError):
+        mom.add_padded("conv.weight", 8, 28, 64)          # not the tensor's element count
+    with pytest.raises(ValueError):
+        mom.add_padded("conv.weight", 8, 27, 16)          # a leading dimension below the row length
+    assert flat_store.patch_kpad(16) == 768 and flat_store.patch_kpad(14) == 640 and flat_store.patch_kpad(3) == 64
+
+
+def test_sync_refreshes_exactly_when_a_watched_parameter_was_written_on_the_torch_side(monkeypatch):
+    from uniir_amd import flat_store
+    calls = []
+    monkeypatch.setattr(flat_store.ops, "call", lambda name, *a: calls.append(name))
+    mod = torch.nn.Module()
+    mod.conv = torch.nn.Parameter(torch.randn(8, 3, 3, 3))
+    mod.w = torch.nn.Parameter(torch.randn(6, 10))
+    mod.temp = torch.nn.Parameter(torch.tensor(0.07))
+    st = flat_store.FlatStore.adopt(list(mod.named_parameters()), "cpu", unversioned=("temp",))
+    st.add_padded("conv", 8, 27, 64)
+    refresh = ["uniir_cast_f32_to_bf16", "uniir_cast_pad_rows"]
+
+    def synced():
+        del calls[:]
+        st.sync()
+        return list(calls)
+
+    assert synced() == refresh          # nothing was cast yet
+    assert synced() == [] and synced() == []          # no version moved
+    st.kernel_wrote()          # a kernel's writes move no version
+    assert synced() == []
+    with torch.no_grad():
+        mod.w[2, :3] += 1.0
+    assert synced() == refresh and synced() == []          # an in-place edit of any adopted parameter: one refresh
+    with torch.no_grad():
+        mod.conv.mul_(2.0)
+        mod.w.mul_(2.0)
+    assert synced() == refresh and synced() == []          # however many moved
+    with torch.no_grad():
+        mod.temp.clamp_(0.001, 0.5)
+    assert synced() == []          # an unversioned one: none
+    mod.load_state_dict({k: v.detach().clone() + 1 for k, v in mod.state_dict().items()})
+    assert st.holds(mod.named_parameters()) and synced() == refresh and synced() == []          # load_state_dict: one
+    assert float(st.p("temp")) == float(mod.temp.detach()) and st.half_bytes() == 0
+    st.half_shadow()
+    with torch.no_grad():
+        mod.w[0, 0] = 3.0
+    st.sync()
+    assert st.half_stale is True          # ... and the fp16 copies follow at their next use

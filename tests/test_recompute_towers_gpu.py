@@ -41,13 +41,13 @@ def _vit_run(model, x, dtok, k, seed=13):
     model.zero_grad()
     torch.manual_seed(seed)                                     # the DropPath draw (torch's CPU generator): the same rowscale
     drop = ops.DropSeeds() if model.training else None
-    tok, T, stash = bm.vit_forward(st, model._conv16, "visual_encoder.", model.vit_cfg, model.image_size, x, True, drop=drop,
+    tok, T, stash = bm.vit_forward(st, "visual_encoder.", model.vit_cfg, model.image_size, x, True, drop=drop,
                                    recompute_from=k)
     kept = [len(e) for e in stash["saved"]]
     inputs_only = all(e[0].dtype == torch.float32 and e[0].shape == (x.shape[0] * T, model.vit_cfg["embed_dim"])
                       for e in stash["saved"])
     rowscale = stash["rowscale"]
-    bm.vit_backward(st, model._dconv, "visual_encoder.", model.vit_cfg, dtok, stash)
+    bm.vit_backward(st, "visual_encoder.", model.vit_cfg, dtok, stash)
     torch.cuda.synchronize()
     return tok.clone(), st.g32.clone(), kept, inputs_only, rowscale
 
@@ -105,9 +105,9 @@ def test_vit_peak_memory_drops_by_the_rebuilt_sets():
     dtok = torch.randn(R, W, generator=g).cuda()
 
     def step(k):
-        tok, _, stash = bm.vit_forward(st, model._conv16, "visual_encoder.", model.vit_cfg, model.image_size, x, True,
+        tok, _, stash = bm.vit_forward(st, "visual_encoder.", model.vit_cfg, model.image_size, x, True,
                                        recompute_from=k)
-        bm.vit_backward(st, model._dconv, "visual_encoder.", model.vit_cfg, dtok, stash)
+        bm.vit_backward(st, "visual_encoder.", model.vit_cfg, dtok, stash)
         del tok, stash
         torch.cuda.synchronize()
 

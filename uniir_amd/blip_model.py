@@ -26,7 +26,7 @@ import torch
 from torch import nn
 
 from . import _lib, comm, ops
-from .flat_store import FlatStore
+from .flat_store import FlatStore, patch_kpad
 from .fp32_forward import attention_f32, layernorm_f32, linear_f32, patch_tokens_f32, tower_fwd_f32
 from .precision import check_mode, embed_mode, env_flag
 from .resblocks import tower_bwd, tower_fwd
@@ -39,6 +39,7 @@ MED_DEFAULT = dict(hidden_size=768, intermediate_size=3072, layer_norm_eps=1e-12
                    num_attention_heads=12, num_hidden_layers=12, vocab_size=30524, hidden_dropout_prob=0.1,
                    attention_probs_dropout_prob=0.1)   # backbone/configs/med_config.json
 VIT_EPS = 1e-6
+CONV = "patch_embed.proj.weight"          # below a ViT's prefix: the tensor its store keeps [D, kpad] copies of (FlatStore.add_padded)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -116,10 +117,10 @@ def vit_recompute_from(depth, vit_grad_ckpt, vit_ckpt_layer):
     return depth - min(max(int(vit_ckpt_layer), 0), depth)
 
 
-def vit_forward(st, conv16, prefix, cfg, img_size, images, save, drop=None, recompute_from=None, dtype16=torch.bfloat16):
+def vit_forward(st, prefix, cfg, img_size, images, save, drop=None, recompute_from=None, dtype16=torch.bfloat16):
     """src/models/uniir_blip/backbone/vit.py:196-221 -> bf16 tokens [M*T, D] (after the final norm) + stash.
-    dtype16 = torch.float16 (forward only: save False, conv16 the fp16 copy of the patch-embedding weight): patches, activations and
-    the returned tokens are fp16, the weights come from st's fp16 shadow (FlatStore.w16h); the residual stream, the LayerNorm
+    dtype16 = torch.float16 (forward only: save False): patches, activations and the returned tokens are fp16, the weights come from
+    st's fp16 shadow (FlatStore.w16h, and padded16h for the patch-embedding weight); the residual stream, the LayerNorm
     statistics and every accumulation stay fp32.  Three more mantissa bits in every operand, the same MFMA rate.
     drop (ops.DropSeeds, train mode): DropPath with rates linspace(0, drop_path_rate, depth) (vit.py:167), one Bernoulli
     draw per item and residual branch from torch's CPU generator.
@@ -130,10 +131,9 @@ def vit_forward(st, conv16, prefix, cfg, img_size, images, save, drop=None, reco
     G = (img_size // P) ** 2
     T = G + 1
     heads = cfg["num_heads"]
-    kpad = conv16.shape[1]
     half = dtype16 == torch.float16
-    if conv16.dtype != dtype16:
-        raise ValueError(f"vit_forward: a {conv16.dtype} patch-embedding weight with dtype16 = {dtype16}")
+    conv16 = (st.padded16h if half else st.padded16)(prefix + CONV)
+    kpad = conv16.shape[1]
     patches = torch.empty(M * G, kpad, device=dev, dtype=dtype16)
     ops.call("uniir_patchify_f16" if half else "uniir_patchify", images.float().contiguous(), patches, M, img_size, P, kpad)
     po = ops.linear_fwd(patches, conv16, st.p(prefix + "patch_embed.proj.bias"))
@@ -153,7 +153,7 @@ def vit_forward(st, conv16, prefix, cfg, img_size, images, save, drop=None, reco
     return tok, T, stash
 
 
-def vit_backward(st, dconv, prefix, cfg, dtok, stash):
+def vit_backward(st, prefix, cfg, dtok, stash):
     """dtok fp32 [M*T, D]: gradient w.r.t. the normed tokens; parameter gradients accumulate into st.g32"""
     D, P, depth, heads = cfg["embed_dim"], cfg["patch_size"], cfg["depth"], cfg["num_heads"]
     M, T = stash["M"], stash["T"]
@@ -168,9 +168,9 @@ def vit_backward(st, dconv, prefix, cfg, dtok, stash):
     ops.call("uniir_vit_assemble_bwd", dx, dpo, st.grad_view(prefix + "cls_token"), st.grad_view(prefix + "pos_embed"),
              M, T, D)
     ops.call("uniir_colsum_bf16", dpo, D, st.grad_view(prefix + "patch_embed.proj.bias"), M * G, D)
-    dconv.zero_()
+    dconv = st.padded_grad(prefix + CONV).zero_()
     ops.linear_wgrad(dpo, stash["patches"], dconv)
-    ops.call("uniir_unpad_add", dconv, st.grad_view(prefix + "patch_embed.proj.weight"), D, 3 * P * P, dconv.shape[1])
+    ops.call("uniir_unpad_add", dconv, st.grad_view(prefix + CONV), D, 3 * P * P, dconv.shape[1])
 
 
 class TextPack:
@@ -648,7 +648,7 @@ class _EncodeFn(torch.autograd.Function):
         save = bool(ctx.needs_input_grad[4])
         st = model._online
         drop = model._drop_seeds()
-        tok, Ti, vst = vit_forward(st, model._conv16, "visual_encoder.", model.vit_cfg, model.image_size, images, save,
+        tok, Ti, vst = vit_forward(st, "visual_encoder.", model.vit_cfg, model.image_size, images, save,
                                    drop=drop, recompute_from=model._vit_boundary(save))
         pooled, bst = bert_forward(st, "text_encoder.", model.med_cfg, ids, key_len, tok, Ti, save, drop=drop, pack=pack,
                                    pool_last=model.pool_last_layer, log=model._path_log())
@@ -661,7 +661,7 @@ class _EncodeFn(torch.autograd.Function):
         bst, vst = ctx.bst, ctx.vst
         ctx.bst = ctx.vst = None
         dimg = bert_backward(st, "text_encoder.", model.med_cfg, dpooled, bst)
-        vit_backward(st, model._dconv, "visual_encoder.", model.vit_cfg, dimg, vst)
+        vit_backward(st, "visual_encoder.", model.vit_cfg, dimg, vst)
         return None, None, None, None, None, None
 
 
@@ -903,15 +903,12 @@ class BLIPFeatureFusion(nn.Module):
             raise RuntimeError("uniir_amd BLIPFeatureFusion runs on an MI355X only (no CPU path); move the model to cuda")
         if self._online is not None and self._online.holds(self._online_params()):
             return self._online
-        self._online = FlatStore.adopt(self._online_params(), dev, frozen=self._frozen)
+        # temp has no shadow and is clamp_()ed every step: its version is not watched
+        self._online = FlatStore.adopt(self._online_params(), dev, frozen=self._frozen, unversioned=("temp",))
         self._mom = FlatStore.adopt(self._momentum_params(), dev, with_grad=False)
         D, P = self.vit_cfg["embed_dim"], self.vit_cfg["patch_size"]
-        kpad = (3 * P * P + 63) // 64 * 64
-        self._conv16 = torch.zeros(D, kpad, device=dev, dtype=torch.bfloat16)
-        self._conv16_m = torch.zeros(D, kpad, device=dev, dtype=torch.bfloat16)
-        self._dconv = torch.zeros(D, kpad, device=dev, dtype=torch.float32)
-        self._conv16h = None              # fp16 twin of _conv16 (_vit_tokens(precision="fp16")): built on first use
-        self._version = -1
+        for st in (self._online, self._mom):
+            st.add_padded("visual_encoder." + CONV, D, 3 * P * P, patch_kpad(P))
         self.refresh_shadow()
         return self._online
 
@@ -925,44 +922,17 @@ class BLIPFeatureFusion(nn.Module):
         the trainable tensors and temp) are not stepped"""
         return None if name in self._frozen else 1
 
-    def _refresh_conv(self, momentum_too=True):
-        D, P = self.vit_cfg["embed_dim"], self.vit_cfg["patch_size"]
-        pairs = [(self._online, self._conv16)] + ([(self._mom, self._conv16_m)] if momentum_too else [])
-        for st, dst in pairs:
-            ops.call("uniir_cast_pad_rows", st.p("visual_encoder.patch_embed.proj.weight"), dst, D, 3 * P * P, dst.shape[1])
-            # every event that moves the master weights ends here -- refresh_shadow(), the fused AdamW (trainer.NativeAdamW.step) and
-            # the EMA of _momentum_update, which write p32 and the bf16 shadow themselves -- so the fp16 copies go stale here
-            st.mark_half_stale()
-
-    def _sync_half(self):
-        """_sync() plus the fp16 copies of the online encoder's weights (its store's fp16 shadow and the fp16 twin of _conv16): built
-        on first use, rebuilt whenever the bf16 ones were refreshed or the parameters moved since.  -> the online store"""
-        self._sync()
-        st = self._online
-        if self._conv16h is None or st.h16_buf is None or st.half_stale:
-            D, P = self.vit_cfg["embed_dim"], self.vit_cfg["patch_size"]
-            if self._conv16h is None:
-                self._conv16h = torch.zeros_like(self._conv16, dtype=torch.float16)
-            ops.call("uniir_cast_pad_rows_f16", st.p("visual_encoder.patch_embed.proj.weight"), self._conv16h, D, 3 * P * P,
-                     self._conv16h.shape[1])
-        st.half_shadow()
-        return st
-
     def refresh_shadow(self):
         self._online.refresh_shadow()
         self._mom.refresh_shadow()
-        self._refresh_conv()
-        self._version = self._param_version()
 
-    def _param_version(self):
-        # torch-side writes (load_state_dict, manual edits) bump these; the kernels' own updates (AdamW, EMA) refresh
-        # the bf16 shadows themselves.  temp has no shadow, and is clamp_()ed every step: left out.
-        return sum(p._version for n, p in self.named_parameters() if n != "temp")
-
-    def _sync(self):
+    def _sync(self, half=False):
+        """both stores, their bf16 copies following torch-side writes (FlatStore.sync); half: the online store's fp16 copies too"""
         self._ensure_flat()
-        if self._version != self._param_version():
-            self.refresh_shadow()
+        self._online.sync()
+        self._mom.sync()
+        if half:
+            self._online.half_shadow()
 
     def zero_grad(self, set_to_none=False):
         if self._online is not None:
@@ -1023,14 +993,10 @@ class BLIPFeatureFusion(nn.Module):
         (mbeir_embedder.py:52-56: autocast(fp16)), 577 tokens at 384 pixels included.  fp16 is an eval-mode path: in training mode
         it raises (DropPath belongs to the bf16 training forward)."""
         check_mode(precision, ("bf16", "fp16"), self.training)
-        if precision == "fp16":
-            st = self._sync_half()
-            conv, dt, drop = self._conv16h, torch.float16, None
-        else:
-            self._sync()
-            st, conv, dt, drop = self._online, self._conv16, torch.bfloat16, self._drop_seeds()
-        tok, T, _ = vit_forward(st, conv, "visual_encoder.", self.vit_cfg, self.image_size, image_batched, False, drop=drop,
-                                dtype16=dt)
+        half = precision == "fp16"
+        self._sync(half)
+        tok, T, _ = vit_forward(self._online, "visual_encoder.", self.vit_cfg, self.image_size, image_batched, False,
+                                drop=None if half else self._drop_seeds(), dtype16=torch.float16 if half else torch.bfloat16)
         return tok.view(image_batched.shape[0], T, -1)
 
     def _embed_mode(self, use_momentum):
@@ -1041,10 +1007,7 @@ class BLIPFeatureFusion(nn.Module):
         -> mode (_embed_mode), ids, key_len, pack; last_text_rows = (BERT rows run, rows of the padded batch).  "fp32" runs the dense
         rows: no pack"""
         mode = self._embed_mode(use_momentum)
-        if mode == "fp16":
-            self._sync_half()          # _sync() plus the fp16 copies
-        else:
-            self._sync()
+        self._sync(half=mode == "fp16")
         ids, key_len = self._text_inputs(txt_dict_batched)
         pack = self._text_pack(txt_dict_batched, key_len, ids.shape[1]) if mode != "fp32" else None
         self.last_text_rows = (pack.R if pack is not None else ids.numel(), ids.numel())
@@ -1060,15 +1023,15 @@ class BLIPFeatureFusion(nn.Module):
         if mode == "fp16":
             with torch.no_grad():
                 st = self._online
-                tok, Ti, _ = vit_forward(st, self._conv16h, "visual_encoder.", self.vit_cfg, self.image_size, image_batched, False,
+                tok, Ti, _ = vit_forward(st, "visual_encoder.", self.vit_cfg, self.image_size, image_batched, False,
                                          dtype16=torch.float16)
                 return bert_forward(st, "text_encoder.", self.med_cfg, ids, key_len, tok, Ti, False, pack=pack,
                                     pool_last=self.pool_last_layer, log=self._path_log(), dtype16=torch.float16)[0]
         if use_momentum:
             with torch.no_grad():
                 drop = self._drop_seeds()
-                tok, Ti, _ = vit_forward(self._mom, self._conv16_m, "visual_encoder.", self.vit_cfg, self.image_size,
-                                         image_batched, False, drop=drop)
+                tok, Ti, _ = vit_forward(self._mom, "visual_encoder.", self.vit_cfg, self.image_size, image_batched, False,
+                                         drop=drop)
                 return bert_forward(self._mom, "text_encoder.", self.med_cfg, ids, key_len, tok, Ti, False, drop=drop,
                                     pack=pack, pool_last=self.pool_last_layer, log=self._path_log())[0]
         anchor = torch.zeros(1, device=ids.device, requires_grad=torch.is_grad_enabled())
@@ -1080,7 +1043,7 @@ class BLIPFeatureFusion(nn.Module):
         self._sync()
         ops.call("uniir_ema_update", self._mom.p32, self._online.p32, self._mom.w16_buf, self._mom.total,
                  float(self.momentum))
-        self._refresh_conv()
+        self._mom.kernel_wrote()
 
     @torch.no_grad()
     def _dequeue_and_enqueue(self, query_feats, cand_feats, idxs):
@@ -1150,7 +1113,7 @@ class _EncodeSFFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, ids, key_len, images, tmask, imask, anchor, pack=None):
         save = bool(ctx.needs_input_grad[6])
-        emb, stash = model._encode_sf(model._online, model._conv16, ids, key_len, images, tmask, imask, save, pack)
+        emb, stash = model._encode_sf(model._online, ids, key_len, images, tmask, imask, save, pack)
         ctx.model, ctx.stash = model, stash
         return emb
 
@@ -1179,7 +1142,7 @@ class _EncodeSFFn(torch.autograd.Function):
         T, D = S["T"], difeat.shape[1]
         dtok = torch.zeros(M * T, D, device=dev, dtype=torch.float32)
         ops.call("uniir_scatter_rows", difeat, None, dtok, M, T, D)
-        vit_backward(st, model._dconv, "visual_encoder.", model.vit_cfg, dtok, S["vst"])
+        vit_backward(st, "visual_encoder.", model.vit_cfg, dtok, S["vst"])
         return None, None, None, None, None, None, None, None
 
 
@@ -1189,16 +1152,16 @@ class BLIPScoreFusion(BLIPFeatureFusion):
     parameters exist but are frozen (:66-69) and unused (mode "text")."""
     SCORE_FUSION = True
 
-    def _encode_sf(self, st, conv16, ids, key_len, images, tmask, imask, save, pack=None, dtype16=torch.bfloat16):
-        """dtype16 = torch.float16 (the fp16 embedding forward: save False, eval mode, conv16 the fp16 patch weight): ViT, BERT and
-        the two projections on fp16 operands from st's fp16 shadow"""
+    def _encode_sf(self, st, ids, key_len, images, tmask, imask, save, pack=None, dtype16=torch.bfloat16):
+        """dtype16 = torch.float16 (the fp16 embedding forward: save False, eval mode): ViT, BERT and the two projections on fp16
+        operands from st's fp16 shadow"""
         dev = ids.device
         M = ids.shape[0]
         E = self.embed_dim
         half = dtype16 == torch.float16
         w16 = st.w16h if half else st.w16
         drop = None if half else self._drop_seeds()
-        tok, T, vst = vit_forward(st, conv16, "visual_encoder.", self.vit_cfg, self.image_size, images, save, drop=drop,
+        tok, T, vst = vit_forward(st, "visual_encoder.", self.vit_cfg, self.image_size, images, save, drop=drop,
                                   recompute_from=self._vit_boundary(save), dtype16=dtype16)
         ifeat16 = tok.view(M, T, -1)[:, 0].contiguous()                     # class-token rows (a copy)
         tfeat, bst = bert_forward(st, "text_encoder.", self.med_cfg, ids, key_len, None, 0, save, cross=False, pool=False,
@@ -1236,10 +1199,10 @@ class BLIPScoreFusion(BLIPFeatureFusion):
             return self._encode_sf_f32(self._online, ids, key_len, image_batched, tmask, imask)
         if mode == "fp16":
             with torch.no_grad():
-                return self._encode_sf(self._online, self._conv16h, ids, key_len, image_batched, tmask, imask, False, pack, torch.float16)[0]
+                return self._encode_sf(self._online, ids, key_len, image_batched, tmask, imask, False, pack, torch.float16)[0]
         if use_momentum:
             with torch.no_grad():
-                return self._encode_sf(self._mom, self._conv16_m, ids, key_len, image_batched, tmask, imask, False, pack)[0]
+                return self._encode_sf(self._mom, ids, key_len, image_batched, tmask, imask, False, pack)[0]
         anchor = torch.zeros(1, device=dev, requires_grad=torch.is_grad_enabled())
         return _EncodeSFFn.apply(self, ids, key_len, image_batched, tmask, imask, anchor, pack)
 

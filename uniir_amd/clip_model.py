@@ -17,11 +17,12 @@ import torch
 from torch import nn
 
 from . import _lib, ops
-from .flat_store import FlatStore
+from .flat_store import FlatStore, patch_kpad
 from .fp32_forward import layernorm_f32, linear_f32, patch_tokens_f32, tower_fwd_f32
 from .precision import env_flag
 from .resblocks import clip_block_names
 
+CONV = "visual.conv1.weight"          # the patch-embedding weight: the store keeps its [width, kpad] copies (FlatStore.add_padded)
 _SIDE_STREAMS = {}          # device index -> the torch stream that carries the text leg of two-stream towers (CLIP.side_leg)
 
 def _tensor_version(t):
@@ -147,7 +148,7 @@ class CLIP(nn.Module):
         self.text_projection = nn.Parameter(torch.randn(tw, E, generator=g) * tw ** -0.5)
         self.logit_scale = nn.Parameter(torch.ones([]) * math.log(1 / 0.07))
         self._flat = None          # the FlatStore of the parameters (built lazily on the device, _ensure_flat)
-        self.kpad = (3 * P * P + 63) // 64 * 64
+        self.kpad = patch_kpad(P)
         # precision / embed_fp32: precision.py.  Here "fp16" and "fp32" are the C towers' forward-only paths (_TowerFn); the weights of
         # "fp16" are read from an fp16 shadow that is refreshed with the bf16 one.
         self.precision = "bf16"
@@ -225,60 +226,23 @@ class CLIP(nn.Module):
             raise RuntimeError("uniir_amd CLIP runs on an MI355X only (no CPU path); move the model to cuda")
         if self._flat is not None and self._flat.holds(self.named_parameters()):
             return self._flat
-        self._flat = FlatStore.adopt(self._flat_order(), dev)
-        self._h16 = self._h16_version = None          # the fp16 shadow (precision = "fp16"): built on first use
-        self._descs = {}                               # tower_desc() cache: raw pointers into this store
-        self._conv16 = torch.zeros(self.cfg["vision_width"], self.kpad, device=dev, dtype=torch.bfloat16)
-        self._dconv = torch.zeros(self.cfg["vision_width"], self.kpad, device=dev, dtype=torch.float32)
-        self.refresh_shadow()
-        return self._flat
+        self._flat = st = FlatStore.adopt(self._flat_order(), dev)
+        st.add_padded(CONV, self.cfg["vision_width"], 3 * self.cfg["vision_patch_size"] ** 2, self.kpad)
+        # tower_desc() cache: raw pointers into this store.  They stay valid for the store's life: its buffers, the fp16 shadow and the
+        # padded copies included, are allocated once and refilled in place (FlatStore.half_shadow)
+        self._descs = {}
+        st.refresh_shadow()
+        return st
 
     def refresh_shadow(self):
-        """bf16 copies of the master weights (called after every optimizer step; the fused AdamW does it itself)."""
+        """the 16-bit copies of the master weights follow a torch-side write (FlatStore.refresh_shadow; _sync_shadow() finds out by
+        itself, and the fused AdamW tells the store)"""
         self._flat.refresh_shadow()
-        self._refresh_conv()
-        self._shadow_version = self._param_version()
-        self._h16_version = None            # the fp16 shadow (precision = "fp16") is rebuilt on demand
-
-    def _sync_half_shadow(self):
-        """fp16 copies of the master weights for the fp16 forward: built on first use, rebuilt when the parameters moved"""
-        st = self._sync_shadow()
-        ver = self._param_version()
-        if self._h16 is None:
-            self._h16 = torch.empty(st.total, device=st.dev, dtype=torch.float16)
-            self._conv16h = torch.zeros(self.cfg["vision_width"], self.kpad, device=st.dev, dtype=torch.float16)
-        if self._h16_version != ver:
-            ops.call("uniir_cast_f32_to_f16", st.p32, self._h16, st.total)
-            vw, P = self.cfg["vision_width"], self.cfg["vision_patch_size"]
-            ops.call("uniir_cast_pad_rows_f16", self.visual.conv1.weight.data, self._conv16h, vw, 3 * P * P, self.kpad)
-            self._h16_version = ver
-        return st
-
-    def _sync_half_flat(self):
-        """_sync_shadow() plus the fp16 copies the per-op towers of CLIP_FF read under fp16 (clipff_model, dtype16 = torch.float16):
-        the store's own fp16 shadow (FlatStore.w16h) and the fp16 twin of _conv16.  Built on first use, rebuilt whenever the bf16
-        shadow was refreshed or a kernel moved the master weights (FlatStore.half_stale).  -> the store"""
-        st = self._sync_shadow()
-        conv = getattr(self, "_conv16h", None)
-        if conv is None or conv.device != st.dev or st.h16_buf is None or st.half_stale:
-            if conv is None or conv.device != st.dev:
-                self._conv16h = torch.zeros(self.cfg["vision_width"], self.kpad, device=st.dev, dtype=torch.float16)
-            vw, P = self.cfg["vision_width"], self.cfg["vision_patch_size"]
-            ops.call("uniir_cast_pad_rows_f16", self.visual.conv1.weight.data, self._conv16h, vw, 3 * P * P, self.kpad)
-        st.half_shadow()
-        return st
-
-    def _refresh_conv(self):
-        vw, P = self.cfg["vision_width"], self.cfg["vision_patch_size"]
-        ops.call("uniir_cast_pad_rows", self.visual.conv1.weight.data, self._conv16, vw, 3 * P * P, self.kpad)
-
-    def _param_version(self):
-        return sum(p._version for _, p in self.named_parameters())
 
     def _sync_shadow(self):
+        """the store, its bf16 copies up to date; the fp16 ones on top: _sync_shadow().half_shadow()"""
         st = self._ensure_flat()
-        if self._shadow_version != self._param_version():
-            self.refresh_shadow()
+        st.sync()
         return st
 
     def optimizer_groups(self):
@@ -303,13 +267,13 @@ class CLIP(nn.Module):
     def tower_desc(self, which, half=False):
         """the POD description uniir_clip_tower_{fwd,bwd} take (include/uniir_hip.h [TOWER]): raw device pointers into the flat
         fp32 / bf16-shadow / gradient buffers; cached until the flat storage is rebuilt.  half: the fp16 forward's description
-        (dtype16 = 1, 16-bit weights from the fp16 shadow)"""
+        (dtype16 = 1, 16-bit weights from the store's fp16 shadow, which the caller has brought up to date)"""
         from ._lib import ClipBlock, ClipTower
         key = (which, bool(half))
         if key in self._descs:
             return self._descs[key][0]
         cfg, st = self.cfg, self._flat
-        w16 = self._h16 if half else st.w16_buf
+        w16 = st.half_shadow() if half else st.w16_buf
 
         def p(name):
             return st.ptr(st.p32, name)
@@ -349,7 +313,7 @@ class CLIP(nn.Module):
             P = cfg["vision_patch_size"]
             t.heads, t.tokens = W // 64, (cfg["image_resolution"] // P) ** 2 + 1
             t.resolution, t.patch, t.kpad = cfg["image_resolution"], P, self.kpad
-            t.conv16 = (self._conv16h if half else self._conv16).data_ptr()
+            t.conv16 = (st.padded16h(CONV) if half else st.padded16(CONV)).data_ptr()
             t.class_emb, t.pos_emb = p("visual.class_embedding"), p("visual.positional_embedding")
             t.ln_pre_w, t.ln_pre_b = p("visual.ln_pre.weight"), p("visual.ln_pre.bias")
             t.ln_post_w, t.ln_post_b, t.proj16 = p("visual.ln_post.weight"), p("visual.ln_post.bias"), h("visual.proj")
@@ -449,7 +413,9 @@ class CLIP(nn.Module):
             return
         # every lazily built shared buffer (flat storage, 16-bit shadows of the weights) is brought up to date on the forking stream,
         # BEFORE the fork: both towers read them
-        (self._sync_half_shadow if self.precision == "fp16" else self._sync_shadow)()
+        st = self._sync_shadow()
+        if self.precision == "fp16":
+            st.half_shadow()
         main = torch.cuda.current_stream(dev)
         side = self._side_streams.get(dev.index)
         if side is None:
@@ -572,7 +538,7 @@ class _TowerFn(torch.autograd.Function):
             if need_grad:
                 raise RuntimeError("precision='fp16' is the embedder's forward-only path; run it under torch.no_grad() or switch "
                                    "back to precision='bf16' for training")
-            model._sync_half_shadow()
+            model._sync_shadow().half_shadow()
         elif model.precision != "bf16":
             raise RuntimeError(f"unknown precision {model.precision!r}")
         # the whole tower in one C call (csrc/tower.hip); the workspace is the activation stash of the backward

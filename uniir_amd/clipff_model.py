@@ -20,7 +20,7 @@ import math
 import torch
 
 from . import ops
-from .clip_model import image_blocks_f32, text_blocks_f32
+from .clip_model import CONV, image_blocks_f32, text_blocks_f32
 from .fp32_forward import layernorm_f32, linear_f32, rmsnorm_f32
 from .resblocks import block_set_bytes, clip_block_names, tower_bwd, tower_fwd
 
@@ -232,7 +232,7 @@ def _recompute_from(model, which, save, M, R, W, heads, L):
 
 def vision_tokens_fwd(model, image, save, dtype16=torch.bfloat16):
     """clip_ff.py:35-59 -> fp32 [M*T, E] = ln_post(all tokens) @ proj.  dtype16 = torch.float16 (save False): fp16 patches, blocks
-    and ln_post output from the fp16 copies of the weights (CLIP._sync_half_flat() made them); the tokens stay fp32 (EPI_F32)"""
+    and ln_post output from the fp16 copies of the weights (the store's half_shadow()); the tokens stay fp32 (EPI_F32)"""
     half = _check_dtype16("vision tower", dtype16, save)
     cfg, st = model.cfg, model._flat
     dev = image.device
@@ -244,7 +244,7 @@ def vision_tokens_fwd(model, image, save, dtype16=torch.bfloat16):
     p32 = st.p
     patches = torch.empty(M * G_, model.kpad, device=dev, dtype=dtype16)
     ops.call("uniir_patchify_f16" if half else "uniir_patchify", image.float().contiguous(), patches, M, res, P, model.kpad)
-    po = ops.linear_fwd(patches, model._conv16h if half else model._conv16)
+    po = ops.linear_fwd(patches, st.padded16h(CONV) if half else st.padded16(CONV))
     x0 = torch.empty(M * T, W, device=dev, dtype=torch.float32)
     ops.call("uniir_vit_assemble_f16" if half else "uniir_vit_assemble", po, p32("visual.class_embedding"),
              p32("visual.positional_embedding"), x0, M, T, W)
@@ -284,9 +284,9 @@ def vision_tokens_bwd(model, dtok, stash):
     dpo = torch.empty(M * (T - 1), W, device=dev, dtype=torch.bfloat16)
     ops.call("uniir_vit_assemble_bwd", dx0, dpo, G("visual.class_embedding"),
              G("visual.positional_embedding"), M, T, W)
-    model._dconv.zero_()
-    ops.linear_wgrad(dpo, stash["patches"], model._dconv)
-    ops.call("uniir_unpad_add", model._dconv, G("visual.conv1.weight"), W, 3 * P * P, model.kpad)
+    dconv = st.padded_grad(CONV).zero_()
+    ops.linear_wgrad(dpo, stash["patches"], dconv)
+    ops.call("uniir_unpad_add", dconv, G(CONV), W, 3 * P * P, model.kpad)
 
 
 def text_tokens_fwd(model, text, save, dtype16=torch.bfloat16):

@@ -35,6 +35,5 @@ def eval_engine(model_without_ddp, model, data_loader, gpu_id, config):
                            lambda mm, batch, i, n: mm(batch=batch, alpha=config.model.alpha * min(1, i / n)))
     m._mom.p32.copy_(momentum_snapshot)
     m._mom.refresh_shadow()
-    m._refresh_conv()
     print("Restored model queue states and model states from the saved variables.")
     return stats

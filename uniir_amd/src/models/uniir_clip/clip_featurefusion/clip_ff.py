@@ -67,7 +67,6 @@ class CLIPFeatureFusion(nn.Module):
         self.embed_fp16 = env_flag("UNIIR_CLIPFF_EMBED_FP16")
         self.embed_fp32 = env_flag("UNIIR_EMBED_FP32")
         self._t5 = None
-        self._t5_version = -1
         if device is not None and str(device) != "cpu":
             self.to(device)
 
@@ -82,11 +81,7 @@ class CLIPFeatureFusion(nn.Module):
         named = self._t5_named()
         if self._t5 is None or not self._t5.holds(named):
             self._t5 = FlatStore.adopt(named, dev)
-            self._t5_version = -1
-        ver = sum(p._version for _, p in named)
-        if ver != self._t5_version:
-            self._t5.refresh_shadow()
-            self._t5_version = ver
+        self._t5.sync()
         return self._t5
 
     def t5_optimizer_group(self, lr, weight_decay=0.2):
@@ -112,12 +107,9 @@ class CLIPFeatureFusion(nn.Module):
 
     def encode_multimodal_input(self, txt_tensor, img_tensor, txt_mask=None, img_mask=None):
         mode = self._embed_mode()
-        if mode == "fp16":          # the fp16 copies of both stores, rebuilt when the weights moved since they were made
-            self.clip_model._sync_half_flat()
-            self._ensure_t5().half_shadow()
-        else:
-            self.clip_model._sync_shadow()
-            self._ensure_t5()
+        for st in (self.clip_model._sync_shadow(), self._ensure_t5()):
+            if mode == "fp16":          # the fp16 copies of both stores, rebuilt when the weights moved since they were made
+                st.half_shadow()
         if mode == "fp32":          # the fp32 masters of both stores
             return fusion_forward_f32(self, txt_tensor.to(torch.int32).contiguous(), img_tensor.contiguous())
         anchor = torch.zeros(1, device=img_tensor.device, requires_grad=torch.is_grad_enabled())

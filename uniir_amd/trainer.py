@@ -116,7 +116,8 @@ class GradGuard:
 class NativeAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW semantics over flat parameter stores (flat_store.FlatStore): the model's own store -- param group 0
     without weight decay, group 1 with -- and one param group per extra store.  Each store gets one fused AdamW launch per run of
-    consecutive tensors of one group (FlatStore.ranges) and one pair of moment buffers.  It is a real torch Optimizer
+    consecutive tensors of one group (FlatStore.ranges) and one pair of moment buffers; the launches write the masters and the bf16
+    shadow, and FlatStore.kernel_wrote() after them brings the store's other copies along.  It is a real torch Optimizer
     (param_groups / lr schedulers / state_dict work)."""
 
     def __init__(self, clip_model, lr=1e-5, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2, allreduce=True, extra=None,
@@ -206,9 +207,7 @@ class NativeAdamW(torch.optim.Optimizer):
                 b1, b2 = group["betas"]
                 ops.call("uniir_adamw_step", st.p32[lo:hi], st.g32[lo:hi], m[lo:hi], v[lo:hi], st.w16_buf[lo:hi], hi - lo,
                          float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], self.opt_step, 1.0 / world)
-            st.mark_half_stale()               # the kernel wrote p32 and the bf16 shadow itself: an fp16 shadow of the store is behind
-            if i == 0:
-                self.clip._refresh_conv()      # the padded bf16 patch-embedding weights are not part of the shadow
+            st.kernel_wrote()                  # the kernel wrote p32 and the bf16 shadow itself: the store's other copies follow
 
     def _step_guarded(self, main, world, reduced):
         """the rest of step() behind the gradient guard: the all-reduce of every store first, then ONE norm / scan over the AdamW
@@ -225,16 +224,14 @@ class NativeAdamW(torch.optim.Optimizer):
                 self._ranges[i] = (st, st.ranges(group_of))
             work.append((st, m, v, self._ranges[i][1]))
         self.guard.measure([(st, lo, hi) for st, _, _, rs in work for lo, hi, _ in rs], 1.0 / world)
-        for i, (st, m, v, rs) in enumerate(work):
+        for st, m, v, rs in work:
             for lo, hi, gi in rs:
                 group = self.param_groups[gi]
                 b1, b2 = group["betas"]
                 ops.call("uniir_adamw_step_guarded", st.p32[lo:hi], st.g32[lo:hi], m[lo:hi], v[lo:hi], st.w16_buf[lo:hi], hi - lo,
                          float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], self.opt_step, 1.0 / world,
                          self.guard.ctl)
-            st.mark_half_stale()
-            if i == 0:
-                self.clip._refresh_conv()
+            st.kernel_wrote()
         self.guard.publish()
 
     def _resolve_guard(self):
