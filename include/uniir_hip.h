@@ -574,6 +574,40 @@ int uniir_clip_tower_bwd_blocks(const uniir_clip_tower* t, int32_t batch, int32_
                                 int64_t workspace_bytes, void* stream);
 int uniir_clip_tower_bwd_stem(const uniir_clip_tower* t, const void* input, int32_t batch, void* workspace,
                               int64_t workspace_bytes, void* stream);
+/* Where the calls above keep what in the workspace: the plan they carve it with, as data (csrc/tower.hip plan(); this call copies
+ * that plan's fields, it computes nothing itself).  Host arithmetic only -- no device, no stream, like uniir_topk_plan.
+ * live_rows = -1: the dense layout (batch x tokens rows); >= 0: the packed text layout of that many live rows.  Every offset is in
+ * bytes from the workspace base and 256-byte aligned; a region the description does not have is -1 (the vision stem of a text tower,
+ * the pl_* buffers without a pooled last block, every backward transient without save_for_backward, o_x with recompute, o_f / o_g
+ * where they are not stashed).  `total` equals uniir_clip_tower_workspace_bytes[_packed] of the same arguments.
+ *   head / stem   eot int32 [batch]; pooled_rows f32 [batch][W] (the pooled row of the last block's output); pooled bf16 [batch][W]
+ *                 (ln_post of it); patches bf16 [batch G][kpad]; po bf16 [batch G][W] (G = tokens - 1); x0 f32 [rows][W]
+ *   layer i       set base = lay0 + i * lay_stride (lay_stride 0: ONE shared set -- forward-only and recompute); inside a set:
+ *                 o_x f32 [rows][W] (the stream that enters the block), o_qkv bf16 [rows][3W], o_ao bf16 [rows][W],
+ *                 o_lse f32 [batch][heads][tokens], o_x2 f32 [rows][W], o_f / o_g bf16 [rows][4W], o_h1 / o_h2 bf16 [rows][W].
+ *                 recompute: block i's input is at xs0 + i * xs_stride instead.  x_last f32 [rows][W]: the stream after the last block
+ *   pooled block  pl_q, pl_h1, pl_ao, pl_h2 bf16 [batch][W]; pl_x, pl_x2 f32 [batch][W]; pl_lse f32 [batch][heads]; pl_f, pl_g bf16
+ *                 [batch][4W]
+ *   transients    from `tmp` on: g bf16 [rows][4W] (act(f) when it is not stashed), then with save_for_backward df bf16 [rows][4W],
+ *                 dh bf16 [rows][W], dx / dx2 f32 [rows][W], dxb bf16 [rows][W], dqkv bf16 [rows][3W], demb16 bf16 [batch][E],
+ *                 dpooled bf16 [batch][W], drows f32 [batch][W], pl_dxb / pl_dh / pl_dhq bf16 [batch][W], pl_df bf16 [batch][4W],
+ *                 pl_dx2 f32 [batch][W], pl_dqkv bf16 [batch][3W], dx0 f32 [rows][W], dpo bf16 [batch G][W], dconv f32 [W][kpad].
+ * No two regions overlap (with lay_stride 0 every layer uses the one set in turn).  The forward's and the backward's transients are one union behind `tmp`: a forward-only layout ends after
+ * `g`, the training layout continues behind it, and `g` is the only transient both directions write. */
+typedef struct {
+    int64_t total;
+    int64_t rows;                             /* rows of the residual stream: batch x tokens, or live_rows */
+    int32_t save, pool_last, stash_act, recompute;          /* the flags as plan() resolved them (0 / 1) */
+    int64_t eot, pooled_rows, pooled, patches, po, x0;
+    int64_t lay0, lay_stride, o_x, o_qkv, o_ao, o_lse, o_x2, o_f, o_g, o_h1, o_h2;
+    int64_t xs0, xs_stride, x_last;
+    int64_t pl_q, pl_h1, pl_x, pl_ao, pl_lse, pl_x2, pl_h2, pl_f, pl_g;
+    int64_t tmp, g, df, dh, dx, dx2, dxb, dqkv, demb16, dpooled, drows;
+    int64_t pl_dxb, pl_df, pl_dh, pl_dx2, pl_dqkv, pl_dhq;
+    int64_t dx0, dpo, dconv;
+} uniir_clip_tower_layout_t;
+int uniir_clip_tower_layout(const uniir_clip_tower* t, int32_t batch, int32_t live_rows /* -1 = dense */, int32_t save_for_backward,
+                            uniir_clip_tower_layout_t* out);
 /* The TEXT tower on packed rows (exact): only the tokens up to and including each caption's EOT are rows of the residual stream.
  * Under CLIP's causal mask nothing behind the EOT reaches the pooled feature (clip_sf.py:43-44 -> CLIP.encode_text pools at
  * argmax(tokens)), so embeddings and activation gradients are bitwise those of the dense calls above and the weight gradients the same

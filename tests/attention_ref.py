@@ -175,6 +175,22 @@ def backward_reference(q, k, v, out_in, dout, lse_in, *, scale, dtype, valid, bi
     return out
 
 
+def backward_dout_sensitivity(q, k, v, out_in, lse_in, b, *, scale, valid):
+    """The backward is linear in dout.  For a dout known only to within b >= 0 element-wise ([Tq][H][64]; an intermediate that was
+    rebuilt by its own reference), the most dq / dk / dv can move: the backward's operator with every coefficient replaced by its
+    absolute value, applied to b -- dP <= b |v|^T, D <= b . |out_in|, dS <= p (dP + D), dV <= p^T b, dK <= scale dS^T |q|,
+    dQ <= scale dS |k|, each times (1 + u) for the 16-bit store.  -> {"dq", "dk", "dv"} [T][H][64], float64"""
+    Q, K, V, O, B = _hd(q), _hd(k), _hd(v), _hd(out_in), _hd(b)
+    H, Tq, Tk = Q.shape[0], Q.shape[1], K.shape[1]
+    valid = valid.expand(H, Tq, Tk)
+    s = scale * (Q @ K.transpose(1, 2))
+    p = torch.exp(s - lse_in.double()[..., None]).masked_fill(~valid, 0.0)
+    dS = p * (B @ V.abs().transpose(1, 2) + (B * O.abs()).sum(-1)[..., None])
+    up = 1 + U_OUT[torch.bfloat16]
+    return {"dq": (up * abs(scale) * (dS @ K.abs())).permute(1, 0, 2), "dk": (up * abs(scale) * (dS.transpose(1, 2) @ Q.abs())).permute(1, 0, 2),
+            "dv": (up * (p.transpose(1, 2) @ B)).permute(1, 0, 2)}
+
+
 def worst(got, ref, bound):
     """largest |got - ref| / bound (elements with bound 0 count as 0 when exact, inf otherwise; NaN counts as inf)"""
     d = (got.double() - ref).abs()

@@ -247,6 +247,20 @@ def norm_bwd(x, gamma_, dy, eps, rms=False, dres=None, branch_scale=None, dgamma
     return out
 
 
+def norm_bwd_dy_sensitivity(x, gamma_, b, eps, rms=False):
+    """The norm backward is linear in dy.  For a dy known only to within b >= 0 element-wise (an intermediate that no longer exists
+    and was rebuilt by its own reference), the most each result can move: the operator of norm_bwd with every coefficient replaced by
+    its absolute value, applied to b.  With g = |gamma| b:  dx <= rstd (g + mean g + |xhat| mean(g |xhat|)),  dgamma <= sum_rows b |xhat|,
+    dbeta <= sum_rows b,  dx_colsum <= the column sums of the dx term.  A derivation, not a measurement; it carries no margin of its
+    own because b already has its reference's."""
+    xhat, _, rstd, _ = _norm_stats(x, eps, rms)
+    b = b.double()
+    g = b * gamma_.double().abs()[None, :]
+    c1 = xhat.new_zeros(xhat.shape[0], 1) if rms else g.mean(1, keepdim=True)
+    dx = rstd * (g + c1 + xhat.abs() * (g * xhat.abs()).mean(1, keepdim=True))
+    return {"dx_f32": dx, "dx_bf16": (1 + U_BF16) * dx, "dgamma": (b * xhat.abs()).sum(0), "dbeta": b.sum(0), "dx_colsum": dx.sum(0)}
+
+
 # ------------------------------------------------------------------------------------------------------------------------- sgemm
 def chain(A, B):
     """the pinned product: A [M][K], B [K][N] logical fp32 operands -> fp32 [M][N], one fmaf chain in ascending k per element"""

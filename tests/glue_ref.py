@@ -91,9 +91,9 @@ def patchify(img, P, kpad):
     n, ch, res, _ = img.shape
     g = res // P
     rows = img.reshape(n, ch, g, P, g, P).permute(0, 2, 4, 1, 3, 5).reshape(n * g * g, ch * P * P)
-    out = torch.zeros(n * g * g, kpad, dtype=torch.float32, device=img.device)
+    out = torch.zeros(n * g * g, kpad, dtype=img.dtype, device=img.device)
     out[:, :ch * P * P] = rows
-    return out.to(BF16)
+    return out if img.dtype == torch.float64 else out.to(BF16)          # (float64 in: the unrounded operation, tests/tower_ref.py)
 
 
 def vit_assemble(po, cls, pos, n, T):
@@ -101,7 +101,7 @@ def vit_assemble(po, cls, pos, n, T):
     w = cls.numel()
     row = torch.arange(n * T, device=po.device)
     t, im = row % T, row // T
-    src = po.float()[(im * (T - 1) + (t - 1)).clamp_min(0)]
+    src = (po if po.dtype == torch.float64 else po.float())[(im * (T - 1) + (t - 1)).clamp_min(0)]
     src = torch.where((t == 0)[:, None], cls[None, :].expand(n * T, w), src)
     return src + pos[t]
 
@@ -111,7 +111,8 @@ def vit_assemble_bwd(dx, n, T, dclass0, dpos0):
     w = dx.shape[1]
     d = dx.view(n, T, w)
     s = chain_sum(d)
-    return {"dpatch": d[:, 1:].reshape(n * (T - 1), w).to(BF16), "dclass": dclass0 + s[0], "dpos": dpos0 + s}
+    dpatch = d[:, 1:].reshape(n * (T - 1), w)
+    return {"dpatch": dpatch if dx.dtype == torch.float64 else dpatch.to(BF16), "dclass": dclass0 + s[0], "dpos": dpos0 + s}
 
 
 def chain_sum(terms, live=None):

@@ -242,6 +242,7 @@ SIGNATURES = {
     "uniir_topk_ip_multi_workspace_bytes": (c_i64, [c_int, c_int, c_i64, c_int]),
     "uniir_topk_ip_multi": (c_int, [P, P, P, c_i64, c_int, P, c_int, c_int, P, P, P, c_i64, S]),
     "uniir_topk_plan": (c_int, [c_i64, c_int, c_int, c_int, c_int, P]),
+    "uniir_clip_tower_layout": (c_int, [C.POINTER(ClipTower), c_int, c_int, c_int, P]),
 }
 
 
@@ -258,6 +259,27 @@ def topk_plan(rows, dim, nq, k, ncu):
     p = TopkPlan()
     check(load().uniir_topk_plan(rows, dim, nq, k, ncu, C.byref(p)), "uniir_topk_plan")
     return p
+
+
+
+class ClipTowerLayout(C.Structure):
+    """uniir_clip_tower_layout_t (include/uniir_hip.h [TOWER]): where the tower calls keep what in the caller's workspace"""
+    _fields_ = ([("total", c_i64), ("rows", c_i64), ("save", c_int), ("pool_last", c_int), ("stash_act", c_int), ("recompute", c_int)]
+                + [(n, c_i64) for n in (
+                    "eot", "pooled_rows", "pooled", "patches", "po", "x0",
+                    "lay0", "lay_stride", "o_x", "o_qkv", "o_ao", "o_lse", "o_x2", "o_f", "o_g", "o_h1", "o_h2",
+                    "xs0", "xs_stride", "x_last",
+                    "pl_q", "pl_h1", "pl_x", "pl_ao", "pl_lse", "pl_x2", "pl_h2", "pl_f", "pl_g",
+                    "tmp", "g", "df", "dh", "dx", "dx2", "dxb", "dqkv", "demb16", "dpooled", "drows",
+                    "pl_dxb", "pl_df", "pl_dh", "pl_dx2", "pl_dqkv", "pl_dhq", "dx0", "dpo", "dconv")])
+
+
+def clip_tower_layout(tower, batch, live_rows=-1, save_for_backward=1):
+    """the library's workspace plan of a tower description (no device needed); live_rows = -1: the dense layout"""
+    p = ClipTowerLayout()
+    check(load().uniir_clip_tower_layout(C.byref(tower), batch, live_rows, save_for_backward, C.byref(p)), "uniir_clip_tower_layout")
+    return p
+
 
 _lib = None
 

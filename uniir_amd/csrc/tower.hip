@@ -621,6 +621,45 @@ extern "C" int uniir_clip_tower_bwd(const uniir_clip_tower* t, const void* input
     return uniir_clip_tower_bwd_stem(t, input, batch, workspace, workspace_bytes, stream);
 }
 
+// The workspace plan as data (include/uniir_hip.h): every field is copied from the Plan that the calls above carve the workspace
+// with -- nothing is computed a second time.  Host arithmetic only, like uniir_topk_plan.
+extern "C" int uniir_clip_tower_layout(const uniir_clip_tower* t, int32_t batch, int32_t live_rows, int32_t save_for_backward,
+                                       uniir_clip_tower_layout_t* out) {
+    if (!out) return UNIIR_EINVAL;
+    TRY(check_tower(t, batch));
+    if (live_rows >= 0) {
+        if (!t->is_text) return UNIIR_EINVAL;
+        if (live_rows < batch || live_rows > batch * t->tokens) return UNIIR_ESHAPE;
+    } else if (live_rows != -1) {
+        return UNIIR_EINVAL;
+    }
+    const Plan p = plan(t, batch, save_for_backward != 0, live_rows);
+    const bool vis = !t->is_text, sv = p.save, pl = p.pool_last;
+    auto abs_or = [](bool present, int64_t off) { return present ? off : (int64_t)-1; };
+    memset(out, 0, sizeof(*out));
+    out->total = p.total;
+    out->rows = p.R;
+    out->save = sv; out->pool_last = pl; out->stash_act = p.stash_act; out->recompute = p.recompute;
+    out->eot = p.eot; out->pooled_rows = p.rows; out->pooled = p.pooled;
+    out->patches = abs_or(vis, p.patches); out->po = abs_or(vis, p.po); out->x0 = abs_or(vis, p.x0);
+    out->lay0 = p.lay0; out->lay_stride = p.lay_stride;
+    out->o_x = abs_or(!p.recompute, p.o_x); out->o_qkv = p.o_qkv; out->o_ao = p.o_ao; out->o_lse = p.o_lse; out->o_x2 = p.o_x2;
+    out->o_f = abs_or(sv, p.o_f); out->o_g = abs_or(p.stash_act, p.o_g); out->o_h1 = p.o_h1; out->o_h2 = p.o_h2;
+    out->xs0 = abs_or(p.recompute, p.xs0); out->xs_stride = p.recompute ? p.xs_stride : 0;
+    out->x_last = p.x_last;
+    out->pl_q = abs_or(pl, p.pl_q); out->pl_h1 = abs_or(pl, p.pl_h1); out->pl_x = abs_or(pl, p.pl_x); out->pl_ao = abs_or(pl, p.pl_ao);
+    out->pl_lse = abs_or(pl, p.pl_lse); out->pl_x2 = abs_or(pl, p.pl_x2); out->pl_h2 = abs_or(pl, p.pl_h2);
+    out->pl_f = abs_or(pl, p.pl_f); out->pl_g = abs_or(pl, p.pl_g);
+    out->tmp = p.tmp; out->g = p.g;
+    out->df = abs_or(sv, p.df); out->dh = abs_or(sv, p.dh); out->dx = abs_or(sv, p.dx); out->dx2 = abs_or(sv, p.dx2);
+    out->dxb = abs_or(sv, p.dxb); out->dqkv = abs_or(sv, p.dqkv); out->demb16 = abs_or(sv, p.demb16);
+    out->dpooled = abs_or(sv, p.dpooled); out->drows = abs_or(sv, p.drows);
+    out->pl_dxb = abs_or(sv && pl, p.pl_dxb); out->pl_df = abs_or(sv && pl, p.pl_df); out->pl_dh = abs_or(sv && pl, p.pl_dh);
+    out->pl_dx2 = abs_or(sv && pl, p.pl_dx2); out->pl_dqkv = abs_or(sv && pl, p.pl_dqkv); out->pl_dhq = abs_or(sv && pl, p.pl_dhq);
+    out->dx0 = abs_or(sv && vis, p.dx0); out->dpo = abs_or(sv && vis, p.dpo); out->dconv = abs_or(sv && vis, p.dconv);
+    return UNIIR_OK;
+}
+
 // ---- the text tower on PACKED rows (exact): only the tokens up to and including each caption's EOT are rows of the residual stream.
 // Under the causal mask nothing behind the EOT reaches the pooled feature (clip_sf.py:43-44; upstream pools at argmax(tokens)), so the
 // embeddings and every activation gradient are bitwise those of the dense call; weight gradients are the same sums over fewer (all
